@@ -32,10 +32,6 @@ import sys
 import tempfile
 import time
 
-# four busy HIP streams next to torch's; the runtime multiplexes streams onto 4 hardware queues by default, which would serialise
-# stages that share a queue.  Must be set before HIP initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in ("oracle", os.path.join("sc-a-loam_amd", "python"), os.path.join("tools", "synth")):
     sys.path.insert(0, os.path.join(ROOT, p))
@@ -53,10 +49,10 @@ def parse():
     ap.add_argument("--config", type=int, default=2, help="2: KITTI-like HDL-64 (BASELINE.json's metric); 3: MulRan-like OS1-64 stream harness")
     ap.add_argument("--replay", default="lockstep", help="config 3: lockstep (every scan through every stage, as fast as possible) or realtime")
     ap.add_argument("--rate", type=float, default=10.0, help="config 3, realtime: scans per second of the replay (10 Hz sensor)")
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="scans in the timed region, K (with the default --reps and --min-timed-s: the timed steps)")
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--reps", type=int, default=3, help="the timed region of K steps is run at least this many times on consecutive scans; value = median")
-    ap.add_argument("--min-timed-s", type=float, default=0.3, help="repetitions are added until the timed regions together last about this long "
+    ap.add_argument("--reps", type=int, default=1, help="the timed region of K steps is run at least this many times on consecutive scans; value = median")
+    ap.add_argument("--min-timed-s", type=float, default=0.0, help="N > 0: repetitions are added until the timed regions together last about this long "
                     "(a 20-step region is ~6 ms: three of those are three noisy samples)")
     ap.add_argument("--h2d", type=int, default=1, help="N=1: one more repetition with every scan uploaded from host memory inside the timed region (reported beside value)")
     ap.add_argument("--sc-db", type=int, default=5000, help="keyframes pre-filled into the ScanContext database")
@@ -79,6 +75,8 @@ def parse():
     ap.add_argument("--timeline", default="", help="development aid: write (kernel, start ms, stop ms) of every dispatch of six timed steps to this CSV")
     ap.add_argument("--seqs", type=int, default=4, help="N=1: after the single-sequence measurement, this many independent sequences are run through ONE "
                     "pipeline whose kernels share launches (scal_pipeline_create_multi); reported as `batched`, never as `value` (0/1 = skip)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step handed its "
+                    "caller (poses, solver statistics, loop answer, ScanContext descriptor) as DIR/<name>.npy (--gpus 1, config 2)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL) for real runs; gloo only to rehearse N>1 on fewer GPUs")
     return ap.parse_args()
 
@@ -332,8 +330,35 @@ def run_batched(a, S, n_seqs, single_rate, device, threads):
     return out
 
 
+def dump_outputs(d, step, sc):
+    """--dump-outputs: the last timed step's results as float64 .npy files (a few KB in all).  Counts are stored as float64 too;
+    MapStats.insert_path (which of two equivalent insertion paths ran) is left out."""
+    def values(st, skip=()):
+        v = []
+        for name, _ in st._fields_:
+            if name not in skip:
+                x = getattr(st, name)
+                v.extend(x[:] if hasattr(x, "__len__") else [x])
+        return np.array(v, np.float64)
+
+    arrays = {"map_pose": np.concatenate([step["q"], step["t"]]),  # q (x, y, z, w), t: /aft_mapped_to_init
+              "odom_pose": np.concatenate([step["q_odom"], step["t_odom"]]),  # /laser_odom_to_init
+              "map_stats": values(step["map"], skip=("insert_path",)), "odom_stats": values(step["odom"])}
+    lp = step["loop"]
+    if lp is not None:
+        arrays["loop"] = np.array([lp["loop_id"], lp["yaw"], lp["min_dist"], lp["nn_idx"], lp["nn_shift"]], np.float64)
+        arrays["loop_candidates"] = np.stack([lp["cand"], lp["cand_d"], lp["cand_sc"], lp["cand_shift"]], 1).astype(np.float64)
+    desc, key = sc.get(sc.size() - 1)  # the last timed scan is the newest keyframe
+    arrays["sc_descriptor"], arrays["sc_ringkey"] = desc.astype(np.float64), key.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
 def main():
     a = parse()
+    if a.dump_outputs and (a.config != 2 or a.gpus != 1):
+        raise SystemExit("--dump-outputs needs --config 2 --gpus 1")
     if a.config == 3:
         return run_stream(a)
     rank = int(os.environ.get("RANK", "0"))
@@ -368,7 +393,8 @@ def main():
     from scaloam.sharded import TreePeriodBook
 
     K, W = a.steps, a.warmup
-    # enough repetitions that the timed regions together last ~min_timed_s (estimated at 0.3 ms per step), at most 1600 timed steps
+    # repetitions on request: --reps, or enough that the timed regions together last ~min_timed_s (estimated at 0.3 ms per step), at most
+    # 1600 timed steps.  By default R = 1: the timed steps are exactly the K of --steps.
     R = max(1, a.reps, min(int(math.ceil(a.min_timed_s / (K * 0.3e-3))), max(1, 1600 // K)))
     do_h2d = bool(a.h2d) and world == 1
     P_STEPS = a.prof_steps if (a.prof_every > 0 and not a.timeline) else 0
@@ -393,6 +419,7 @@ def main():
     stats = dict(loops=0, blocks=0, stack_pts=0, solved=0, map_pts=0, win_pts=0, edge=0, plane=0, evals=0, odom_blocks=0, odom_evals=0)
     lm_bytes = dict(map=0.0, map_launches=0, odom=0.0, odom_launches=0, map_blocks=0, map_evals=0)
     last_pose = {}
+    last_step = {}  # what the newest step handed its caller (--dump-outputs)
     sc_max = a.sc_db // world + total * world + 64
 
     P = reg = od = mp = None
@@ -506,6 +533,7 @@ def main():
 
     def on_result(res):
         last_pose["q"], last_pose["t"] = res["q"].tolist(), res["t"].tolist()
+        last_step.update(res)
         account_step(res["map"], res["odom"], res["loop"])
         if world > 1:
             feed_exchange(res)
@@ -546,6 +574,7 @@ def main():
             qlc, tlc, qw, tw, ost = od.step_features(reg)
             qm, tm, mst = mp.process_features(reg, qw, tw)
             last_pose["q"], last_pose["t"] = qm.tolist(), tm.tolist()
+            last_step.update(q=qm, t=tm, q_odom=qw, t_odom=tw, map=mst, odom=ost)
             if world == 1:
                 sc.insert_features(reg)
                 r = sc.detectLoopClosureID()
@@ -564,6 +593,7 @@ def main():
                 rec = allr.cpu().numpy().reshape(world, world, 3, 24)[:, rank]
                 r = S.merge_candidates([S.SCCand.from_buffer_copy(rec[s, c].tobytes()) for s in range(world) for c in range(3)], 0.4)
             account_step(mst, ost, r)
+            last_step["loop"] = r
         mp.finish()
 
     def fence():
@@ -611,6 +641,10 @@ def main():
     t_wall1 = time.time()
     final_pose_resident = dict(last_pose)
     loops_timed = int(stats["loops"])
+    if a.dump_outputs:
+        if sc.size() != a.sc_db + W + R * K:
+            raise RuntimeError(f"ScanContext database holds {sc.size()} keyframes, expected {a.sc_db + W + R * K}")
+        dump_outputs(a.dump_outputs, last_step, sc)
     dt_h2d = None
     if do_h2d:  # PCIe-inclusive leg: every scan starts in (pageable) host memory; never reported as `value`
         k0 = W + R * K

@@ -9,6 +9,10 @@ import sys
 
 import numpy as np
 import pytest
+# torch ships its own HIP and HSA runtimes under the same sonames as the system ones.  Loaded first, they are the ones
+# libscaloam_hip binds to; loaded after the library (a CPU test importing torch between GPU tests), they would be a second
+# runtime in the process and whichever initialises second finds no device.
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
