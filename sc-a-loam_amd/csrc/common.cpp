@@ -1,5 +1,6 @@
 // Error reporting and device selection for libscaloam_hip.so.
 #include "common.hpp"
+#include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <memory>
@@ -205,7 +206,7 @@ struct DevStream {
     int refs = 0;
 };
 DevStream g_streams[64][6];  // [device][lane], see common.hpp
-int g_stream_mode = 0;
+std::atomic<int> g_stream_mode{0};  // scal_set_stream_mode: the layout of contexts created through the public entry points
 }  // namespace
 
 int acquire_stream(int device, hipStream_t* out, int lane) {
@@ -229,14 +230,10 @@ int acquire_stream(int device, hipStream_t* out, int lane) {
     return SCAL_OK;
 }
 
-int stream_mode() {
-    std::lock_guard<std::mutex> lk(g_stream_mu);
-    return g_stream_mode;
-}
+StreamLayout default_stream_layout() { return g_stream_mode.load() ? StreamLayout::PerStage : StreamLayout::Shared; }
 
-int stage_lane(int stage) {
-    std::lock_guard<std::mutex> lk(g_stream_mu);
-    if (g_stream_mode == 0) return stage == STAGE_MAP_PREFETCH ? 2 : 0;
+int stage_lane(StreamLayout layout, int stage) {
+    if (layout == StreamLayout::Shared) return stage == STAGE_MAP_PREFETCH ? 2 : 0;
     // Four streams, not five: an MI355X advances four dependent kernel chains at full rate, and with more streams than that they
     // all slow down together (tools/stream_probe.hip: 0.62 M kernels/s with 4 streams, 0.25-0.35 M with 6-8).  The side jobs that
     // only depend on stage A are spread so that the four chains come out about equally long (tools/gpu_chains.sh): stage C's surf
@@ -418,7 +415,6 @@ extern "C" int scal_set_stream_mode(int mode) {
         scal::set_error("scal_set_stream_mode: mode must be 0 or 1");
         return SCAL_E_ARG;
     }
-    std::lock_guard<std::mutex> lk(scal::g_stream_mu);
     scal::g_stream_mode = mode;
     return SCAL_OK;
 }

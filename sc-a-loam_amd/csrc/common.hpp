@@ -7,6 +7,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include <utility>
 #include <mutex>
 #include "../../include/scaloam_hip.h"
 #include "batch.hpp"
@@ -37,18 +38,78 @@ void set_error(const char* fmt, ...);
 
 // selects the device and verifies it is a gfx950 part: the product path must fail loudly otherwise
 int select_device(int device);
-// Streams are shared per device and reference counted.  Lane 0 is the pipeline's in-order stream: by default stages A -> B -> C
-// of a scan all run there, strictly dependent, no cross-stream events.  Lanes 1 and 2 carry work that only depends on stage A
-// (1: ScanContext with scal_sc_config::side_stream, 2: scal_map_prefetch_features).  With scal_set_stream_mode(1) (set before
-// the contexts are created) every stage gets its own stream - A: 0, D: 1, C prefetch: 2, B: 3, C: 4 - so that consecutive
-// scans overlap the way the reference's four ROS nodes do; every hand-over between contexts is ordered by events in both
-// directions (features_wait_done / features_note_reader).  Lane 5 is free for a context that must not queue behind another one
-// of its kind (scal_sc_config::side_stream = 5: the sharded database next to the descriptor builder, bench.py --gpus N).
+// Streams are shared per device and reference counted (held through LaneStream).  Lane 0 is the pipeline's in-order stream.  A stage
+// context's lane follows the StreamLayout it is created with (the public scal_*_create take scal_set_stream_mode's, once, at entry):
+// - Shared: stages A -> B -> C of a scan all run on lane 0, strictly dependent, no cross-stream events.  Lanes 1 and 2 carry work
+//   that only depends on stage A (1: ScanContext with scal_sc_config::side_stream, 2: scal_map_prefetch_features).
+// - PerStage (scal_pipeline_create): every stage gets its own stream - A: 0, D: 1, C prefetch: 2, B: 3, C: 4, folded onto four lanes
+//   by stage_lane - so that consecutive scans overlap the way the reference's four ROS nodes do; every hand-over between contexts
+//   is ordered by events in both directions (features_wait_done / features_note_reader).
+// Lane 5 is free for a context that must not queue behind another one of its kind (scal_sc_config::side_stream = 5: the sharded
+// database next to the descriptor builder, bench.py --gpus N).
+enum class StreamLayout { Shared, PerStage };
 enum { STAGE_FEATURES = 0, STAGE_SC = 1, STAGE_ODOM = 3, STAGE_MAP = 4, STAGE_MAP_PREFETCH = 2, STAGE_SC_FILTER = 5 };
-int stage_lane(int stage);
-int stream_mode();  // the value scal_set_stream_mode last set
+int stage_lane(StreamLayout layout, int stage);
+StreamLayout default_stream_layout();
 int acquire_stream(int device, hipStream_t* out, int lane = 0);
 void release_stream(int device, int lane = 0);
+// scal_odom_create / scal_map_create / scal_sc_create with an explicit layout
+int odom_create(const scal_odom_config* cfg, StreamLayout layout, scal_odom_t** out);
+int map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t** out);
+int sc_create(const scal_sc_config* cfg, StreamLayout layout, scal_sc_t** out);
+
+// Owning handles in the style of DevBuf (move-only): one reference to a shared stream, released when the handle goes away ...
+struct LaneStream {
+    hipStream_t s = nullptr;
+    int device = 0, lane = 0;
+    LaneStream() = default;
+    LaneStream(LaneStream&& o) noexcept { *this = std::move(o); }
+    LaneStream& operator=(LaneStream&& o) noexcept {
+        release();
+        std::swap(s, o.s);
+        device = o.device, lane = o.lane;
+        return *this;
+    }
+    ~LaneStream() { release(); }
+    operator hipStream_t() const { return s; }
+    int acquire(int dev, int ln) {
+        release();
+        device = dev, lane = ln;
+        return acquire_stream(dev, &s, ln);
+    }
+    void release() {
+        if (s) release_stream(device, lane);
+        s = nullptr;
+    }
+};
+// ... and an event, destroyed with its handle; ensure() creates the ones a context only needs once it is used in a particular way
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept { *this = std::move(o); }
+    Event& operator=(Event&& o) noexcept {
+        reset();
+        std::swap(e, o.e);
+        return *this;
+    }
+    ~Event() { reset(); }
+    operator hipEvent_t() const { return e; }
+    int create(unsigned flags) {
+        reset();
+        return ensure(flags);
+    }
+    int ensure(unsigned flags) {
+        const hipError_t r = e ? hipSuccess : hipEventCreateWithFlags(&e, flags);
+        if (r == hipSuccess) return SCAL_OK;
+        set_error("hipEventCreateWithFlags failed: %s", hipGetErrorString(r));
+        e = nullptr;
+        return SCAL_E_HIP;
+    }
+    void reset() {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+};
 
 template <class T>
 struct DevBuf {

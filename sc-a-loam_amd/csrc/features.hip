@@ -701,13 +701,14 @@ using namespace scal;
 
 struct scal_features {
     scal_features_config cfg;
-    hipStream_t stream = nullptr;
+    // the stream and the events are released by `delete c`, after scal_features_destroy has synchronised with them
+    LaneStream stream;
     // last read of this context's buffers by each consumer stream (B, C, C's prefetch, D may all run on their own)
     static constexpr int MAX_READERS = 8;
     hipStream_t reader_stream[MAX_READERS] = {};
-    hipEvent_t reader_ev[MAX_READERS] = {};
+    Event reader_ev[MAX_READERS];
     bool reader_pending[MAX_READERS] = {};
-    hipEvent_t done_ev = nullptr;    // end of the most recent run, recorded on demand
+    Event done_ev;  // end of the most recent run, recorded on demand
     bool done_recorded = false;
     unsigned generation = 0;  // runs so far (FeatDeviceView::generation)
     bool cross_stream_consumers = false;
@@ -717,7 +718,7 @@ struct scal_features {
     // pinned staging of host scans (two slots, each guarded by the event of the upload that last read it): the upload is an
     // ordinary stream-ordered copy and the caller's buffer is free again when scal_features_run returns
     PinBuf<float> h_in[2];
-    hipEvent_t up_ev[2] = {};
+    Event up_ev[2];
     bool up_used[2] = {};
     int up_next = 0;
     DevBuf<signed char> d_ring;
@@ -765,7 +766,7 @@ FeatDeviceView features_view(scal_features* c) {
 int features_wait_done(scal_features* c, hipStream_t consumer_stream) {
     if (consumer_stream == c->stream) return SCAL_OK;
     std::lock_guard<std::mutex> lk(c->ev_mu);
-    if (!c->done_ev) SCAL_HIP(hipEventCreateWithFlags(&c->done_ev, EV_DEVICE_ONLY));
+    SCAL_TRY(c->done_ev.ensure(EV_DEVICE_ONLY));
     c->cross_stream_consumers = true;
     if (!c->done_recorded) {
         // At once, also under a recorder: `done_recorded` tells the consumers on OTHER host threads (the pipeline queues stage B, the
@@ -788,7 +789,7 @@ int features_note_reader(scal_features* c, hipStream_t consumer_stream) {
         return SCAL_E_STATE;
     }
     c->reader_stream[slot] = consumer_stream;
-    if (!c->reader_ev[slot]) SCAL_HIP(hipEventCreateWithFlags(&c->reader_ev[slot], EV_DEVICE_ONLY));
+    SCAL_TRY(c->reader_ev[slot].ensure(EV_DEVICE_ONLY));
     SCAL_HIP(op_event_record(c->reader_ev[slot], consumer_stream));
     c->reader_pending[slot] = true;
     return SCAL_OK;
@@ -843,17 +844,13 @@ extern "C" int scal_features_create(const scal_features_config* cfg, scal_featur
     A(c->d_P.alloc(1));
     A(c->d_boxparts.alloc((size_t)6 * (div_up(cap, 256) + 1)));
     A(c->h_P.alloc(1));
-    if (rc == SCAL_OK && acquire_stream(c->cfg.device, &c->stream) != SCAL_OK) {
-        set_error("hipStreamCreate failed");
-        rc = SCAL_E_HIP;
-    }
+    if (rc == SCAL_OK) rc = c->stream.acquire(c->cfg.device, 0);
     // Initialisation goes through the context's own stream.  hipMemset on the legacy null stream returns before the fill has
     // run and is not ordered against a hipStreamNonBlocking stream: a fill landing after the first k_pre cleared
     // FeatParams::empty again (the E_EMPTY that test_errors once missed).
     if (rc == SCAL_OK && (op_memset_async(c->d_P.p, 0, sizeof(FeatParams), c->stream) != hipSuccess || op_stream_synchronize(c->stream) != hipSuccess))
         rc = SCAL_E_HIP;
-    for (int k = 0; k < 2 && rc == SCAL_OK; ++k)
-        if (hipEventCreateWithFlags(&c->up_ev[k], hipEventDisableTiming) != hipSuccess) rc = SCAL_E_HIP;
+    for (int k = 0; k < 2 && rc == SCAL_OK; ++k) rc = c->up_ev[k].create(hipEventDisableTiming);
     if (rc == SCAL_OK) {
         const int lds = sizeof(unsigned long long) * RING_MAX + RING_MAX + 16;
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_ring), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
@@ -873,17 +870,8 @@ extern "C" void scal_features_destroy(scal_features_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     for (int i = 0; i < scal_features::MAX_READERS; ++i)
-        if (c->reader_ev[i]) {  // consumers on other streams must be done with the buffers
-            (void)op_event_synchronize(c->reader_ev[i]);
-            (void)hipEventDestroy(c->reader_ev[i]);
-        }
-    if (c->done_ev) (void)hipEventDestroy(c->done_ev);
-    for (int k = 0; k < 2; ++k)
-        if (c->up_ev[k]) (void)hipEventDestroy(c->up_ev[k]);
-    if (c->stream) {
-        (void)op_stream_synchronize(c->stream);
-        release_stream(c->cfg.device);
-    }
+        if (c->reader_ev[i]) (void)op_event_synchronize(c->reader_ev[i]);  // consumers on other streams must be done with the buffers
+    if (c->stream) (void)op_stream_synchronize(c->stream);
     delete c;
 }
 

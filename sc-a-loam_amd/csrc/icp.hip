@@ -402,7 +402,7 @@ using namespace scal;
 
 struct scal_icp {
     scal_icp_config cfg;
-    hipStream_t stream = nullptr;
+    LaneStream stream;  // released by `delete c`, after scal_icp_destroy has synchronised it
     DevBuf<float4> src, cur, tgt;
     const float4* tgt_cur = nullptr;  // the target of the alignment in flight: tgt, or the caller's device cloud
     DevBuf<unsigned long long> best;
@@ -434,7 +434,7 @@ extern "C" int scal_icp_create(const scal_icp_config* cfg, scal_icp_t** out) {
     A(c->h_sums.alloc(ICP_NSUM));
     A(c->grid.alloc(1)); A(c->mm.alloc(6)); A(c->count.alloc(ICP_NCELL)); A(c->start.alloc(ICP_NCELL + 4)); A(c->bsum.alloc(256));
     A(c->cell_of.alloc(cfg->max_target)); A(c->sorted.alloc(cfg->max_target)); A(c->un_list.alloc(cfg->max_source)); A(c->d_nun.alloc(2));
-    if (rc == SCAL_OK && acquire_stream(cfg->device, &c->stream) != SCAL_OK) rc = SCAL_E_HIP;
+    if (rc == SCAL_OK) rc = c->stream.acquire(cfg->device, 0);
     if (rc == SCAL_OK) {  // initialised on the context's own stream (the legacy null stream is not ordered against it)
         const unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
         if (hipMemcpyAsync(c->mm.p, init, sizeof init, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -461,10 +461,7 @@ extern "C" int scal_icp_set_search(scal_icp_t* c, int mode) {
 extern "C" void scal_icp_destroy(scal_icp_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
-    if (c->stream) {
-        (void)hipStreamSynchronize(c->stream);
-        release_stream(c->cfg.device);
-    }
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
     delete c;
 }
 

@@ -130,7 +130,7 @@ using namespace scal;
 
 struct scal_mapmerge {
     scal_mapmerge_config cfg;
-    hipStream_t stream = nullptr;
+    LaneStream stream;  // released by `delete c`, after scal_mapmerge_destroy has synchronised it
     long long cap = 0;
     DevBuf<float4> out, stage;
     PinBuf<float4> h_stage;     // pinned staging of host frames, block descriptors and poses (stream-ordered uploads)
@@ -167,7 +167,7 @@ extern "C" int scal_mapmerge_create(const scal_mapmerge_config* cfg, scal_mapmer
     A(c->h_stage.alloc(static_cast<size_t>(cfg->max_frame_points)));
     A(c->d_total.alloc(1));
     A(c->d_error.alloc(1));
-    if (rc == SCAL_OK && acquire_stream(cfg->device, &c->stream) != SCAL_OK) rc = SCAL_E_HIP;
+    if (rc == SCAL_OK) rc = c->stream.acquire(cfg->device, 0);
     if (rc == SCAL_OK && (hipMemsetAsync(c->d_total.p, 0, sizeof(long long), c->stream) != hipSuccess ||
                           hipMemsetAsync(c->d_error.p, 0, sizeof(int), c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess))
         rc = SCAL_E_HIP;
@@ -182,10 +182,7 @@ extern "C" int scal_mapmerge_create(const scal_mapmerge_config* cfg, scal_mapmer
 extern "C" void scal_mapmerge_destroy(scal_mapmerge_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
-    if (c->stream) {
-        (void)hipStreamSynchronize(c->stream);
-        release_stream(c->cfg.device);
-    }
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
     delete c;
 }
 

@@ -1513,10 +1513,9 @@ struct MapStep {
 
 struct scal_map {
     scal_map_config cfg;
-    int lane = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t side = nullptr;          // side stream for scal_map_prefetch_features (lazily acquired)
-    int side_lane = 2;
+    // the streams and the events are released by `delete c`, after scal_map_destroy has synchronised the streams
+    LaneStream stream;
+    LaneStream side;                     // side stream for scal_map_prefetch_features
     static constexpr int NSETS = 8;      // input sets: steps in flight (<= MAX_STEPS) + prefetches queued ahead (<= MAX_PF) + 1
     static constexpr int MAX_STEPS = 4;  // steps whose insertion has not been confirmed
     static constexpr int MAX_PF = 3;
@@ -1532,10 +1531,10 @@ struct scal_map {
     Prefetch pf_half[MAX_PF];  // scal_map_prefetch_begin done, scal_map_prefetch_finish still to come (FIFO)
     int n_half = 0;
     int next_set = 0;  // ring allocation of input sets
-    hipEvent_t ev_pre[NSETS] = {};    // side stream: surf stack ready
-    hipEvent_t ev_pre_a[NSETS] = {};  // features stream: corner stack ready
+    Event ev_pre[NSETS];    // side stream: surf stack ready
+    Event ev_pre_a[NSETS];  // features stream: corner stack ready
     std::deque<MapStep> steps;
-    hipEvent_t ev_pose[NSLOTS] = {}, ev_done[NSLOTS] = {};
+    Event ev_pose[NSLOTS], ev_done[NSLOTS];
     int next_slot = 0;
     PinBuf<MapResult> res;
     // Ceres-adapter mode (scal_map_adapter_begin ... _finish): the step whose solve the caller drives
@@ -1607,7 +1606,7 @@ struct scal_map {
     }
 };
 
-extern "C" int scal_map_create(const scal_map_config* cfg, scal_map_t** out) {
+int scal::map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t** out) {
     if (!cfg || !out || cfg->max_scan_points <= 0 || cfg->max_map_points <= 0 || !(cfg->line_res > 0) || !(cfg->plane_res > 0)) {
         set_error("scal_map_create: bad argument");
         return SCAL_E_ARG;
@@ -1684,19 +1683,18 @@ extern "C" int scal_map_create(const scal_map_config* cfg, scal_map_t** out) {
         }
     }
     if (rc == SCAL_OK) std::memset(static_cast<void*>(c->res.p), 0, sizeof(MapResult) * scal_map::NSLOTS);  // seq_pose / seq_done: no step has reported
-    c->lane = stage_lane(STAGE_MAP);
     if (rc == SCAL_OK) rc = lm_check_residency<AssocFit, MapPoseDone>(c->cfg.device);
     // per device, hence here and not behind a process-wide flag at the first launch
     if (rc == SCAL_OK && hipFuncSetAttribute(reinterpret_cast<const void*>(k_merge_keys), hipFuncAttributeMaxDynamicSharedMemorySize,
                                              static_cast<int>(sizeof(unsigned long long) * MERGE_MAX)) != hipSuccess)
         rc = SCAL_E_HIP;
-    if (rc == SCAL_OK && acquire_stream(c->cfg.device, &c->stream, c->lane) != SCAL_OK) rc = SCAL_E_HIP;
-    // the prefetch's side stream is fixed HERE, under the stream mode the context is created in (a pipeline restores the caller's mode
-    // after creating its contexts: a lane looked up at the first prefetch would be a fifth busy stream - measured: -20 % throughput)
-    if (rc == SCAL_OK && acquire_stream(c->cfg.device, &c->side, c->side_lane = stage_lane(STAGE_MAP_PREFETCH)) != SCAL_OK) rc = SCAL_E_HIP;
+    if (rc == SCAL_OK) rc = c->stream.acquire(c->cfg.device, stage_lane(layout, STAGE_MAP));
+    // the prefetch's side stream: in the per-stage layout the lane it shares with ScanContext's keyframe filter (a fifth busy stream
+    // next to the pipeline's four measured -20 % throughput)
+    if (rc == SCAL_OK) rc = c->side.acquire(c->cfg.device, stage_lane(layout, STAGE_MAP_PREFETCH));
     for (int k = 0; k < scal_map::NSLOTS && rc == SCAL_OK; ++k) {
-        if (hipEventCreateWithFlags(&c->ev_pose[k], hipEventDisableTiming) != hipSuccess) rc = SCAL_E_HIP;
-        if (rc == SCAL_OK && hipEventCreateWithFlags(&c->ev_done[k], hipEventDisableTiming) != hipSuccess) rc = SCAL_E_HIP;
+        rc = c->ev_pose[k].create(hipEventDisableTiming);
+        if (rc == SCAL_OK) rc = c->ev_done[k].create(hipEventDisableTiming);
     }
     if (rc == SCAL_OK) {
         // Everything is initialised on the context's own stream (the legacy null stream is not ordered against it).
@@ -1722,25 +1720,13 @@ extern "C" int scal_map_create(const scal_map_config* cfg, scal_map_t** out) {
     return SCAL_OK;
 }
 
+extern "C" int scal_map_create(const scal_map_config* cfg, scal_map_t** out) { return map_create(cfg, default_stream_layout(), out); }
+
 extern "C" void scal_map_destroy(scal_map_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
-    if (c->stream) {
-        (void)op_stream_synchronize(c->stream);
-        release_stream(c->cfg.device, c->lane);
-    }
-    if (c->side) {
-        (void)op_stream_synchronize(c->side);
-        release_stream(c->cfg.device, c->side_lane);
-    }
-    for (int k = 0; k < scal_map::NSETS; ++k) {
-        if (c->ev_pre[k]) (void)hipEventDestroy(c->ev_pre[k]);
-        if (c->ev_pre_a[k]) (void)hipEventDestroy(c->ev_pre_a[k]);
-    }
-    for (int k = 0; k < scal_map::NSLOTS; ++k) {
-        if (c->ev_pose[k]) (void)hipEventDestroy(c->ev_pose[k]);
-        if (c->ev_done[k]) (void)hipEventDestroy(c->ev_done[k]);
-    }
+    if (c->stream) (void)op_stream_synchronize(c->stream);
+    if (c->side) (void)op_stream_synchronize(c->side);
     delete c;
 }
 
@@ -2431,10 +2417,8 @@ extern "C" int scal_map_prefetch_begin(scal_map_t* c, scal_features_t* feat) {
         return SCAL_E_STATE;
     }
     const int nset = c->alloc_set();
-    if (!c->ev_pre[nset]) {
-        SCAL_HIP(hipEventCreateWithFlags(&c->ev_pre[nset], EV_DEVICE_ONLY));
-        SCAL_HIP(hipEventCreateWithFlags(&c->ev_pre_a[nset], EV_DEVICE_ONLY));
-    }
+    SCAL_TRY(c->ev_pre[nset].ensure(EV_DEVICE_ONLY));
+    SCAL_TRY(c->ev_pre_a[nset].ensure(EV_DEVICE_ONLY));
     // The gather (it also stores per-block bounding boxes of the surf cloud for the filter) and the small corner filter ride on the
     // features context's own stream, right behind stage A; the surf filter runs on the side stream, which it shares with
     // ScanContext's keyframe filter.  (More than four busy streams slow every stream down on this GPU; see stage_lane().)

@@ -497,9 +497,9 @@ using namespace scal;
 
 struct scal_odom {
     scal_odom_config cfg;
-    hipStream_t stream = nullptr;
+    // the stream and the events are released by `delete c`, after scal_odom_destroy has synchronised the stream
+    LaneStream stream;
     int cap = 0, feat_cap = 0, slot_cap = 0;
-    int lane = 0;
     bool systemInited = false;
     // steps enqueued and not collected yet: B(k+1) only needs B(k)'s device state, so it can be queued right behind it
     static constexpr int MAX_STEPS = 4;
@@ -508,7 +508,7 @@ struct scal_odom {
         bool solve;
     };
     std::deque<Pending> pending;
-    hipEvent_t ev[MAX_STEPS] = {};
+    Event ev[MAX_STEPS];
     int next_slot = 0;
     double q_w_curr[4] = {0, 0, 0, 1}, t_w_curr[3] = {0, 0, 0};  // :93-94
     DevBuf<float> aos;
@@ -547,7 +547,7 @@ struct scal_odom {
     FactorSoA factors() { return FactorSoA{fvalid.p, fkind.p, fcp.p, fpa.p, fpb.p, slot_cap}; }
 };
 
-extern "C" int scal_odom_create(const scal_odom_config* cfg, scal_odom_t** out) {
+int scal::odom_create(const scal_odom_config* cfg, StreamLayout layout, scal_odom_t** out) {
     if (!cfg || !out || cfg->max_points <= 0) {
         set_error("scal_odom_create: bad argument");
         return SCAL_E_ARG;
@@ -575,11 +575,9 @@ extern "C" int scal_odom_create(const scal_odom_config* cfg, scal_odom_t** out) 
     A(c->bl_live.alloc(c->slot_cap)); A(c->bl_rowoff.alloc(c->slot_cap + 1)); A(c->bl_counts.alloc(2)); A(c->h_counts.alloc(2)); A(c->h_x7.alloc(8));
     A(c->d_x7.alloc(8)); A(c->d_res.alloc(3 * (size_t)c->slot_cap)); A(c->d_jac.alloc(21 * (size_t)c->slot_cap)); A(c->d_blocks.alloc(10 * (size_t)c->slot_cap));
     A(c->d_st.alloc(1)); A(c->d_C.alloc(1)); A(c->h_st.alloc(scal_odom::MAX_STEPS)); A(c->h_up.alloc(1));
-    c->lane = stage_lane(STAGE_ODOM);
     if (rc == SCAL_OK) rc = lm_check_residency<LMNoHook, LMNoHook>(c->cfg.device);
-    if (rc == SCAL_OK && acquire_stream(c->cfg.device, &c->stream, c->lane) != SCAL_OK) rc = SCAL_E_HIP;
-    for (int k = 0; k < scal_odom::MAX_STEPS && rc == SCAL_OK; ++k)
-        if (hipEventCreateWithFlags(&c->ev[k], hipEventDisableTiming) != hipSuccess) rc = SCAL_E_HIP;
+    if (rc == SCAL_OK) rc = c->stream.acquire(c->cfg.device, stage_lane(layout, STAGE_ODOM));
+    for (int k = 0; k < scal_odom::MAX_STEPS && rc == SCAL_OK; ++k) rc = c->ev[k].create(hipEventDisableTiming);
     if (rc == SCAL_OK) {
         // everything is initialised on the context's own stream (the legacy null stream is not ordered against it)
         if (op_memset_async(c->lm_sync.p, 0, sizeof(LMSync), c->stream) != hipSuccess) rc = SCAL_E_HIP;
@@ -600,15 +598,12 @@ extern "C" int scal_odom_create(const scal_odom_config* cfg, scal_odom_t** out) 
     return SCAL_OK;
 }
 
+extern "C" int scal_odom_create(const scal_odom_config* cfg, scal_odom_t** out) { return odom_create(cfg, default_stream_layout(), out); }
+
 extern "C" void scal_odom_destroy(scal_odom_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
-    if (c->stream) {
-        (void)op_stream_synchronize(c->stream);
-        release_stream(c->cfg.device, c->lane);
-    }
-    for (int k = 0; k < scal_odom::MAX_STEPS; ++k)
-        if (c->ev[k]) (void)hipEventDestroy(c->ev[k]);
+    if (c->stream) (void)op_stream_synchronize(c->stream);
     delete c;
 }
 

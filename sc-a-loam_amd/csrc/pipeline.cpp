@@ -442,8 +442,6 @@ int create(const scal_pipeline_config* cfg, int n_seqs, scal_pipeline_t** out) {
         return SCAL_E_ARG;
     }
     SCAL_TRY(select_device(cfg->device));
-    const int mode_before = stream_mode();
-    SCAL_TRY(scal_set_stream_mode(1));  // one stream per stage; the contexts created below pick their lanes from it
     auto* p = new scal_pipeline();
     p->cfg = *cfg, p->ring = ring, p->depth = depth, p->S = n_seqs;
     int rc = SCAL_OK;
@@ -459,23 +457,23 @@ int create(const scal_pipeline_config* cfg, int n_seqs, scal_pipeline_t** out) {
         if (rc == SCAL_OK) {
             scal_odom_config oc{};
             oc.max_points = cfg->max_points, oc.device = cfg->device;
-            rc = scal_odom_create(&oc, &p->od[q]);
+            rc = odom_create(&oc, StreamLayout::PerStage, &p->od[q]);  // one stream per stage
         }
         if (rc == SCAL_OK) {
             scal_map_config mc{};
             mc.line_res = cfg->line_res, mc.plane_res = cfg->plane_res, mc.max_scan_points = cfg->max_points, mc.max_map_points = cfg->max_map_points;
             mc.device = cfg->device;
-            rc = scal_map_create(&mc, &p->mp[q]);
+            rc = map_create(&mc, StreamLayout::PerStage, &p->mp[q]);
         }
         if (rc == SCAL_OK && p->sc_on()) {
             scal_sc_config sc{};
             sc.max_radius = cfg->sc_max_radius, sc.dist_thres = cfg->sc_dist_thres, sc.max_keyframes = cfg->sc_max_keyframes;
             sc.float_math = cfg->float_math, sc.device = cfg->device, sc.n_shards = 1, sc.shard = 0, sc.side_stream = env_int("SCALOAM_PIPE_SC_LANE", 1, 0, 5);
             // ScanContext entirely on the side stream it shares with stage C's surf filter (keyframe filter, descriptor, search: one in-order
-            // chain, no cross-stream wait).  With the descriptor + search behind stage B instead (scal_set_stream_mode(1)'s own split, lane 0
+            // chain, no cross-stream wait).  With the descriptor + search behind stage B instead (the per-stage layout's own split, lane 0
             // here) stage B's chain queues behind a search that waits for the keyframe filter on the other stream: 3250-3360 scans/s against
             // 3660 on one box (tools/gpu_pipe_knobs.sh).
-            rc = scal_sc_create(&sc, &p->sc[q]);
+            rc = sc_create(&sc, StreamLayout::PerStage, &p->sc[q]);
             if (rc == SCAL_OK && cfg->sc_mode == SCAL_PIPE_SC_DESCRIPTOR) {
                 if (cfg->d_desc_ring) {
                     p->d_desc = cfg->d_desc_ring;
@@ -488,7 +486,6 @@ int create(const scal_pipeline_config* cfg, int n_seqs, scal_pipeline_t** out) {
             }
         }
     }
-    (void)scal_set_stream_mode(mode_before);  // the mode only matters while contexts are created
     if (rc != SCAL_OK) {
         const std::string keep = scal_last_error();
         scal_pipeline_destroy(p);

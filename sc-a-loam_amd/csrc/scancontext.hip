@@ -669,14 +669,14 @@ using namespace scal;
 
 struct scal_sc {
     scal_sc_config cfg;
-    hipStream_t stream = nullptr;
+    // the streams and the events are released by `delete c`, after scal_sc_destroy has synchronised the streams
+    LaneStream stream;
     HostStage hs;  // pinned staging of scal_sc_insert_cloud's host array (first call)
     // keyframe filter of the *_features entry points: on its own lane in the stage-pipelined mode (the filter is three quarters of a
     // keyframe's device time, descriptor + search are short), on `stream` otherwise.  One set of filter outputs: ev_ds = filter
     // done (the main stream waits for it), ev_tail = descriptor built from them (the next filter waits for it).
-    hipStream_t fstream = nullptr;
-    int flane = -1;
-    hipEvent_t ev_ds = nullptr, ev_tail = nullptr;
+    LaneStream fstream;
+    Event ev_ds, ev_tail;
     bool tail_recorded = false;
     std::mutex mu;  // insert and detect come from two threads in the reference with no common lock
     int cap = 0;
@@ -709,8 +709,6 @@ struct scal_sc {
     DevBuf<float> dsx, dsy, dsz, dsw;
     DevBuf<int> d_nds;
     int vf_cap = 0;
-    hipEvent_t ev = nullptr;
-    int lane = 0;
     // batched shard queries
     DevBuf<float> bq_rkey;
     DevBuf<double> bq_skey, bq_norm;
@@ -722,9 +720,9 @@ struct scal_sc {
     // each with its own record slot and event, so collecting one does not wait for anything queued on the stream behind it
     static constexpr int DET_DEPTH = 4;
     int det_mode[DET_DEPTH] = {};
-    hipEvent_t det_ev[DET_DEPTH] = {};
+    Event det_ev[DET_DEPTH];
     int det_head = 0, det_count = 0;
-    hipEvent_t made_ev[4] = {};  // descriptors queued by scal_sc_make_features_enqueue, oldest first
+    Event made_ev[4];  // descriptors queued by scal_sc_make_features_enqueue, oldest first
     unsigned made_head = 0, made_tail = 0;
     SCDb db() const { return SCDb{desc.p, rkey.p, skey.p, cnorm.p}; }
     SCSlot staging() const { return SCSlot{qdesc.p, qrkey.p, qskey.p, qnorm.p}; }
@@ -732,7 +730,7 @@ struct scal_sc {
     bool owns(int g) const { return cfg.n_shards <= 1 || (g % cfg.n_shards) == cfg.shard; }
 };
 
-extern "C" int scal_sc_create(const scal_sc_config* cfg, scal_sc_t** out) {
+int scal::sc_create(const scal_sc_config* cfg, StreamLayout layout, scal_sc_t** out) {
     if (!cfg || !out || cfg->max_keyframes <= 0 || !(cfg->max_radius > 0)) {
         set_error("scal_sc_create: bad argument");
         return SCAL_E_ARG;
@@ -759,16 +757,12 @@ extern "C" int scal_sc_create(const scal_sc_config* cfg, scal_sc_t** out) {
     A(c->d_rec.alloc(4 * scal_sc::DET_DEPTH));
     A(c->gcell.alloc(DESC));
     A(c->h_rec.alloc(4 * scal_sc::DET_DEPTH));
-    if (rc == SCAL_OK && acquire_stream(c->cfg.device, &c->stream, c->lane = (c->cfg.side_stream > 0 ? std::min(c->cfg.side_stream, 5) : stage_lane(STAGE_SC))) != SCAL_OK) {
-        set_error("hipStreamCreate failed");
-        rc = SCAL_E_HIP;
-    }
-    if (rc == SCAL_OK && c->cfg.side_stream <= 0 && stage_lane(STAGE_SC_FILTER) != c->lane) {
-        if (acquire_stream(c->cfg.device, &c->fstream, c->flane = stage_lane(STAGE_SC_FILTER)) != SCAL_OK ||
-            hipEventCreateWithFlags(&c->ev_ds, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming) != hipSuccess) {
-            set_error("hipStreamCreate failed");
-            rc = SCAL_E_HIP;
-        }
+    const int lane = c->cfg.side_stream > 0 ? std::min(c->cfg.side_stream, 5) : stage_lane(layout, STAGE_SC);
+    if (rc == SCAL_OK) rc = c->stream.acquire(c->cfg.device, lane);
+    if (rc == SCAL_OK && c->cfg.side_stream <= 0 && stage_lane(layout, STAGE_SC_FILTER) != lane) {
+        rc = c->fstream.acquire(c->cfg.device, stage_lane(layout, STAGE_SC_FILTER));
+        if (rc == SCAL_OK) rc = c->ev_ds.create(hipEventDisableTiming);
+        if (rc == SCAL_OK) rc = c->ev_tail.create(hipEventDisableTiming);
     }
     // initialised on the context's own stream (the legacy null stream is not ordered against it)
     if (rc == SCAL_OK && (op_memset_async(c->gcell.p, 0, sizeof(unsigned) * DESC, c->stream) != hipSuccess || op_stream_synchronize(c->stream) != hipSuccess))
@@ -781,22 +775,13 @@ extern "C" int scal_sc_create(const scal_sc_config* cfg, scal_sc_t** out) {
     return SCAL_OK;
 }
 
+extern "C" int scal_sc_create(const scal_sc_config* cfg, scal_sc_t** out) { return sc_create(cfg, default_stream_layout(), out); }
+
 extern "C" void scal_sc_destroy(scal_sc_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
-    if (c->fstream) {
-        (void)op_stream_synchronize(c->fstream);
-        release_stream(c->cfg.device, c->flane);
-    }
-    if (c->stream) {
-        (void)op_stream_synchronize(c->stream);
-        release_stream(c->cfg.device, c->lane);
-    }
-    if (c->ev_ds) (void)hipEventDestroy(c->ev_ds);
-    if (c->ev_tail) (void)hipEventDestroy(c->ev_tail);
-    if (c->ev) (void)hipEventDestroy(c->ev);
-    for (int k = 0; k < scal_sc::DET_DEPTH; ++k)
-        if (c->det_ev[k]) (void)hipEventDestroy(c->det_ev[k]);
+    if (c->fstream) (void)op_stream_synchronize(c->fstream);
+    if (c->stream) (void)op_stream_synchronize(c->stream);
     delete c;
 }
 
@@ -991,8 +976,8 @@ static int make_features(scal_sc_t* c, scal_features_t* feat, double* d_desc, bo
             set_error("scal_sc_make_features_enqueue: four descriptors are queued and none has been waited for");
             return SCAL_E_STATE;
         }
-        hipEvent_t& ev = c->made_ev[c->made_tail % 4];
-        if (!ev) SCAL_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        Event& ev = c->made_ev[c->made_tail % 4];
+        SCAL_TRY(ev.ensure(hipEventDisableTiming));
         SCAL_HIP(op_event_record(ev, c->stream));
         c->made_tail++;
     }
@@ -1201,7 +1186,7 @@ static int detect_enqueue(scal_sc* c) {
         return SCAL_OK;
     }
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    if (!c->det_ev[slot]) SCAL_HIP(hipEventCreateWithFlags(&c->det_ev[slot], hipEventDisableTiming));
+    SCAL_TRY(c->det_ev[slot].ensure(hipEventDisableTiming));
     if (c->tree_making_period_conter % TREE_MAKING_PERIOD_ == 0) c->size_at_rebuild = c->n_global;  // :353-364
     c->tree_making_period_conter++;
     // query = newest keyframe (:340-341), read in place from its database slot

@@ -445,7 +445,7 @@ using namespace scal;
 
 struct scal_voxel {
     int device = 0, cap = 0;
-    hipStream_t stream = nullptr;
+    LaneStream stream;  // released by `delete c`, after scal_voxel_destroy has synchronised it
     VoxelFilter vf;
     DevBuf<float> aos, ix, iy, iz, iw, ox, oy, oz, ow;
     DevBuf<int> d_n;  // [0] in, [1] out
@@ -468,10 +468,7 @@ extern "C" int scal_voxel_create(int max_points, int device, scal_voxel_t** out)
     A(c->ix.alloc(max_points)); A(c->iy.alloc(max_points)); A(c->iz.alloc(max_points)); A(c->iw.alloc(max_points));
     A(c->ox.alloc(max_points)); A(c->oy.alloc(max_points)); A(c->oz.alloc(max_points)); A(c->ow.alloc(max_points));
     A(c->d_n.alloc(2));
-    if (rc == SCAL_OK && acquire_stream(c->device, &c->stream) != SCAL_OK) {
-        set_error("hipStreamCreate failed");
-        rc = SCAL_E_HIP;
-    }
+    if (rc == SCAL_OK) rc = c->stream.acquire(c->device, 0);
     if (rc != SCAL_OK) {
         delete c;
         return rc;
@@ -483,10 +480,7 @@ extern "C" int scal_voxel_create(int max_points, int device, scal_voxel_t** out)
 extern "C" void scal_voxel_destroy(scal_voxel_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->stream) {
-        (void)op_stream_synchronize(c->stream);
-        release_stream(c->device);
-    }
+    if (c->stream) (void)op_stream_synchronize(c->stream);
     delete c;
 }
 

@@ -5,6 +5,7 @@ loop answers must be bit-identical to one scan at a time through the per-stage c
 import json
 import os
 import subprocess
+import threading
 
 import numpy as np
 import pytest
@@ -186,3 +187,39 @@ def test_multi_sequence_batched_launches_equal_solo_runs(S, worlds, n_seqs):
         for w in (0, 1):
             assert np.array_equal(_sorted_rows(m.maps[q].export(w)), solo_maps[q][w]), (q, w)
     m.close()
+
+
+def test_pipeline_creation_leaves_the_stream_layout_alone(S):
+    """scal_pipeline_create builds its contexts in the per-stage stream layout without touching the process-wide default that
+    scal_set_stream_mode sets: contexts created by another thread at the same time keep the shared layout, where features and
+    odometry both run on lane 0.  Only creates and destroys contexts (nothing is launched); ctypes drops the GIL, so they overlap."""
+    L = S.lib()
+    S.set_stream_mode(0)
+    done, errors = threading.Event(), []
+
+    def churn():
+        try:
+            for _ in range(4):  # 0.2 / 0.4 m: no preallocated grid pools in the pipeline's mapping context
+                S.Pipeline(S.HDL64, 5.0, max_points=20000, line_res=0.2, plane_res=0.4, max_map_points=100000, sc_max_keyframes=64).close()
+        except Exception as e:  # reported below, from the main thread
+            errors.append(e)
+        finally:
+            done.set()
+
+    t = threading.Thread(target=churn)
+    pairs = 0
+    try:
+        t.start()
+        while not done.is_set() or pairs < 4:
+            reg, od = S.ScanRegistration(S.HDL64, 5.0, max_points=20000), S.LaserOdometry(max_points=20000)
+            try:
+                fs, ods = L.scal_features_stream(reg.h), L.scal_odom_stream(od.h)
+            finally:
+                od.close()
+                reg.close()
+            assert fs and ods == fs, (pairs, fs, ods)
+            pairs += 1
+    finally:
+        t.join()
+        S.set_stream_mode(0)
+    assert not errors, errors
