@@ -285,7 +285,8 @@ int scal_map_prefetch_finish(scal_map_t* ctx, scal_features_t* feat);
  * Such a step is speculative: it assumes the cube window of the previous step and the merge insert; when that does not hold the
  * device stops the chain, and collect / finish redo the step on the general path (window shift, full-sort insertion) and replay
  * the steps queued behind it - results are identical either way.  A features context handed to enqueue must not be run again
- * before its step has been collected.  scal_map_export and scal_map_finish wait for all queued insertions (and report a
+ * before its step has been collected; once the pose is collected it may be, even when the step's insertion is still to be redone
+ * (that redo reads only what the step copied out of the context).  scal_map_export and scal_map_finish wait for all queued insertions (and report a
  * capacity error of an insertion).  The map sizes in the statistics of collect are those before this scan's insertion,
  * insert_path is -1. */
 int scal_map_enqueue_features(scal_map_t* ctx, scal_features_t* feat, const double* q_wodom, const double* t_wodom);

@@ -80,6 +80,9 @@ struct MapState {
     int next_valid[2];
     int next_unsorted;
     int next_over;
+    // sequence number of the last step whose pose stands (written by its pose hook unless the chain was stopped): the fused
+    // registration of that step runs even when its merge is then called off, so that redoing the insertion needs no features input
+    unsigned pose_seq;
 };
 
 __device__ __forceinline__ int pack_cube(int ai, int aj, int ak) { return (ai + 512) | ((aj + 512) << 10) | ((ak + 512) << 20); }
@@ -1265,10 +1268,14 @@ struct MapResult {
 
 // k_merge_write.  tail.fused = 0: the merge write alone.  tail.fused = 1 (speculative chain): the launch also carries the registration
 // of the full-resolution cloud (:845-849) as extra blocks - what k_transform_cloud does in a launch of its own on the general path.
+// The registration depends on the pose only, so it runs whenever this step's pose stands - also when the merge is called off in
+// this very launch (merge_fail, map pool full) or a workgroup of the solve gave up after the pose was out: the host then redoes
+// the insertion alone, after the caller may already have rerun the features context (scal_map_enqueue_features).
 // (Committing the sizes from the last block to finish was tried as well: a ticket counter bumped by 2,300 workgroups costs more
 // than the 5 us launch of k_map_end it saves.)
 struct MergeTail {
     int fused;
+    unsigned seq;  // the step's sequence number: registration runs when MapState::pose_seq says this step's pose stands
     CSoA4 full;
     const int* d_nfull;
     int full_cap;
@@ -1278,7 +1285,7 @@ struct MergeTail {
 __device__ __forceinline__ void k_merge_write_body(const MergeArgs& a, MapState* S, MapCounters* C, const MergeTail& t) {
     merge_write_body(a, S, C);
     if (!t.fused) return;
-    if (static_cast<int>(blockIdx.x) >= MERGE_WRITE_GRID && !S->abort) {
+    if (static_cast<int>(blockIdx.x) >= MERGE_WRITE_GRID && S->pose_seq == t.seq) {
         const int i = (blockIdx.x - MERGE_WRITE_GRID) * 256 + threadIdx.x;
         if (i < min(*t.d_nfull, t.full_cap)) {
             double x7[7];
@@ -1411,6 +1418,7 @@ struct MapPoseDone {
             for (int i = 0; i < 4; ++i) S->q_wmap_wodom[i] = qn[i];
 #pragma unroll
             for (int i = 0; i < 3; ++i) S->t_wmap_wodom[i] = x[4 + i] - r2[i];
+            S->pose_seq = seq;
         }
         __syncthreads();
         copy_words(&host->st, st, sizeof(LMState));
@@ -1825,7 +1833,7 @@ int launch_insert_merge(scal_map* c, const MapStep& e, bool fused = false) {
     MergeTail t{};
     int grid = MERGE_WRITE_GRID;
     if (fused) {
-        t.fused = 1, t.st = c->d_st.p, t.full_out = c->full_out.v(), t.full_cap = c->scan_cap;
+        t.fused = 1, t.seq = e.seq, t.st = c->d_st.p, t.full_out = c->full_out.v(), t.full_cap = c->scan_cap;
         if (e.have_full && e.feat) {
             FeatDeviceView v = features_view(e.feat);
             t.full = CSoA4{v.x, v.y, v.z, v.i}, t.d_nfull = &v.P->n_kept;
@@ -1842,10 +1850,11 @@ int launch_insert_merge(scal_map* c, const MapStep& e, bool fused = false) {
     return SCAL_OK;
 }
 
-// registration of the full-resolution cloud (:845-849), commit of the new map sizes, counters to the host; fires ev_done
-int launch_tail(scal_map* c, const MapStep& e) {
+// registration of the full-resolution cloud (:845-849), commit of the new map sizes, counters to the host; fires ev_done.
+// registered: the fused merge write of the step's speculative run has registered the cloud already - the features context is not read.
+int launch_tail(scal_map* c, const MapStep& e, bool registered = false) {
     hipStream_t s = c->stream;
-    if (e.have_full) {
+    if (e.have_full && !registered) {
         const int nb = std::max(1, div_up(c->scan_cap, 256));
         if (e.feat) {
             FeatDeviceView v = features_view(e.feat);
@@ -1859,7 +1868,7 @@ int launch_tail(scal_map* c, const MapStep& e) {
     SCAL_LAUNCH("k_map_end", k_map_end, dim3(1), dim3(256), 0, s, c->d_S.p, c->d_C(e.set).p, c->res.p + e.slot, e.seq);
     SCAL_HIP(hipGetLastError());
     SCAL_HIP(op_event_record(c->ev_done[e.slot], s));
-    if (e.feat) SCAL_TRY(features_note_reader(e.feat, s));  // the registration transform reads the full-resolution cloud last
+    if (e.feat && !registered) SCAL_TRY(features_note_reader(e.feat, s));  // the registration transform reads the full-resolution cloud last
     return SCAL_OK;
 }
 
@@ -2109,7 +2118,9 @@ void confirm(scal_map* c, MapStep& e) {
     c->last_insert_path = e.insert_path;
     e.confirmed = true;
 }
-// a step whose features context has been run again since it was enqueued cannot be redone: its inputs are gone
+// a step whose features context has been run again since it was enqueued cannot be redone from its start: its inputs are gone.
+// Only steps whose pose has not been collected are ever redone from their start (collect redoes a stopped step first); an
+// insertion redone after the pose was out does not read the context.
 int check_generation(const MapStep& e, bool needs_inputs) {
     if (!e.feat || features_view(e.feat).generation == e.feat_generation) return SCAL_OK;
     if (!needs_inputs && !e.have_full) return SCAL_OK;
@@ -2174,12 +2185,15 @@ int recover(scal_map* c) {
         else SCAL_HIP(op_memset_async(&c->d_S.p->abort, 0, sizeof(int), s));
         if (c->res.p[e.slot].S2.abort == MAP_ABORT_LM)
             SCAL_LAUNCH("k_grid_clear", k_grid_clear, dim3(GRID_BLOCKS), dim3(256), 0, s, grid_args(c, e.par), c->d_S.p);
-        SCAL_TRY(check_generation(e, false));
         const MapResult& R = c->res.p[e.slot];
+        // the pose was out before the stop, so the caller may have collected it and run the features context again: the stopped
+        // merge write has registered the full-resolution cloud already, and the redo reads only the stacks of its own input set
+        const bool registered = R.S2.pose_seq == e.seq;
+        if (!registered) SCAL_TRY(check_generation(e, false));
         const int n_map[2] = {R.S2.n_map[0], R.S2.n_map[1]};  // not committed: still the sizes before the insertion
         e.fast = false, e.insert_path = 0;
         SCAL_TRY(insert_full_sort(c, e, n_map));
-        SCAL_TRY(launch_tail(c, e));
+        SCAL_TRY(launch_tail(c, e, registered));
         SCAL_HIP(op_event_synchronize(c->ev_done[e.slot]));
         if (R.C2.error) return report_device_error(c, R.C2.error);
         c->cur = e.par ^ 1;

@@ -226,6 +226,50 @@ def test_queued_steps_equal_general_path(S, hdl64_stream, plane_res):
         m.close()
 
 
+def test_insertion_redo_after_the_features_context_was_rerun(S, hdl64_stream):
+    """A speculative step whose merge gives up (plane_res 0.25: more stack points than one merge takes) stops the chain AFTER its
+    pose has been published.  collect does not poll, so the caller gets the pose, reruns the step's features context with the next
+    scan - allowed once the pose is collected (include/scaloam_hip.h) - and only then does finish notice the stop and redo the
+    insertion with the full sort.  That redo must not need the context: finish succeeds, and the map and the next scan's pose equal,
+    bit for bit, those of a context driven one synchronous step at a time."""
+    n0 = 4
+    regs = [S.ScanRegistration(S.HDL64, 5.0, max_points=200000) for _ in range(2)]
+    od = S.LaserOdometry(max_points=200000)
+    mk = lambda: S.LaserMapping(0.4, 0.25, max_scan_points=200000, max_map_points=3000000)
+    a, b = mk(), mk()
+    b.set_poll(False)
+    for k in range(n0):   # the first scan takes the general path, the rest are queued speculatively (and redone synchronously)
+        r = regs[k % 2]
+        r.laserCloudHandler(hdl64_stream(k))
+        _, _, qw, tw, _ = od.step_features(r)
+        qa, ta, _ = a.process_features(r, qw, tw)
+        qb, tb, _ = b.process_features(r, qw, tw)
+        assert np.array_equal(qa, qb) and np.array_equal(ta, tb), k
+    before = b.path_counters()
+    assert before[0] >= 1, before
+    x = regs[n0 % 2]
+    x.laserCloudHandler(hdl64_stream(n0))
+    _, _, qw, tw, _ = od.step_features(x)
+    qa, ta, _ = a.process_features(x, qw, tw)
+    b.enqueue_features(x, qw, tw)
+    qb, tb, _ = b.collect()                      # the pose stands; the stop of the merge has not been noticed yet
+    assert np.array_equal(qa, qb) and np.array_equal(ta, tb)
+    x.laserCloudHandler(hdl64_stream(n0 + 1))    # the context is rerun before the insertion is redone
+    b.finish()
+    after = b.path_counters()
+    assert after[3] == before[3] + 1 and after[0] == before[0] + 1, (before, after)   # this step's insertion was redone
+    for which in (0, 1):
+        assert np.array_equal(_sorted_rows(a.export(which)), _sorted_rows(b.export(which))), which
+    _, _, qw, tw, _ = od.step_features(x)
+    qa, ta, _ = a.process_features(x, qw, tw)
+    qb, tb, _ = b.process_features(x, qw, tw)
+    assert np.array_equal(qa, qb) and np.array_equal(ta, tb)
+    for which in (0, 1):
+        assert np.array_equal(_sorted_rows(a.export(which)), _sorted_rows(b.export(which))), which
+    for m in regs + [od, a, b]:
+        m.close()
+
+
 def test_long_stream_parity_device_pipeline(O, S, hdl64_stream):
     """50 scans of the BASELINE config #2 sequence (seed 205) through the device-resident pipeline A -> B -> C (features context handed
     from stage to stage, stage C on its speculative chain) against the oracle chain.  Long enough for the trajectory (1 m per scan)

@@ -21,11 +21,11 @@ def _descs(n, seed=7):
     return [rng.uniform(-2.0, 18.0, (20, 60)) * (rng.uniform(size=(20, 60)) < 0.5) for _ in range(n)]
 
 
-def _serial(S, scans, descs, sc_thres=0.4):
+def _serial(S, scans, descs, sc_thres=0.4, plane_res=0.8):
     """one scan at a time through the per-stage entry points"""
     cap = max(s.shape[0] for s in scans) + 1024
     reg = S.ScanRegistration(S.HDL64, 5.0, max_points=cap)
-    od, mp = S.LaserOdometry(max_points=cap), S.LaserMapping(0.4, 0.8, max_scan_points=cap, max_map_points=3000000)
+    od, mp = S.LaserOdometry(max_points=cap), S.LaserMapping(0.4, plane_res, max_scan_points=cap, max_map_points=3000000)
     sc = S.SCManager(max_radius=80.0, dist_thres=sc_thres, max_keyframes=len(descs) + len(scans) + 8)
     for d in descs:
         sc.saveScancontextAndKeys(d)
@@ -80,6 +80,57 @@ def test_pipeline_equals_stage_calls(S, hdl64_stream, ahead):
     for which in (0, 1):
         assert np.array_equal(_sorted_rows(p.map.export(which)), _sorted_rows(ref_maps[which])), which
     p.close()
+
+
+def test_pipeline_redoes_insertions_after_the_pose_is_out(O, S, hdl64_stream):
+    """plane_res 0.25 gives more stack points than one merge insert takes: every speculative step's merge gives up on the device
+    after its pose has been published, and the insertion is redone with the full sort once the stop is noticed.  With a ring of
+    four features contexts and three scans pushed ahead, the front thread reruns a context as soon as its scan's pose is collected -
+    possibly before that redo, which must then not need the context.  Everything must equal the per-stage calls bit for bit, and
+    the poses the oracle's within 1e-6."""
+    n = 44
+    scans = [hdl64_stream(k) for k in range(n)]
+    descs = _descs(40)
+    ref, ref_maps = _serial(S, scans, descs, plane_res=0.25)
+    cap = max(s.shape[0] for s in scans) + 1024
+    p = S.Pipeline(S.HDL64, 5.0, max_points=cap, plane_res=0.25, max_map_points=3000000, sc_mode=S.SC_EVERY_SCAN, sc_dist_thres=0.4,
+                   sc_max_keyframes=len(descs) + n + 8, ring=4, depth=3)
+    for d in descs:
+        p.sc.saveScancontextAndKeys(d)
+    got = []
+    for k in range(n):
+        p.push(scans[k])
+        while p.in_flight() > 3:
+            got.append(p.pop())
+    p.drain()
+    while p.in_flight():
+        got.append(p.pop())
+    assert [g["seq"] for g in got] == list(range(n))
+    for k in range(n):
+        g, r = got[k], ref[k]
+        assert np.array_equal(g["q_odom"], r["q_odom"]) and np.array_equal(g["t_odom"], r["t_odom"]), k
+        assert np.array_equal(g["q"], r["q"]) and np.array_equal(g["t"], r["t"]), (k, np.abs(g["t"] - r["t"]).max())
+        assert list(g["map"].n_edge) == r["n_edge"] and list(g["map"].n_plane) == r["n_plane"] and list(g["map"].lm_iters) == r["iters"], k
+        for key in ("loop_id", "nn_idx", "nn_shift", "min_dist"):
+            assert g["loop"][key] == r["loop"][key] or (np.isnan(g["loop"][key]) and np.isnan(r["loop"][key])), (k, key)
+        assert np.array_equal(g["loop"]["cand"], r["loop"]["cand"]), k
+    for which in (0, 1):
+        assert np.array_equal(_sorted_rows(p.map.export(which)), _sorted_rows(ref_maps[which])), which
+    cnt = p.map.path_counters()
+    p.close()
+    print("path counters (speculative, general, window redo, insertion redo):", cnt)
+    assert cnt[3] >= n - 4, cnt
+    oo, om = O.Odometry(), O.Mapper(0.4, 0.25, voxel_order=1, knn_mode=0)
+    worst = 0.0
+    for k in range(n):
+        f = O.features(scans[k], O.HDL64, 5.0)
+        c = f["cloud"]
+        a = oo.step(c[f["sharp"]], c[f["less_sharp"]], c[f["flat"]], f["less_flat"])
+        qo, to, so, _ = om.step(c[f["less_sharp"]], f["less_flat"], c, a[2], a[3])
+        d = max(np.abs(got[k]["q"] - qo).max(), np.abs(got[k]["t"] - to).max())
+        worst = max(worst, d)
+        assert d <= 1e-6, (k, d)
+    print("worst pose difference from the oracle:", worst)
 
 
 def test_pipeline_device_input_and_errors(S, hdl64_stream):
