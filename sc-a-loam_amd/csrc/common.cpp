@@ -207,6 +207,30 @@ struct DevStream {
 };
 DevStream g_streams[64][6];  // [device][lane], see common.hpp
 std::atomic<int> g_stream_mode{0};  // scal_set_stream_mode: the layout of contexts created through the public entry points
+
+// The four lanes that carry the stage pipeline's busy chains (stage_lane: 0, 1, 3, 4) each get a hardware queue of their own.  A plain
+// stream takes a queue from the runtime's pool, which GPU_MAX_HW_QUEUES caps (4 by default, fewer on some systems); once the pool is
+// used up - torch's null stream counts - new streams share queues, and two streams on one queue run their packets in order: the lanes
+// then stop overlapping and a scan costs the sum of two chains rather than the longest one ("Streams").  A stream
+// created with a CU mask always gets a new queue outside that pool; the mask here covers every CU, so the kernels see the same
+// device.  Lanes 2 and 5 carry little and keep plain streams.
+bool lane_has_own_queue(int lane) { return lane == 0 || lane == 1 || lane == 3 || lane == 4; }
+
+// A stream on a queue of its own, or null if the runtime will not make one (the caller then falls back to a plain stream).  Such a
+// stream is created blocking (the runtime offers no flags for it), which orders it behind work on the legacy null stream: more
+// ordering than a non-blocking stream, never less.
+hipStream_t own_queue_stream(int device) {
+    int ncu = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0) return nullptr;
+    std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
+    for (int cu = 0; cu < ncu; ++cu) mask[cu / 32] |= 1u << (cu % 32);
+    hipStream_t s = nullptr;
+    if (hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return s;
+}
 }  // namespace
 
 int acquire_stream(int device, hipStream_t* out, int lane) {
@@ -218,7 +242,12 @@ int acquire_stream(int device, hipStream_t* out, int lane) {
     DevStream& d = g_streams[device][lane];
     if (!d.s) {
         hipError_t e = hipSetDevice(device);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking);
+        if (e == hipSuccess && lane_has_own_queue(lane)) {
+            d.s = own_queue_stream(device);
+            if (!d.s) e = hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking);
+        } else if (e == hipSuccess) {
+            e = hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking);
+        }
         if (e != hipSuccess) {
             set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
             d.s = nullptr;
@@ -238,8 +267,47 @@ int stage_lane(StreamLayout layout, int stage) {
     // all slow down together (tools/stream_probe.hip: 0.62 M kernels/s with 4 streams, 0.25-0.35 M with 6-8).  The side jobs that
     // only depend on stage A are spread so that the four chains come out about equally long (tools/gpu_chains.sh): stage C's surf
     // filter and ScanContext's keyframe filter share the side stream, its corner filter rides behind stage A, and ScanContext's
-    // descriptor + search (short) ride behind stage B.
+    // descriptor + search (short) ride behind stage B.  The four chains overlap only if their streams sit on four hardware queues:
+    // acquire_stream gives lanes 0, 1, 3 and 4 a queue each (lane_has_own_queue), whatever the runtime's queue pool holds.
     return (stage == STAGE_ODOM || stage == STAGE_SC) ? 3 : stage == STAGE_MAP ? 4 : (stage == STAGE_SC_FILTER || stage == STAGE_MAP_PREFETCH) ? 1 : 0;
+}
+
+// Diagnostic (tests): the hardware queue behind a lane's stream that is already held (lane -1: the legacy null stream), read by a
+// one-thread kernel from its dispatch packet's queue pointer.  Two streams report the same value exactly when they share a queue.
+__global__ void k_queue_ptr(unsigned long long* out) { out[0] = reinterpret_cast<unsigned long long>(__builtin_amdgcn_queue_ptr()); }
+
+int lane_queue(int device, int lane, unsigned long long* out) {
+    if (!out || device < 0 || device >= 64 || lane < -1 || lane > 5) {
+        set_error("lane_queue: bad argument (device %d, lane %d)", device, lane);
+        return SCAL_E_ARG;
+    }
+    hipStream_t s = nullptr;
+    if (lane >= 0) {
+        std::lock_guard<std::mutex> lk(g_stream_mu);
+        DevStream& d = g_streams[device][lane];
+        if (!d.s) {
+            set_error("lane_queue: no context holds lane %d of device %d", lane, device);
+            return SCAL_E_STATE;
+        }
+        d.refs++;
+        s = d.s;
+    }
+    unsigned long long* dq = nullptr;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipMalloc(&dq, sizeof *dq);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_queue_ptr, dim3(1), dim3(1), 0, s, dq);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dq, sizeof *dq, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (dq) (void)hipFree(dq);
+    if (lane >= 0) release_stream(device, lane);
+    if (e != hipSuccess) {
+        set_error("lane_queue: %s", hipGetErrorString(e));
+        return SCAL_E_HIP;
+    }
+    return SCAL_OK;
 }
 
 void release_stream(int device, int lane) {
@@ -418,6 +486,9 @@ extern "C" int scal_set_stream_mode(int mode) {
     scal::g_stream_mode = mode;
     return SCAL_OK;
 }
+
+// not in the public header: a diagnostic for the tests (tests/test_lane_queues_gpu.py), reached through ctypes
+extern "C" int scal_debug_lane_queue(int device, int lane, unsigned long long* queue) { return scal::lane_queue(device, lane, queue); }
 
 extern "C" const char* scal_last_error(void) { return scal::g_err; }
 extern "C" int scal_device_count(void) {
