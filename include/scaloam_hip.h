@@ -449,7 +449,14 @@ int scal_icp_set_search(scal_icp_t* ctx, int mode);
 enum {
     SCAL_PIPE_SC_OFF = 0,        /* stages A-C only */
     SCAL_PIPE_SC_EVERY_SCAN = 1, /* makeAndSaveScancontextAndKeys + detectLoopClosureID for every scan (BASELINE config #2's "SC loop search" per scan) */
-    SCAL_PIPE_SC_DESCRIPTOR = 2  /* only build each scan's descriptor into device memory (sharded search: the caller exchanges it over RCCL) */
+    SCAL_PIPE_SC_DESCRIPTOR = 2, /* only build each scan's descriptor into device memory (sharded search: the caller exchanges it over RCCL) */
+    /* the pose-graph node's keyframe path (laserPosegraphOptimization.cpp:598-639, :713-730, :472-548): stage D gates the stage-C poses
+     * into keyframes (scal_keyframe_gate), keeps each keyframe's 0.4 m cloud and pose, inserts only keyframes into ScanContext, searches
+     * from the newest keyframe once 30 of the pipeline's own keyframes exist (:715), and verifies every detected loop with ICP between
+     * the current keyframe and the loop keyframe's +-25 neighbours, all moved by the loop keyframe's pose and downsampled at 0.4 m
+     * (:472-548).  Verified / rejected loops come out with scal_pipeline_pop_loop.  Deviation: the search runs for every keyframe (the
+     * project's per-keyframe detect convention), not on the reference's 1 Hz timer (:735-745).  One sequence only. */
+    SCAL_PIPE_SC_KEYFRAME = 3
 };
 typedef struct {
     int lidar_type, n_scans;      /* as scal_features_config */
@@ -466,6 +473,11 @@ typedef struct {
     int depth;                    /* stage-C steps queued on the device and not collected: 1..3, 0 = 2 */
     double* d_desc_ring;          /* sc_mode 2: caller-owned device memory for ring x 1200 doubles, scan k's descriptor at slot k % ring
                                    * (NULL: allocated by the pipeline) - so that an RCCL all-gather can read it in place */
+    /* sc_mode 3 (0 = the reference's default everywhere) */
+    double keyframe_meter_gap;    /* keyframe_meter_gap rosparam, 0 = 2.0 m (:874) */
+    double keyframe_deg_gap;      /* keyframe_deg_gap rosparam, 0 = 10 deg (:875) */
+    int kf_max_points;            /* keyframe cloud store, points over all keyframes; 0 = no clouds kept, no loop is verified */
+    double loop_fitness_thres;    /* loopFitnessScoreThreshold, 0 = 0.3 (:531) */
 } scal_pipeline_config;
 typedef struct {
     long long seq;                        /* 0, 1, 2 ... in push order */
@@ -476,6 +488,10 @@ typedef struct {
     int have_loop;                        /* sc_mode 1: `loop` is detectLoopClosureID's answer with this scan as the query */
     scal_sc_result loop;
     const double* d_descriptor;           /* sc_mode 2: this scan's 20x60 descriptor in device memory (valid until `ring` more scans were pushed) */
+    /* sc_mode 3: `have_loop` / `loop` are the search with this keyframe as the query (have_loop = 0 while fewer than 30 keyframes
+     * of the pipeline exist, and for scans that are not keyframes) */
+    int is_keyframe;
+    int keyframe_id;                      /* its ScanContext database index (pre-filled entries count), -1 = not a keyframe */
 } scal_pipeline_result;
 typedef struct scal_pipeline scal_pipeline_t;
 int scal_pipeline_create(const scal_pipeline_config* cfg, scal_pipeline_t** p);
@@ -486,10 +502,11 @@ int scal_pipeline_push_device(scal_pipeline_t* p, const float* d_xyz, int n, int
 /* The same from host memory (PointCloud2 layout, as scal_features_run): the scan is copied into pinned staging and uploaded on
  * stage A's stream; the caller's buffer is free when the call returns. */
 int scal_pipeline_push_host(scal_pipeline_t* p, const void* xyz, int n, int stride_bytes);
-/* Result of the oldest scan not yet popped; blocks until its mapping pose (and, in sc_mode 1, its loop answer) is on the host.
+/* Result of the oldest scan not yet popped; blocks until its mapping pose (and, in sc_mode 1 and 3, its loop answer) is on the host.
  * An error of any stage is returned here (and by every later call) with the failing stage's message in scal_last_error(). */
 int scal_pipeline_pop(scal_pipeline_t* p, scal_pipeline_result* out);
-/* waits until every pushed scan has its result ready AND the last scan's map insertion has finished; results stay queued for pop */
+/* waits until every pushed scan has its result ready AND the last scan's map insertion has finished (sc_mode 3: and every detected
+ * loop has been verified); results stay queued for pop */
 int scal_pipeline_drain(scal_pipeline_t* p);
 /* scans pushed and not popped */
 int scal_pipeline_in_flight(scal_pipeline_t* p);
@@ -499,6 +516,44 @@ scal_sc_t* scal_pipeline_sc(scal_pipeline_t* p);
 scal_map_t* scal_pipeline_map(scal_pipeline_t* p);
 scal_odom_t* scal_pipeline_odom(scal_pipeline_t* p);
 scal_features_t* scal_pipeline_features(scal_pipeline_t* p, int i);
+
+/* ---- sc_mode 3: loop candidates and keyframes
+ * One detected loop (loop_id >= 0) and its ICP verification (doICPVirtualRelative, :500-548).  The source is the current keyframe's
+ * cloud, the target the clouds of keyframes loop_kf-25 .. loop_kf+25 that have one, all moved by loop_kf's pose (local2global with the
+ * root keyframe's pose, :479-486, a quirk of the reference kept here) and downsampled at 0.4 m (:491-492); ICP with :519-523's settings. */
+typedef struct {
+    long long seq;          /* the scan (push order) whose keyframe was the query */
+    int curr_kf, loop_kf;   /* ScanContext database indices */
+    float yaw_rad;          /* the search's yaw */
+    double min_dist;        /* the search's SC distance */
+    int verified;           /* 1 accepted (converged && fitness <= loop_fitness_thres), 0 rejected, -1 not verifiable: the current or
+                             * the loop keyframe has no stored cloud (a pre-filled database entry, or kf_max_points == 0); no ICP ran */
+    int converged, iterations, state; /* as scal_icp_result */
+    double fitness;
+    double T[16];           /* icp.getFinalTransformation(), row-major */
+    int n_src, n_tgt;       /* cloud sizes after the 0.4 m filters */
+    double q_rel[4];        /* poseFrom.between(poseTo) (:540-547), x y z w: getTranslationAndEulerAngles of T (f32), */
+    double t_rel[3];        /* Rot3::RzRyRx, inverse - in double; set whenever ICP ran */
+} scal_pipeline_loop;
+/* the oldest loop record not yet popped, in detection order: 1 = *out filled; 0 = none is ready (wait = 0), or none is ready and no
+ * verification is pending (wait = 1: blocks while one is); < 0 error.  Push returns SCAL_E_STATE while 64 records wait to be popped
+ * (the pipeline itself never waits for this queue).  scal_pipeline_drain also waits for every pending verification. */
+int scal_pipeline_pop_loop(scal_pipeline_t* p, scal_pipeline_loop* out, int wait);
+/* keyframe kf (database index) of this pipeline, only while drained: pose6 = x y z roll pitch yaw (getOdom, :312-323) and its
+ * stored 0.4 m cloud (the one keyframeLaserClouds holds, :629-634): *n = its size, the first min(*n, cap) xyzi records go to xyzi
+ * (host; may be NULL with cap 0).  *n = 0 when no clouds are kept.  SCAL_E_ARG for a pre-filled entry or an unknown index. */
+int scal_pipeline_keyframe(scal_pipeline_t* p, int kf, double pose6[6], float* xyzi, int cap, int* n);
+
+/* ---- the keyframe gate (:598-617 with getOdom :312-323 and diffTransformation :325-336), host only, no device needed.  The
+ * accumulators start at 1e6 (:67-68), so the first pose is a keyframe; roll/pitch/yaw from tf's getRPY in double, the delta through
+ * pcl::getTransformation / getTranslationAndEulerAngles in f32, the rotation summed naively. */
+typedef struct {
+    double meter_gap, rad_gap;
+    double translation_accumulated, rotation_accumulated;
+    double curr[6];         /* odom_pose_curr: x y z roll pitch yaw */
+} scal_keyframe_gate_state;
+int scal_keyframe_gate_init(scal_keyframe_gate_state* st, double meter_gap, double deg_gap);
+int scal_keyframe_gate(scal_keyframe_gate_state* st, const double q_xyzw[4], const double t_xyz[3], int* is_keyframe);
 
 /* ---- several independent sequences (sensor streams) on ONE GPU, their kernels sharing launches ("batched /
  * streamed numbers - several independent scans or sequences in flight").  One scan's kernels run on 1..50 workgroups of a 256-CU part

@@ -57,6 +57,16 @@ void release_stream(int device, int lane = 0);
 int odom_create(const scal_odom_config* cfg, StreamLayout layout, scal_odom_t** out);
 int map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t** out);
 int sc_create(const scal_sc_config* cfg, StreamLayout layout, scal_sc_t** out);
+// scal_icp_create on a given lane (scal_pipeline's loop verification keeps off the four busy lanes)
+int icp_create_on_lane(const scal_icp_config* cfg, int lane, scal_icp_t** out);
+// scal_sc_insert_features with a hook queued on the ScanContext stream behind the descriptor and before the next keyframe filter may
+// overwrite the 0.4 m filter output: after(stream, x, y, z, intensity, device count, capacity) (scal_pipeline's keyframe store)
+struct ScFilterOut {
+    const float *x, *y, *z, *w;
+    const int* d_n;
+    int cap;
+};
+int sc_insert_features_then(scal_sc_t* ctx, scal_features_t* feat, int (*after)(void* user, hipStream_t s, const ScFilterOut& ds), void* user);
 
 // Owning handles in the style of DevBuf (move-only): one reference to a shared stream, released when the handle goes away ...
 struct LaneStream {

@@ -417,7 +417,9 @@ struct scal_icp {
     DevBuf<float4> sorted;
 };
 
-extern "C" int scal_icp_create(const scal_icp_config* cfg, scal_icp_t** out) {
+extern "C" int scal_icp_create(const scal_icp_config* cfg, scal_icp_t** out) { return icp_create_on_lane(cfg, 0, out); }
+
+int scal::icp_create_on_lane(const scal_icp_config* cfg, int lane, scal_icp_t** out) {
     if (!cfg || !out || cfg->max_source <= 0 || cfg->max_target <= 0 || cfg->max_iterations <= 0 || !(cfg->max_corr_dist > 0)) {
         set_error("scal_icp_create: bad argument");
         return SCAL_E_ARG;
@@ -434,7 +436,7 @@ extern "C" int scal_icp_create(const scal_icp_config* cfg, scal_icp_t** out) {
     A(c->h_sums.alloc(ICP_NSUM));
     A(c->grid.alloc(1)); A(c->mm.alloc(6)); A(c->count.alloc(ICP_NCELL)); A(c->start.alloc(ICP_NCELL + 4)); A(c->bsum.alloc(256));
     A(c->cell_of.alloc(cfg->max_target)); A(c->sorted.alloc(cfg->max_target)); A(c->un_list.alloc(cfg->max_source)); A(c->d_nun.alloc(2));
-    if (rc == SCAL_OK) rc = c->stream.acquire(cfg->device, 0);
+    if (rc == SCAL_OK) rc = c->stream.acquire(cfg->device, lane);
     if (rc == SCAL_OK) {  // initialised on the context's own stream (the legacy null stream is not ordered against it)
         const unsigned init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
         if (hipMemcpyAsync(c->mm.p, init, sizeof init, hipMemcpyHostToDevice, c->stream) != hipSuccess ||

@@ -1,0 +1,370 @@
+// The pose-graph node's keyframe path for scal_pipeline's sc_mode 3 (laserPosegraphOptimization.cpp):
+//  - the keyframe gate (:598-617, getOdom :312-323, diffTransformation :325-336), host only;
+//  - the keyframe store (keyframeLaserClouds / keyframePoses, :629-637): stage D appends each keyframe's 0.4 m cloud - the output of
+//    ScanContext's keyframe filter, still in HBM - to an xyzi arena on the ScanContext stream (k_kf_append), nothing is read back;
+//  - the loop verification (loopFindNearKeyframesCloud / doICPVirtualRelative, :472-548) on a stream of its own: the source and the
+//    target submap are moved by the loop keyframe's pose (k_kf_submap: local2global, :338-359), filtered at 0.4 m by the device voxel
+//    filter and aligned by the exact-NN ICP; the acceptance test (:531) and the relative pose (:536-547) are computed on the host.
+// The clouds never leave HBM.
+#include "keyframes.hpp"
+#include <algorithm>
+#include <cmath>
+#include <limits>
+
+namespace scal {
+namespace {
+
+struct Aff34 {
+    float m[12];  // row-major top 3x4 of pcl::getTransformation's Affine3f
+};
+
+// keyframe j's cloud (the keyframe filter's SoA output, *d_n points) -> arena[off[j] ..), off[j + 1] = off[j] + n.  A cloud that does
+// not fit writes nothing, leaves off[j + 1] = off[j] and raises *overflow.  Grid-stride: 16-byte stores, coalesced reads of four planes.
+__global__ void k_kf_append(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z, const float* __restrict__ w,
+                            const int* __restrict__ d_n, float4* __restrict__ arena, int* __restrict__ off, int j, int cap,
+                            int* __restrict__ overflow) {
+    const int n = *d_n, base = off[j];
+    const bool fits = n >= 0 && n <= cap - base;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        off[j + 1] = fits ? base + n : base;
+        if (!fits) *overflow = 1;
+    }
+    if (!fits) return;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) arena[base + i] = make_float4(x[i], y[i], z[i], w[i]);
+}
+
+// local2global (:338-359) of keyframes j0 .. j1 (contiguous in the arena, in keyframe order) with ONE transform, into out[0 .. n):
+// each coordinate ((T0 * x + T1 * y) + T2 * z) + T3 in f32, rounded operation by operation (Eigen's expression, no contraction).
+// Streaming: one 16-byte load and one 16-byte store per point.
+__global__ void k_kf_submap(const float4* __restrict__ arena, const int* __restrict__ off, int j0, int j1, Aff34 T, float4* __restrict__ out,
+                            int* __restrict__ d_n_out) {
+    const int base = off[j0], n = off[j1 + 1] - base;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *d_n_out = n;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float4 p = arena[base + i];
+        float4 q;
+        q.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.m[0], p.x), __fmul_rn(T.m[1], p.y)), __fmul_rn(T.m[2], p.z)), T.m[3]);
+        q.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.m[4], p.x), __fmul_rn(T.m[5], p.y)), __fmul_rn(T.m[6], p.z)), T.m[7]);
+        q.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.m[8], p.x), __fmul_rn(T.m[9], p.y)), __fmul_rn(T.m[10], p.z)), T.m[11]);
+        q.w = p.w;
+        out[i] = q;
+    }
+}
+
+// pcl::getTransformation (f32 Affine3f, R = Rz(yaw) Ry(pitch) Rx(roll)), as scaloam.pgo._affine_f32 states it: the sines and cosines
+// in double rounded to f32, the products in f32
+Aff34 affine_f32(const double p[6]) {
+    const float A = static_cast<float>(std::cos(p[5])), B = static_cast<float>(std::sin(p[5]));
+    const float C = static_cast<float>(std::cos(p[4])), D = static_cast<float>(std::sin(p[4]));
+    const float E = static_cast<float>(std::cos(p[3])), F = static_cast<float>(std::sin(p[3]));
+    const float DE = D * E, DF = D * F;
+    Aff34 T;
+    const float m[12] = {A * C, A * DF - B * E, B * F + A * DE, static_cast<float>(p[0]),
+                         B * C, A * E + B * DF, B * DE - A * F, static_cast<float>(p[1]),
+                         -D,    C * F,          C * E,          static_cast<float>(p[2])};
+    std::memcpy(T.m, m, sizeof m);
+    return T;
+}
+
+// tf::Matrix3x3(q).getRPY (:318-320), in double
+void rpy_from_quat(const double q[4], double* roll, double* pitch, double* yaw) {
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double n = x * x + y * y + z * z + w * w, s = 2.0 / n;
+    const double m00 = 1 - s * (y * y + z * z), m01 = s * (x * y - w * z), m02 = s * (x * z + w * y);
+    const double m10 = s * (x * y + w * z);
+    const double m20 = s * (x * z - w * y), m21 = s * (y * z + w * x), m22 = 1 - s * (x * x + y * y);
+    if (std::fabs(m20) >= 1.0) {  // gimbal lock branch of tf's getEulerYPR
+        *yaw = 0.0;
+        if (m20 < 0)
+            *pitch = M_PI / 2, *roll = std::atan2(m01, m02);
+        else
+            *pitch = -M_PI / 2, *roll = std::atan2(-m01, -m02);
+        return;
+    }
+    *pitch = -std::asin(m20);
+    const double cp = std::cos(*pitch);
+    *roll = std::atan2(m21 / cp, m22 / cp);
+    *yaw = std::atan2(m10 / cp, m00 / cp);
+}
+
+// Eigen::Quaterniond(const Matrix3d&) (gtsam Rot3::toQuaternion): x y z w
+void quat_from_matrix(const double m[3][3], double q[4]) {
+    const double t = m[0][0] + m[1][1] + m[2][2];
+    if (t > 0) {
+        double s = std::sqrt(t + 1.0);
+        q[3] = 0.5 * s;
+        s = 0.5 / s;
+        q[0] = (m[2][1] - m[1][2]) * s, q[1] = (m[0][2] - m[2][0]) * s, q[2] = (m[1][0] - m[0][1]) * s;
+        return;
+    }
+    int i = 0;
+    if (m[1][1] > m[0][0]) i = 1;
+    if (m[2][2] > m[i][i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    double s = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
+    q[i] = 0.5 * s;
+    s = 0.5 / s;
+    q[3] = (m[k][j] - m[j][k]) * s;
+    q[j] = (m[j][i] + m[i][j]) * s;
+    q[k] = (m[k][i] + m[i][k]) * s;
+}
+
+// doICPVirtualRelative's return value (:536-547): getTranslationAndEulerAngles of the f32 transform, poseFrom = (RzRyRx(roll, pitch,
+// yaw), (x, y, z)), poseFrom.between(identity) = poseFrom^-1, in double
+void relative_pose(const double T[16], double q[4], double t[3]) {
+    const float x = static_cast<float>(T[3]), y = static_cast<float>(T[7]), z = static_cast<float>(T[11]);
+    const float roll = std::atan2(static_cast<float>(T[9]), static_cast<float>(T[10]));
+    const float pitch = std::asin(-static_cast<float>(T[8]));
+    const float yaw = std::atan2(static_cast<float>(T[4]), static_cast<float>(T[0]));
+    // gtsam Rot3::RzRyRx (Rot3M.cpp)
+    const double cx = std::cos(double(roll)), sx = std::sin(double(roll)), cy = std::cos(double(pitch)), sy = std::sin(double(pitch));
+    const double cz = std::cos(double(yaw)), sz = std::sin(double(yaw));
+    const double ss_ = sx * sy, cs_ = cx * sy, sc_ = sx * cy, cc_ = cx * cy, c_s = cx * sz, s_s = sx * sz, _cs = cy * sz, _cc = cy * cz;
+    const double s_c = sx * cz, c_c = cx * cz, ssc = ss_ * cz, csc = cs_ * cz, sss = ss_ * sz, css = cs_ * sz;
+    const double R[3][3] = {{_cc, -c_s + ssc, s_s + csc}, {_cs, c_c + sss, -s_c + css}, {-sy, sc_, cc_}};
+    double Rt[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Rt[r][c] = R[c][r];
+    const double p[3] = {x, y, z};
+    for (int r = 0; r < 3; ++r) t[r] = -((Rt[r][0] * p[0] + Rt[r][1] * p[1]) + Rt[r][2] * p[2]);
+    quat_from_matrix(Rt, q);
+}
+
+}  // namespace
+
+void pose6_from(const double q[4], const double t[3], double p6[6]) {
+    p6[0] = t[0], p6[1] = t[1], p6[2] = t[2];
+    rpy_from_quat(q, &p6[3], &p6[4], &p6[5]);
+}
+
+KeyframeStore::~KeyframeStore() {
+    (void)hipSetDevice(device);
+    if (vstream) (void)hipStreamSynchronize(vstream);
+    if (icp) scal_icp_destroy(icp);
+}
+
+int KeyframeStore::init(int dev, int points, int keyframes) {
+    device = dev, max_points = points, max_keyframes = keyframes;
+    db_of_own.reserve(static_cast<size_t>(keyframes));
+    pose6.reserve(static_cast<size_t>(keyframes));
+    if (!keeps_clouds()) return SCAL_OK;
+    SCAL_TRY(arena.alloc(static_cast<size_t>(points)));
+    SCAL_TRY(d_off.alloc(static_cast<size_t>(keyframes) + 1));
+    SCAL_TRY(d_overflow.alloc(1));
+    SCAL_TRY(h_off.alloc(static_cast<size_t>(keyframes) + 1));
+    SCAL_TRY(h_overflow.alloc(1));
+    SCAL_TRY(ev_append.create(hipEventDisableTiming));
+    h_off.p[0] = 0, h_overflow.p[0] = 0;
+    // verification: lane 5 (scal_pipeline's busy chains are on lanes 0, 1, 3 and 4)
+    SCAL_TRY(vstream.acquire(dev, 5));
+    SCAL_TRY(vf.init(points));
+    vf.set_tag(".V");
+    for (DevBuf<float4>* b : {&raw_src, &raw_tgt, &ds_src, &ds_tgt}) SCAL_TRY(b->alloc(static_cast<size_t>(points)));
+    for (DevBuf<float>* b : {&sx, &sy, &sz, &sw, &ox, &oy, &oz, &ow}) SCAL_TRY(b->alloc(static_cast<size_t>(points)));
+    SCAL_TRY(d_n.alloc(2));
+    SCAL_TRY(h_cnt.alloc(2));
+    scal_icp_config ic{};
+    ic.max_corr_dist = 150, ic.max_iterations = 100, ic.transformation_epsilon = 1e-6, ic.fitness_epsilon = 1e-6;  // :519-523
+    ic.max_source = points, ic.max_target = points, ic.device = dev;
+    SCAL_TRY(icp_create_on_lane(&ic, 5, &icp));
+    SCAL_HIP(hipMemsetAsync(d_off.p, 0, sizeof(int), vstream));
+    SCAL_HIP(hipMemsetAsync(d_overflow.p, 0, sizeof(int), vstream));
+    SCAL_HIP(hipStreamSynchronize(vstream));
+    return SCAL_OK;
+}
+
+int KeyframeStore::own_count() {
+    std::lock_guard<std::mutex> lk(mu);
+    return static_cast<int>(db_of_own.size());
+}
+
+namespace {
+struct AppendArgs {
+    KeyframeStore* st;
+    int j;
+};
+int append_hook(void* user, hipStream_t s, const ScFilterOut& ds) {
+    auto* a = static_cast<AppendArgs*>(user);
+    KeyframeStore* st = a->st;
+    const int grid = std::max(1, std::min(div_up(ds.cap, 256), 256));
+    hipLaunchKernelGGL(k_kf_append, dim3(grid), dim3(256), 0, s, ds.x, ds.y, ds.z, ds.w, ds.d_n, st->arena.p, st->d_off.p, a->j, st->max_points,
+                       st->d_overflow.p);
+    SCAL_HIP(hipGetLastError());
+    SCAL_HIP(hipMemcpyAsync(st->h_off.p + a->j + 1, st->d_off.p + a->j + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipMemcpyAsync(st->h_overflow.p, st->d_overflow.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipEventRecord(st->ev_append, s));
+    return SCAL_OK;
+}
+}  // namespace
+
+int KeyframeStore::insert(scal_sc_t* sc, scal_features_t* feat, int db_index, const double p6[6]) {
+    int j;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        j = static_cast<int>(db_of_own.size());
+    }
+    if (j >= max_keyframes) {
+        set_error("scal_pipeline: more than %d keyframes (sc_max_keyframes)", max_keyframes);
+        return SCAL_E_CAPACITY;
+    }
+    if (keeps_clouds()) {
+        AppendArgs a{this, j};
+        SCAL_TRY(sc_insert_features_then(sc, feat, append_hook, &a));
+    } else {
+        SCAL_TRY(scal_sc_insert_features(sc, feat));
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    db_of_own.push_back(db_index);
+    pose6.push_back({p6[0], p6[1], p6[2], p6[3], p6[4], p6[5]});
+    return SCAL_OK;
+}
+
+int KeyframeStore::check() {
+    if (!keeps_clouds()) return SCAL_OK;
+    const int n = own_count();  // only stage D's thread inserts and checks
+    if (checked == n) return SCAL_OK;
+    SCAL_HIP(hipSetDevice(device));
+    SCAL_HIP(hipEventSynchronize(ev_append));
+    if (h_overflow.p[0]) {
+        set_error("scal_pipeline: the keyframe cloud store is full (kf_max_points = %d, keyframe %d does not fit)", max_points, n - 1);
+        return SCAL_E_CAPACITY;
+    }
+    std::lock_guard<std::mutex> lk(mu);
+    checked = n;
+    return SCAL_OK;
+}
+
+int KeyframeStore::verify(const KfLoopJob& job, double fitness_thres, scal_pipeline_loop* out) {
+    std::memset(out, 0, sizeof *out);
+    out->seq = job.seq, out->curr_kf = job.curr_kf, out->loop_kf = job.loop_kf, out->yaw_rad = job.yaw_rad, out->min_dist = job.min_dist;
+    out->verified = -1;
+    out->fitness = std::numeric_limits<double>::max();
+    for (int k = 0; k < 16; ++k) out->T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    out->q_rel[3] = 1.0;
+    int jc, jl, j0, j1;
+    Aff34 T;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        if (!keeps_clouds()) return SCAL_OK;
+        auto own = [&](int db) {
+            auto it = std::lower_bound(db_of_own.begin(), db_of_own.end(), db);
+            return (it != db_of_own.end() && *it == db) ? static_cast<int>(it - db_of_own.begin()) : -1;
+        };
+        jc = own(job.curr_kf), jl = own(job.loop_kf);
+        if (jc < 0 || jl < 0 || jc >= checked) return SCAL_OK;
+        // loopFindNearKeyframesCloud(target, loop, 25, loop): keyframes loop-25 .. loop+25 that have a cloud, in keyframe order
+        const int submap = 25;  // historyKeyframeSearchNum (:502)
+        j0 = static_cast<int>(std::lower_bound(db_of_own.begin(), db_of_own.end(), job.loop_kf - submap) - db_of_own.begin());
+        j1 = static_cast<int>(std::upper_bound(db_of_own.begin(), db_of_own.end(), job.loop_kf + submap) - db_of_own.begin()) - 1;
+        j1 = std::min(j1, checked - 1);
+        T = affine_f32(pose6[static_cast<size_t>(jl)].data());  // every keyframe is moved by the ROOT (loop) keyframe's pose (:506-507)
+    }
+    const int n_src = h_off.p[jc + 1] - h_off.p[jc], n_tgt = h_off.p[j1 + 1] - h_off.p[j0];
+    SCAL_HIP(hipSetDevice(device));
+    hipStream_t s = vstream;
+    SCAL_HIP(hipStreamWaitEvent(s, ev_append, 0));  // behind the current keyframe's append (and every earlier one)
+    int n_ds[2] = {0, 0};
+    float4* raw[2] = {raw_src.p, raw_tgt.p};
+    float4* ds[2] = {ds_src.p, ds_tgt.p};
+    const int jr0[2] = {jc, j0}, jr1[2] = {jc, j1}, nr[2] = {n_src, n_tgt};
+    for (int c = 0; c < 2; ++c) {
+        if (nr[c] <= 0) continue;
+        const int grid = std::min(div_up(nr[c], 256), 1024);
+        hipLaunchKernelGGL(k_kf_submap, dim3(grid), dim3(256), 0, s, arena.p, d_off.p, jr0[c], jr1[c], T, raw[c], d_n.p);
+        SCAL_HIP(hipGetLastError());
+        // downSizeFilterICP (:491-492): leaf 0.4, the voxel filter of scal_voxel_downsample_device (45 key bits)
+        launch_deinterleave(s, reinterpret_cast<const float*>(raw[c]), nr[c], SoA4{sx.p, sy.p, sz.p, sw.p});
+        SCAL_TRY(vf.run(s, CSoA4{sx.p, sy.p, sz.p, sw.p}, d_n.p, nr[c], 0.4f, 45, SoA4{ox.p, oy.p, oz.p, ow.p}, d_n.p + 1));
+        launch_interleave(s, d_n.p + 1, nr[c], CSoA4{ox.p, oy.p, oz.p, ow.p}, reinterpret_cast<float*>(ds[c]));
+        VoxMeta hm;
+        SCAL_HIP(hipMemcpyAsync(&hm, vf.meta.p, sizeof hm, hipMemcpyDeviceToHost, s));
+        SCAL_HIP(hipMemcpyAsync(h_cnt.p, d_n.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+        SCAL_HIP(hipStreamSynchronize(s));
+        if (hm.error) {
+            set_error("scal_pipeline: loop verification: voxel grid bounding box needs more than 45 key bits");
+            return SCAL_E_CAPACITY;
+        }
+        n_ds[c] = h_cnt.p[0];
+    }
+    out->n_src = n_ds[0], out->n_tgt = n_ds[1];
+    scal_icp_result r;
+    SCAL_TRY(scal_icp_align_device(icp, reinterpret_cast<const float*>(ds_src.p), n_ds[0], reinterpret_cast<const float*>(ds_tgt.p), n_ds[1], &r));
+    out->converged = r.converged, out->iterations = r.iterations, out->state = r.state, out->fitness = r.fitness;
+    std::memcpy(out->T, r.T, sizeof out->T);
+    out->verified = (r.converged && r.fitness <= fitness_thres) ? 1 : 0;  // :531
+    relative_pose(r.T, out->q_rel, out->t_rel);
+    return SCAL_OK;
+}
+
+int KeyframeStore::read(int db_index, double p6[6], float* xyzi, int cap, int* n) {
+    int j, a = 0, b = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        auto it = std::lower_bound(db_of_own.begin(), db_of_own.end(), db_index);
+        if (it == db_of_own.end() || *it != db_index) {
+            set_error("scal_pipeline_keyframe: %d is not a keyframe of this pipeline", db_index);
+            return SCAL_E_ARG;
+        }
+        j = static_cast<int>(it - db_of_own.begin());
+        for (int k = 0; k < 6; ++k) p6[k] = pose6[static_cast<size_t>(j)][static_cast<size_t>(k)];
+        if (keeps_clouds() && j < checked) a = h_off.p[j], b = h_off.p[j + 1];
+    }
+    *n = b - a;
+    const int m = std::min(b - a, cap);
+    if (m > 0) {
+        SCAL_HIP(hipSetDevice(device));
+        SCAL_HIP(hipMemcpy(xyzi, arena.p + a, sizeof(float4) * static_cast<size_t>(m), hipMemcpyDeviceToHost));
+    }
+    return SCAL_OK;
+}
+
+}  // namespace scal
+
+using namespace scal;
+
+// ------------------------------------------------------------------------------------------------ the keyframe gate (host only)
+extern "C" int scal_keyframe_gate_init(scal_keyframe_gate_state* st, double meter_gap, double deg_gap) {
+    if (!st || !std::isfinite(meter_gap) || !std::isfinite(deg_gap) || meter_gap < 0 || deg_gap < 0) {
+        set_error("scal_keyframe_gate_init: bad argument");
+        return SCAL_E_ARG;
+    }
+    std::memset(st, 0, sizeof *st);
+    st->meter_gap = meter_gap;
+    st->rad_gap = deg_gap * (M_PI / 180.0);  // :875-876
+    st->translation_accumulated = 1000000.0, st->rotation_accumulated = 1000000.0;  // :67-68
+    return SCAL_OK;
+}
+
+extern "C" int scal_keyframe_gate(scal_keyframe_gate_state* st, const double q[4], const double t[3], int* is_keyframe) {
+    if (!st || !q || !t || !is_keyframe) {
+        set_error("scal_keyframe_gate: null argument");
+        return SCAL_E_ARG;
+    }
+    const double nq = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    if (!(nq > 0) || !std::isfinite(nq) || !std::isfinite(t[0]) || !std::isfinite(t[1]) || !std::isfinite(t[2])) {
+        set_error("scal_keyframe_gate: the pose must be finite with a non-zero quaternion");
+        return SCAL_E_ARG;
+    }
+    double cur[6];
+    pose6_from(q, t, cur);
+    // diffTransformation (:325-336): SE3_p1^-1 * SE3_p2 in f32 (the inverse of a rigid transform), then getTranslationAndEulerAngles
+    const Aff34 A = affine_f32(st->curr), B = affine_f32(cur);
+    float Ri[3][3], ti[3], D[3][4];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) Ri[r][c] = A.m[4 * c + r];
+    for (int r = 0; r < 3; ++r) ti[r] = -((Ri[r][0] * A.m[3] + Ri[r][1] * A.m[7]) + Ri[r][2] * A.m[11]);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) D[r][c] = (Ri[r][0] * B.m[c] + Ri[r][1] * B.m[4 + c]) + Ri[r][2] * B.m[8 + c] + (c == 3 ? ti[r] : 0.0f);
+    const double dx = std::fabs(double(D[0][3])), dy = std::fabs(double(D[1][3])), dz = std::fabs(double(D[2][3]));
+    const double droll = std::fabs(double(std::atan2(D[2][1], D[2][2]))), dpitch = std::fabs(double(std::asin(-D[2][0])));
+    const double dyaw = std::fabs(double(std::atan2(D[1][0], D[0][0])));
+    std::memcpy(st->curr, cur, sizeof cur);
+    st->translation_accumulated += std::sqrt(dx * dx + dy * dy + dz * dz);
+    st->rotation_accumulated += droll + dpitch + dyaw;  // "sum just naive approach"
+    *is_keyframe = 0;
+    if (st->translation_accumulated > st->meter_gap || st->rotation_accumulated > st->rad_gap) {
+        *is_keyframe = 1;
+        st->translation_accumulated = 0.0, st->rotation_accumulated = 0.0;
+    }
+    return SCAL_OK;
+}

@@ -12,9 +12,15 @@
 //   pose    a collected odometry pose goes straight into stage C's enqueue, which queues behind the stage-C steps still running on
 //           the device (`depth` uncollected); finished steps are collected;
 //   loop    ScanContext's answers, collected one scan behind their searches.
+// sc_mode 3 (keyframes) moves ScanContext behind stage C, as the pose-graph node sits behind laserMapping: the side thread does only the
+// prefetch half (as with ScanContext off); the loop thread becomes stage D - in scan order it waits for the scan's stage-C pose, runs
+// the keyframe gate and, for a keyframe, queues the ScanContext insert with the keyframe store's append behind it and (30 keyframes
+// on) the search, then collects the answer; a detected loop goes to a sixth thread that verifies it (keyframes.hip) on its own stream.
 // Nothing here touches the device except through the per-stage C-ABI, so the poses are those of the per-stage calls.
 #include "common.hpp"
+#include "keyframes.hpp"
 #include <condition_variable>
+#include <deque>
 #include <chrono>
 #include <cstdlib>
 #include <string>
@@ -28,6 +34,7 @@ using namespace scal;
 namespace {
 constexpr int REC_N = 64;      // per-scan records (ring); at most 32 scans may be pushed and not popped
 constexpr int MAX_UNPOPPED = 32;
+constexpr int MAX_LOOPS_UNPOPPED = 64;  // sc_mode 3: loop records detected and not popped
 // development knobs (environment), read once: how far the stages may run ahead of each other
 int env_int(const char* name, int dflt, int lo, int hi) {
     const char* e = std::getenv(name);
@@ -93,8 +100,20 @@ struct scal_pipeline {
     std::string errmsg;
     std::thread t_front, t_side, t_odom, t_pose, t_loop;
     HostTimer tm_front, tm_side, tm_odom, tm_pose, tm_loop;
+    // sc_mode 3: keyframe gate and store (stage D's thread), loops waiting for verification / to be popped
+    KeyframeStore* kf = nullptr;
+    scal_keyframe_gate_state gate{};
+    double fitness_thres = 0.3;
+    std::deque<KfLoopJob> jobs;
+    std::deque<scal_pipeline_loop> loops;
+    bool verifying = false;
+    long long loops_owed = 0;  // detected and not popped
+    std::thread t_verify;
 
     bool sc_on() const { return cfg.sc_mode != SCAL_PIPE_SC_OFF; }
+    bool side_sc() const { return cfg.sc_mode == SCAL_PIPE_SC_EVERY_SCAN || cfg.sc_mode == SCAL_PIPE_SC_DESCRIPTOR; }  // ScanContext behind stage A
+    bool kf_mode() const { return cfg.sc_mode == SCAL_PIPE_SC_KEYFRAME; }
+    bool verify_idle() const { return jobs.empty() && !verifying; }
     Rec& r(long long k) { return rec[k % REC_N]; }
     // one per-stage call for every sequence.  S = 1: the call itself.  S > 1: each sequence's call runs under a recorder (nothing
     // reaches the device), then the S lists are zipped: same kernel, same shape -> one launch with gridDim.z = S.
@@ -190,14 +209,14 @@ void side_thread(scal_pipeline* p) {
         p->cv.wait(lk, [&] {
             if (p->stop || p->err) return true;
             if (p->a_done <= k) return false;
-            return !(p->sc_on() && k - p->d_coll >= 3);  // the ScanContext context holds four searches / descriptors in flight
+            return !(p->side_sc() && k - p->d_coll >= 3);  // the ScanContext context holds four searches / descriptors in flight
         });
         if (p->stop || p->err) return;
         const int slot = static_cast<int>(k % p->ring);
         lk.unlock();
         double* dd = p->d_desc ? p->d_desc + static_cast<size_t>(slot) * 1200 : nullptr;
         int st = p->tm_side.run(1, "C: prefetch, side half + D: insert", [&]() -> int {
-            if (!p->sc_on() && p->S == 1) return scal_map_prefetch_finish(p->mp[0], p->regs[0][slot]);
+            if (!p->side_sc() && p->S == 1) return scal_map_prefetch_finish(p->mp[0], p->regs[0][slot]);
             Recorder recs[2 * SMAX];
             Recorder* ptr[2 * SMAX];
             int nr = 0, rc2 = SCAL_OK;
@@ -211,7 +230,7 @@ void side_thread(scal_pipeline* p) {
                 }
                 return r3;
             });
-            if (rc2 == SCAL_OK && p->sc_on())
+            if (rc2 == SCAL_OK && p->side_sc())
                 rc2 = p->tm_side.run(4, "   record insert", [&] {
                     int r3 = SCAL_OK;
                     for (int q = 0; q < p->S && r3 == SCAL_OK; ++q) {
@@ -242,7 +261,7 @@ void side_thread(scal_pipeline* p) {
         }
         p->r(k).res[0].d_descriptor = dd;
         p->pf_done = k + 1;
-        if (p->sc_on()) p->d_ins = k + 1;
+        if (p->side_sc()) p->d_ins = k + 1;
         p->cv.notify_all();
     }
 }
@@ -378,6 +397,84 @@ void loop_thread(scal_pipeline* p) {  // ScanContext's answers (the searches the
     }
 }
 
+// sc_mode 3, stage D (laserPosegraphOptimization.cpp:590-639, :713-730): scan k's stage-C pose through the keyframe gate, in scan order.  A
+// keyframe is inserted into ScanContext from its features context (keyframe filter 0.4 m + descriptor), its filtered cloud appended to the
+// keyframe store behind the descriptor, and - once the pipeline has 30 keyframes of its own (:715) - searched for.  A scan that is not a
+// keyframe passes at once.  The insert is queued before d_ins lets the front thread reuse the features context.
+void keyframe_thread(scal_pipeline* p) {
+    std::unique_lock<std::mutex> lk(p->mu);
+    for (;;) {
+        const long long k = p->d_coll;
+        p->cv.wait(lk, [&] { return p->stop || p->err || p->c_coll > k; });
+        if (p->stop || p->err) return;
+        scal_pipeline_result& R = p->r(k).res[0];
+        const int slot = static_cast<int>(k % p->ring);
+        lk.unlock();
+        int is_kf = 0;
+        bool detect = false;
+        int st = scal_keyframe_gate(&p->gate, R.q_w_curr, R.t_w_curr, &is_kf);
+        R.is_keyframe = is_kf, R.keyframe_id = -1, R.have_loop = 0;
+        if (st == SCAL_OK && is_kf) {
+            const int id = scal_sc_size(p->sc[0]);
+            double p6[6];
+            pose6_from(R.q_w_curr, R.t_w_curr, p6);
+            st = p->tm_loop.run(0, "D: insert + append", [&] { return p->kf->insert(p->sc[0], p->regs[0][slot], id, p6); });
+            if (st == SCAL_OK) {
+                R.keyframe_id = id;
+                detect = p->kf->own_count() >= 30;  // performSCLoopClosure: keyframePoses.size() < NUM_EXCLUDE_RECENT -> no search
+                if (detect) st = p->tm_loop.run(1, "D: sc_detect_enqueue", [&] { return scal_sc_detect_enqueue(p->sc[0]); });
+            }
+        }
+        lk.lock();
+        if (st != SCAL_OK) {
+            p->fail(st);
+            return;
+        }
+        p->d_ins = k + 1;
+        p->cv.notify_all();
+        lk.unlock();
+        if (detect) {
+            st = p->tm_loop.run(2, "D: sc_detect_collect (wait)", [&] { return scal_sc_detect_collect(p->sc[0], &R.loop); });
+            R.have_loop = st == SCAL_OK;
+        }
+        if (st == SCAL_OK && is_kf) st = p->kf->check();  // the append has run: an overflowing store is reported with this scan
+        lk.lock();
+        if (st != SCAL_OK) {
+            p->fail(st);
+            return;
+        }
+        if (detect && R.loop.loop_id >= 0) {  // scLoopICPBuf (:726)
+            p->jobs.push_back(KfLoopJob{k, R.keyframe_id, R.loop.loop_id, R.loop.yaw_rad, R.loop.min_dist});
+            p->loops_owed++;
+        }
+        p->d_coll = k + 1;
+        p->cv.notify_all();
+    }
+}
+
+// sc_mode 3: process_icp (:777-800) - every detected loop, oldest first, on the keyframe store's own stream
+void verify_thread(scal_pipeline* p) {
+    std::unique_lock<std::mutex> lk(p->mu);
+    for (;;) {
+        p->cv.wait(lk, [&] { return p->stop || p->err || !p->jobs.empty(); });
+        if (p->stop || p->err) return;
+        const KfLoopJob job = p->jobs.front();
+        p->jobs.pop_front();
+        p->verifying = true;
+        lk.unlock();
+        scal_pipeline_loop rec;
+        const int st = p->kf->verify(job, p->fitness_thres, &rec);
+        lk.lock();
+        p->verifying = false;
+        if (st != SCAL_OK) {
+            p->fail(st);
+            return;
+        }
+        p->loops.push_back(rec);
+        p->cv.notify_all();
+    }
+}
+
 int report(scal_pipeline* p) {  // mu held
     set_error("%s", p->errmsg.c_str());
     return p->err;
@@ -388,6 +485,10 @@ int push(scal_pipeline* p, const float* const* d_xyz, const void* const* h_xyz, 
     if (p->err) return report(p);
     if (p->pushed - p->popped >= MAX_UNPOPPED) {
         set_error("scal_pipeline_push: %d results wait to be popped", MAX_UNPOPPED);
+        return SCAL_E_STATE;
+    }
+    if (p->loops_owed >= MAX_LOOPS_UNPOPPED) {
+        set_error("scal_pipeline_push: %d loop records wait to be popped (scal_pipeline_pop_loop)", MAX_LOOPS_UNPOPPED);
         return SCAL_E_STATE;
     }
     const long long k = p->pushed;
@@ -433,18 +534,33 @@ int create(const scal_pipeline_config* cfg, int n_seqs, scal_pipeline_t** out) {
     }
     *out = nullptr;
     const int ring = cfg->ring == 0 ? 6 : cfg->ring, depth = cfg->depth == 0 ? 2 : cfg->depth;
-    if (ring < 4 || ring > 16 || depth < 1 || depth > 3 || cfg->sc_mode < 0 || cfg->sc_mode > 2) {
-        set_error("scal_pipeline_create: ring must be 4..16, depth 1..3, sc_mode 0..2");
+    if (ring < 4 || ring > 16 || depth < 1 || depth > 3 || cfg->sc_mode < 0 || cfg->sc_mode > 3) {
+        set_error("scal_pipeline_create: ring must be 4..16, depth 1..3, sc_mode 0..3");
         return SCAL_E_ARG;
     }
-    if (n_seqs < 1 || n_seqs > SMAX || (n_seqs > 1 && cfg->sc_mode == SCAL_PIPE_SC_DESCRIPTOR)) {
-        set_error("scal_pipeline_create_multi: 1..%d sequences (sc_mode 2 only with one)", SMAX);
+    if (n_seqs < 1 || n_seqs > SMAX || (n_seqs > 1 && (cfg->sc_mode == SCAL_PIPE_SC_DESCRIPTOR || cfg->sc_mode == SCAL_PIPE_SC_KEYFRAME))) {
+        set_error("scal_pipeline_create_multi: 1..%d sequences (sc_mode 2 and 3 only with one)", SMAX);
         return SCAL_E_ARG;
+    }
+    scal_keyframe_gate_state gate{};
+    if (cfg->sc_mode == SCAL_PIPE_SC_KEYFRAME) {  // zero: the reference's defaults (:874-876, :531)
+        if (cfg->kf_max_points < 0 || !(cfg->loop_fitness_thres >= 0) || cfg->sc_max_keyframes <= 0 ||
+            scal_keyframe_gate_init(&gate, cfg->keyframe_meter_gap == 0 ? 2.0 : cfg->keyframe_meter_gap,
+                                    cfg->keyframe_deg_gap == 0 ? 10.0 : cfg->keyframe_deg_gap) != SCAL_OK) {
+            set_error("scal_pipeline_create: sc_mode 3 needs keyframe gaps >= 0, kf_max_points >= 0, loop_fitness_thres >= 0, sc_max_keyframes > 0");
+            return SCAL_E_ARG;
+        }
     }
     SCAL_TRY(select_device(cfg->device));
     auto* p = new scal_pipeline();
     p->cfg = *cfg, p->ring = ring, p->depth = depth, p->S = n_seqs;
+    p->gate = gate;
+    p->fitness_thres = cfg->loop_fitness_thres == 0 ? 0.3 : cfg->loop_fitness_thres;
     int rc = SCAL_OK;
+    if (p->kf_mode()) {
+        p->kf = new KeyframeStore();
+        rc = p->kf->init(cfg->device, cfg->kf_max_points, cfg->sc_max_keyframes);
+    }
     scal_features_config fc{};
     fc.lidar_type = cfg->lidar_type, fc.n_scans = cfg->n_scans, fc.minimum_range = cfg->minimum_range, fc.max_points = cfg->max_points;
     fc.float_math = cfg->float_math, fc.check_finite = cfg->check_finite, fc.device = cfg->device;
@@ -496,7 +612,8 @@ int create(const scal_pipeline_config* cfg, int n_seqs, scal_pipeline_t** out) {
     p->t_side = std::thread(side_thread, p);
     p->t_odom = std::thread(odom_thread, p);
     p->t_pose = std::thread(pose_thread, p);
-    if (p->sc_on()) p->t_loop = std::thread(loop_thread, p);
+    if (p->side_sc()) p->t_loop = std::thread(loop_thread, p);
+    if (p->kf_mode()) p->t_loop = std::thread(keyframe_thread, p), p->t_verify = std::thread(verify_thread, p);
     *out = p;
     return SCAL_OK;
 }
@@ -519,6 +636,7 @@ extern "C" void scal_pipeline_destroy(scal_pipeline_t* p) {
     if (p->t_odom.joinable()) p->t_odom.join();
     if (p->t_pose.joinable()) p->t_pose.join();
     if (p->t_loop.joinable()) p->t_loop.join();
+    if (p->t_verify.joinable()) p->t_verify.join();
     if (TIMING) {
         p->tm_front.print("front"), p->tm_side.print("side"), p->tm_odom.print("odom"), p->tm_pose.print("pose"), p->tm_loop.print("loop");
         std::fprintf(stderr, "[scal_pipeline] sequences %d, recorded lists flushed in the middle of an entry point: %ld\n", p->S, g_forced_flushes);
@@ -533,6 +651,7 @@ extern "C" void scal_pipeline_destroy(scal_pipeline_t* p) {
     }
     for (int q = 0; q < SMAX; ++q)
         for (auto* f : p->regs[q]) scal_features_destroy(f);
+    delete p->kf;  // after the ScanContext context, whose stream appended to it
     if (p->d_desc && p->own_desc) (void)hipFree(p->d_desc);
     delete p;
 }
@@ -600,10 +719,47 @@ extern "C" int scal_pipeline_drain(scal_pipeline_t* p) {
     p->drain_req = true;
     p->pop_waiting++;  // the loop thread collects its last answer, the pose thread every queued pose
     p->cv.notify_all();
-    p->cv.wait(lk, [&] { return p->err || (p->drained && (!p->sc_on() || p->d_coll == p->pushed)); });
+    p->cv.wait(lk, [&] { return p->err || (p->drained && (!p->sc_on() || p->d_coll == p->pushed) && p->verify_idle()); });
     p->pop_waiting--;
     if (p->err) return report(p);
     return SCAL_OK;
+}
+
+extern "C" int scal_pipeline_pop_loop(scal_pipeline_t* p, scal_pipeline_loop* out, int wait) {
+    if (!p || !out) {
+        set_error("scal_pipeline_pop_loop: null argument");
+        return SCAL_E_ARG;
+    }
+    std::unique_lock<std::mutex> lk(p->mu);
+    if (!p->kf_mode()) {
+        set_error("scal_pipeline_pop_loop: only in sc_mode 3");
+        return SCAL_E_STATE;
+    }
+    for (;;) {
+        if (p->err) return report(p);
+        if (!p->loops.empty()) {
+            *out = p->loops.front();
+            p->loops.pop_front();
+            p->loops_owed--;
+            return 1;
+        }
+        if (!wait || p->verify_idle()) return 0;
+        p->cv.wait(lk);
+    }
+}
+
+extern "C" int scal_pipeline_keyframe(scal_pipeline_t* p, int kf, double pose6[6], float* xyzi, int cap, int* n) {
+    if (!p || !pose6 || !n || cap < 0 || (cap > 0 && !xyzi)) {
+        set_error("scal_pipeline_keyframe: bad argument");
+        return SCAL_E_ARG;
+    }
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (p->err) return report(p);
+    if (!p->kf_mode() || !p->drained || p->d_coll != p->pushed || !p->verify_idle()) {
+        set_error("scal_pipeline_keyframe: only in sc_mode 3, while the pipeline is drained");
+        return SCAL_E_STATE;
+    }
+    return p->kf->read(kf, pose6, xyzi, cap, n);
 }
 
 extern "C" int scal_pipeline_in_flight(scal_pipeline_t* p) {

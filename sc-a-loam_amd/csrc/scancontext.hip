@@ -942,7 +942,7 @@ static int ds_consumed(scal_sc* c) {
     return SCAL_OK;
 }
 
-extern "C" int scal_sc_insert_features(scal_sc_t* c, scal_features_t* feat) {
+int scal::sc_insert_features_then(scal_sc_t* c, scal_features_t* feat, int (*after)(void* user, hipStream_t s, const ScFilterOut& ds), void* user) {
     if (!c || !feat) {
         set_error("scal_sc_insert_features: null argument");
         return SCAL_E_ARG;
@@ -953,8 +953,11 @@ extern "C" int scal_sc_insert_features(scal_sc_t* c, scal_features_t* feat) {
     int cap;
     SCAL_TRY(ds_features(c, feat, &d_n, &cap));
     SCAL_TRY(make_into(c, c->dsx.p, c->dsy.p, c->dsz.p, 1, d_n, cap, true));
+    if (after) SCAL_TRY(after(user, c->stream, ScFilterOut{c->dsx.p, c->dsy.p, c->dsz.p, c->dsw.p, d_n, cap}));  // before ds_consumed
     return ds_consumed(c);
 }
+
+extern "C" int scal_sc_insert_features(scal_sc_t* c, scal_features_t* feat) { return sc_insert_features_then(c, feat, nullptr, nullptr); }
 
 static int make_features(scal_sc_t* c, scal_features_t* feat, double* d_desc, bool wait) {
     if (!c || !feat || !d_desc) {

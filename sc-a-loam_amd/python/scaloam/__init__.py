@@ -92,13 +92,25 @@ class PipelineConfig(C.Structure):
     _fields_ = [("lidar_type", C.c_int), ("n_scans", C.c_int), ("minimum_range", C.c_double), ("max_points", C.c_int),
                 ("float_math", C.c_int), ("check_finite", C.c_int), ("line_res", C.c_float), ("plane_res", C.c_float),
                 ("max_map_points", C.c_int), ("sc_max_radius", C.c_double), ("sc_dist_thres", C.c_double), ("sc_max_keyframes", C.c_int),
-                ("sc_mode", C.c_int), ("device", C.c_int), ("ring", C.c_int), ("depth", C.c_int), ("d_desc_ring", C.c_void_p)]
+                ("sc_mode", C.c_int), ("device", C.c_int), ("ring", C.c_int), ("depth", C.c_int), ("d_desc_ring", C.c_void_p),
+                ("keyframe_meter_gap", C.c_double), ("keyframe_deg_gap", C.c_double), ("kf_max_points", C.c_int), ("loop_fitness_thres", C.c_double)]
 
 
 class PipelineResult(C.Structure):
     _fields_ = [("seq", C.c_longlong), ("q_w_curr", C.c_double * 4), ("t_w_curr", C.c_double * 3), ("q_odom", C.c_double * 4),
                 ("t_odom", C.c_double * 3), ("odom", OdomStats), ("map", MapStats), ("have_loop", C.c_int), ("loop", SCResult),
-                ("d_descriptor", C.c_void_p)]
+                ("d_descriptor", C.c_void_p), ("is_keyframe", C.c_int), ("keyframe_id", C.c_int)]
+
+
+class PipelineLoop(C.Structure):
+    _fields_ = [("seq", C.c_longlong), ("curr_kf", C.c_int), ("loop_kf", C.c_int), ("yaw_rad", C.c_float), ("min_dist", C.c_double),
+                ("verified", C.c_int), ("converged", C.c_int), ("iterations", C.c_int), ("state", C.c_int), ("fitness", C.c_double),
+                ("T", C.c_double * 16), ("n_src", C.c_int), ("n_tgt", C.c_int), ("q_rel", C.c_double * 4), ("t_rel", C.c_double * 3)]
+
+
+class KeyframeGateState(C.Structure):
+    _fields_ = [("meter_gap", C.c_double), ("rad_gap", C.c_double), ("translation_accumulated", C.c_double),
+                ("rotation_accumulated", C.c_double), ("curr", C.c_double * 6)]
 
 
 # every symbol include/scaloam_hip.h declares (tests check the library exports all of them)
@@ -119,6 +131,7 @@ EXPORTED_SYMBOLS = [
     "scal_pipeline_create", "scal_pipeline_destroy", "scal_pipeline_push_device", "scal_pipeline_push_host", "scal_pipeline_pop", "scal_pipeline_drain",
     "scal_pipeline_in_flight", "scal_pipeline_sc", "scal_pipeline_map", "scal_pipeline_odom", "scal_pipeline_features",
     "scal_pipeline_create_multi", "scal_pipeline_seqs", "scal_pipeline_push_device_multi", "scal_pipeline_pop_multi", "scal_pipeline_sc_of", "scal_pipeline_map_of",
+    "scal_pipeline_pop_loop", "scal_pipeline_keyframe", "scal_keyframe_gate_init", "scal_keyframe_gate",
 ]
 
 _lib = None
@@ -256,6 +269,10 @@ def lib():
     L.scal_pipeline_seqs.argtypes = [vp]
     L.scal_pipeline_push_device_multi.argtypes = [vp, C.POINTER(C.c_void_p), _i32p, C.c_int]
     L.scal_pipeline_pop_multi.argtypes = [vp, C.POINTER(PipelineResult)]
+    L.scal_pipeline_pop_loop.argtypes = [vp, C.POINTER(PipelineLoop), C.c_int]
+    L.scal_pipeline_keyframe.argtypes = [vp, C.c_int, _f64p, _f32p, C.c_int, _i32p]
+    L.scal_keyframe_gate_init.argtypes = [C.POINTER(KeyframeGateState), C.c_double, C.c_double]
+    L.scal_keyframe_gate.argtypes = [C.POINTER(KeyframeGateState), _f64p, _f64p, _i32p]
     for fn in ("scal_pipeline_sc_of", "scal_pipeline_map_of"):
         getattr(L, fn).restype = C.c_void_p
         getattr(L, fn).argtypes = [vp, C.c_int]
@@ -857,7 +874,22 @@ def factors_eval(kind, cp, pa, pb, x7, device=0):
 
 
 # ---------------------------------------------------------------------------------------------- the four stages as one object
-SC_OFF, SC_EVERY_SCAN, SC_DESCRIPTOR = 0, 1, 2
+SC_OFF, SC_EVERY_SCAN, SC_DESCRIPTOR, SC_KEYFRAME = 0, 1, 2, 3
+
+
+class KeyframeGate:
+    """scal_keyframe_gate: the pose-graph node's keyframe gate (laserPosegraphOptimization.cpp:598-617) in the library, host only (no GPU
+    needed); the same decisions as scaloam.pgo.KeyframeGate.  gate(q_xyzw, t_xyz) -> True for a keyframe."""
+
+    def __init__(self, meter_gap=2.0, deg_gap=10.0):
+        self.st = KeyframeGateState()
+        _check(lib().scal_keyframe_gate_init(C.byref(self.st), float(meter_gap), float(deg_gap)))
+
+    def __call__(self, q_xyzw, t_xyz):
+        q, t = _f64(np.asarray(q_xyzw, np.float64).reshape(4)), _f64(np.asarray(t_xyz, np.float64).reshape(3))
+        k = C.c_int(0)
+        _check(lib().scal_keyframe_gate(C.byref(self.st), q.ctypes.data_as(_f64p), t.ctypes.data_as(_f64p), C.byref(k)))
+        return bool(k.value)
 
 
 def _borrow(cls, handle):
@@ -874,9 +906,12 @@ class Pipeline:
 
     def __init__(self, lidar_type, minimum_range, max_points=400000, line_res=0.4, plane_res=0.8, max_map_points=4000000, sc_mode=SC_EVERY_SCAN,
                  sc_max_radius=80.0, sc_dist_thres=0.2, sc_max_keyframes=8192, device=0, ring=0, depth=0, float_math=0, check_finite=1, d_desc_ring=None,
-                 n_seqs=1):
+                 n_seqs=1, keyframe_meter_gap=0, keyframe_deg_gap=0, kf_max_points=0, loop_fitness_thres=0):
+        """sc_mode=SC_KEYFRAME: the pose-graph node's keyframe path - keyframe gate (0 = 2 m / 10 deg), keyframe clouds kept in a store of
+        kf_max_points points (0 = none, no loop is verified), loops verified by ICP (loop_fitness_thres 0 = 0.3): pop_loop(), keyframe()."""
         self.cfg = PipelineConfig(lidar_type, SCAN_LINES.get(lidar_type, 0), float(minimum_range), max_points, float_math, check_finite, line_res,
-                                  plane_res, max_map_points, sc_max_radius, sc_dist_thres, sc_max_keyframes, sc_mode, device, ring, depth, d_desc_ring)
+                                  plane_res, max_map_points, sc_max_radius, sc_dist_thres, sc_max_keyframes, sc_mode, device, ring, depth, d_desc_ring,
+                                  float(keyframe_meter_gap), float(keyframe_deg_gap), int(kf_max_points), float(loop_fitness_thres))
         self.h = C.c_void_p()
         self.n_seqs = n_seqs
         _check(lib().scal_pipeline_create_multi(C.byref(self.cfg), n_seqs, C.byref(self.h)))
@@ -902,7 +937,8 @@ class Pipeline:
     @staticmethod
     def _res(r):
         return dict(seq=r.seq, q=np.array(r.q_w_curr[:]), t=np.array(r.t_w_curr[:]), q_odom=np.array(r.q_odom[:]), t_odom=np.array(r.t_odom[:]),
-                    odom=r.odom, map=r.map, loop=SCManager._result(r.loop) if r.have_loop else None, d_descriptor=r.d_descriptor)
+                    odom=r.odom, map=r.map, loop=SCManager._result(r.loop) if r.have_loop else None, d_descriptor=r.d_descriptor,
+                    is_keyframe=bool(r.is_keyframe), keyframe_id=r.keyframe_id)
 
     def pop(self):
         r = PipelineResult()
@@ -923,6 +959,26 @@ class Pipeline:
 
     def drain(self):
         _check(lib().scal_pipeline_drain(self.h))
+
+    def pop_loop(self, wait=True):
+        """sc_mode 3: the oldest verified / rejected loop record (dict), or None when none is ready (wait=False) or none is pending"""
+        r = PipelineLoop()
+        rc = lib().scal_pipeline_pop_loop(self.h, C.byref(r), 1 if wait else 0)
+        _check(min(rc, 0))
+        if rc == 0:
+            return None
+        return dict(seq=r.seq, curr_kf=r.curr_kf, loop_kf=r.loop_kf, yaw=r.yaw_rad, min_dist=r.min_dist, verified=r.verified,
+                    converged=r.converged, iterations=r.iterations, state=r.state, fitness=r.fitness, T=np.array(r.T[:]).reshape(4, 4),
+                    n_src=r.n_src, n_tgt=r.n_tgt, q_rel=np.array(r.q_rel[:]), t_rel=np.array(r.t_rel[:]))
+
+    def keyframe(self, kf):
+        """sc_mode 3, drained: (pose6 x y z roll pitch yaw, stored 0.4 m xyzi cloud) of keyframe kf (database index)"""
+        pose = np.zeros(6)
+        n = C.c_int(0)
+        _check(lib().scal_pipeline_keyframe(self.h, kf, pose.ctypes.data_as(_f64p), None, 0, C.byref(n)))
+        cloud = np.zeros((max(n.value, 1), 4), np.float32)
+        _check(lib().scal_pipeline_keyframe(self.h, kf, pose.ctypes.data_as(_f64p), cloud.ctypes.data_as(_f32p), n.value, C.byref(n)))
+        return pose, cloud[:n.value].copy()
 
     def in_flight(self):
         return lib().scal_pipeline_in_flight(self.h)

@@ -114,3 +114,56 @@ def read_g2o(path):
             v = [float(x) for x in w[3:10]]
             E.append((int(w[1]), int(w[2]), np.array(v[:3]), np.array(v[3:])))
     return V, E
+
+
+def local2global_f32(xyzi, pose6):
+    """local2global (:338-359): the cloud moved by pcl::getTransformation(pose6) in f32, each coordinate ((T0 x + T1 y) + T2 z) + T3 rounded
+    operation by operation; intensity kept"""
+    T = _affine_f32(*pose6)
+    p = np.asarray(xyzi, np.float32)
+    out = p.copy()
+    for r in range(3):
+        out[:, r] = ((T[r, 0] * p[:, 0] + T[r, 1] * p[:, 1]) + T[r, 2] * p[:, 2]) + T[r, 3]
+    return out
+
+
+def _quat_from_matrix(m):
+    """Eigen::Quaterniond(Matrix3d) (gtsam Rot3::toQuaternion), (x, y, z, w)"""
+    q = np.zeros(4)
+    t = m[0, 0] + m[1, 1] + m[2, 2]
+    if t > 0:
+        s = np.sqrt(t + 1.0)
+        q[3] = 0.5 * s
+        s = 0.5 / s
+        q[0], q[1], q[2] = (m[2, 1] - m[1, 2]) * s, (m[0, 2] - m[2, 0]) * s, (m[1, 0] - m[0, 1]) * s
+        return q
+    i = 0
+    if m[1, 1] > m[0, 0]:
+        i = 1
+    if m[2, 2] > m[i, i]:
+        i = 2
+    j, k = (i + 1) % 3, (i + 2) % 3
+    s = np.sqrt(m[i, i] - m[j, j] - m[k, k] + 1.0)
+    q[i] = 0.5 * s
+    s = 0.5 / s
+    q[3] = (m[k, j] - m[j, k]) * s
+    q[j] = (m[j, i] + m[i, j]) * s
+    q[k] = (m[k, i] + m[i, k]) * s
+    return q
+
+
+def relative_pose_from_icp(T):
+    """doICPVirtualRelative's return value (:536-547): pcl::getTranslationAndEulerAngles of the f32 ICP transform, poseFrom =
+    Pose3(Rot3::RzRyRx(roll, pitch, yaw), (x, y, z)), poseFrom.between(identity) -> (q_xyzw, t) in double"""
+    T = np.asarray(T, np.float64).reshape(4, 4).astype(np.float32)
+    x, y, z = T[0, 3], T[1, 3], T[2, 3]
+    roll, pitch, yaw = np.arctan2(T[2, 1], T[2, 2]), np.arcsin(-T[2, 0]), np.arctan2(T[1, 0], T[0, 0])
+    cr, sr, cp, sp, cy, sy = (np.cos(float(roll)), np.sin(float(roll)), np.cos(float(pitch)), np.sin(float(pitch)),
+                              np.cos(float(yaw)), np.sin(float(yaw)))
+    Rx = np.array([[1, 0, 0], [0, cr, -sr], [0, sr, cr]])
+    Ry = np.array([[cp, 0, sp], [0, 1, 0], [-sp, 0, cp]])
+    Rz = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1]])
+    R = Rz @ Ry @ Rx
+    Rt = R.T
+    t = -(Rt @ np.array([float(x), float(y), float(z)]))
+    return _quat_from_matrix(Rt), t
