@@ -478,6 +478,7 @@ typedef struct {
     double keyframe_deg_gap;      /* keyframe_deg_gap rosparam, 0 = 10 deg (:875) */
     int kf_max_points;            /* keyframe cloud store, points over all keyframes; 0 = no clouds kept, no loop is verified */
     double loop_fitness_thres;    /* loopFitnessScoreThreshold, 0 = 0.3 (:531) */
+    int pgo_map_max_points;       /* sc_mode 3: capacity of the pose-graph map in points before its filter; 0 = no map buffers */
 } scal_pipeline_config;
 typedef struct {
     long long seq;                        /* 0, 1, 2 ... in push order */
@@ -543,6 +544,28 @@ int scal_pipeline_pop_loop(scal_pipeline_t* p, scal_pipeline_loop* out, int wait
  * stored 0.4 m cloud (the one keyframeLaserClouds holds, :629-634): *n = its size, the first min(*n, cap) xyzi records go to xyzi
  * (host; may be NULL with cap 0).  *n = 0 when no clouds are kept.  SCAL_E_ARG for a pre-filled entry or an unknown index. */
 int scal_pipeline_keyframe(scal_pipeline_t* p, int kf, double pose6[6], float* xyzi, int cap, int* n);
+/* updatePoses (:408-431): the caller's optimized poses for n keyframes of this pipeline, given by database index (as keyframe_id /
+ * curr_kf / loop_kf); pose6 = x y z roll pitch yaw (keyframePosesUpdated's Pose6D, the layout scal_pipeline_keyframe returns).
+ * Allowed at any time, drained or with scans in flight.  All or nothing: SCAL_E_ARG (and nothing changes) when an id is not a keyframe
+ * stage D has assigned to this pipeline (pre-filled entries and unknown ids are refused) or a pose is not finite.  The latest update
+ * of a keyframe wins; one never updated keeps its gated pose (:636).  The loop verification (loopFindNearKeyframesCloud, :479-486)
+ * moves both ICP clouds by the loop keyframe's updated pose: a loop whose query scan was pushed after this call returned sees this
+ * update, one whose query scan was pushed before sees the poses that held when that scan was pushed - whatever the device timing, the
+ * schedule or a drain.  scal_pipeline_keyframe keeps returning the gated pose. */
+int scal_pipeline_update_keyframe_poses(scal_pipeline_t* p, const int* kf, const double* pose6 /* [n][6] */, int n);
+/* pubMap (:810-834) on the device: the pipeline's own keyframes with database index < kf_end, counted in their own order (node_idx),
+ * every skip-th starting with the first (the reference: skip 2, kf_end = recentIdxUpdated), each moved by its current pose (the latest
+ * update) with local2global's f32 arithmetic (:338-359), concatenated in keyframe order and filtered by pcl::VoxelGrid(leaf)
+ * (mapviz_filter_size 0.4, :895-896; PCL's "leaf size too small" guard included: output = input), in PCL order.  *n_out = points of
+ * the map; its first min(*n_out, cap) xyzi records go to out_xyzi (host; NULL with cap 0 allowed).  Allowed with scans in flight: it
+ * never waits for stage D nor queues work on the pipeline's streams, and returns when the map is complete; concurrent calls run one
+ * after the other.  SCAL_E_STATE: sc_mode is not 3, pgo_map_max_points is 0, or kf_end is beyond the keyframes whose append stage D
+ * has confirmed (every keyframe_id popped so far is confirmed).  SCAL_E_CAPACITY: more selected points than pgo_map_max_points
+ * (*n_out = the points needed, nothing runs), or a bounding box that needs more than 45 key bits.  SCAL_E_ARG: leaf not finite and
+ * > 0, skip < 1, kf_end < 0. */
+int scal_pipeline_pgo_map(scal_pipeline_t* p, int kf_end, int skip, float leaf, float* out_xyzi, long long cap, long long* n_out);
+/* the last map scal_pipeline_pgo_map built: xyzi records in device memory, valid until the next call or destroy; NULL before the first */
+const float* scal_pipeline_pgo_map_device(scal_pipeline_t* p, long long* n);
 
 /* ---- the keyframe gate (:598-617 with getOdom :312-323 and diffTransformation :325-336), host only, no device needed.  The
  * accumulators start at 1e6 (:67-68), so the first pose is a keyframe; roll/pitch/yaw from tf's getRPY in double, the delta through

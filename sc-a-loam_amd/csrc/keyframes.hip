@@ -4,7 +4,11 @@
 //    ScanContext's keyframe filter, still in HBM - to an xyzi arena on the ScanContext stream (k_kf_append), nothing is read back;
 //  - the loop verification (loopFindNearKeyframesCloud / doICPVirtualRelative, :472-548) on a stream of its own: the source and the
 //    target submap are moved by the loop keyframe's pose (k_kf_submap: local2global, :338-359), filtered at 0.4 m by the device voxel
-//    filter and aligned by the exact-NN ICP; the acceptance test (:531) and the relative pose (:536-547) are computed on the host.
+//    filter and aligned by the exact-NN ICP; the acceptance test (:531) and the relative pose (:536-547) are computed on the host;
+//  - the caller's optimized poses (updatePoses, :408-431 -> keyframePosesUpdated), versioned by the push counter so that each
+//    verification sees the poses that held when its query scan was pushed;
+//  - the pose-graph map (pubMap, :810-834) on a stream of its own: every skip-th keyframe moved by its current pose (k_pgo_gather: one
+//    launch for all of them, straight into the voxel filter's SoA planes with the filter's bounding box), then the device voxel filter.
 // The clouds never leave HBM.
 #include "keyframes.hpp"
 #include <algorithm>
@@ -12,6 +16,64 @@
 #include <limits>
 
 namespace scal {
+
+// pubMap's local2global + concatenation (:815-822) of n_sel keyframes into map positions [0, n): position i lies in table entry s with
+// xf[s].dst <= i < xf[s + 1].dst and is arena record xf[s].src + (i - xf[s].dst), moved by xf[s].m exactly as k_kf_submap moves it.
+// A fixed grid (<= 256 workgroups: the filter's key kernel reduces one bounding box per workgroup in every workgroup) of contiguous
+// chunks; each thread carries its table entry forward (positions only grow), so the table is searched once per workgroup.  Per point
+// one 16-byte load (PGO_ITEMS of them in flight per thread) and four coalesced 4-byte stores into the planes the filter reads.
+constexpr int PGO_ITEMS = 4, PGO_TILE = 256 * PGO_ITEMS, PGO_MAX_BLOCKS = 256;
+static __global__ void __launch_bounds__(256) k_pgo_gather(const float4* __restrict__ arena, const PgoXf* __restrict__ xf, int n_sel, int n, int chunk,
+                                                           float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz,
+                                                           float* __restrict__ ow, unsigned* __restrict__ parts, int* __restrict__ d_n) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *d_n = n;  // the filter's device-side count
+    const int c0 = blockIdx.x * chunk, c1 = static_cast<int>(min(static_cast<long long>(n), static_cast<long long>(c0) + chunk));
+    int s = 0;
+    for (int hi = n_sel - 1; s < hi;) {  // the last entry with dst <= c0 (entries of empty keyframes share their dst)
+        const int mid = (s + hi + 1) >> 1;
+        if (xf[mid].dst <= c0) s = mid;
+        else hi = mid - 1;
+    }
+    int s_src = xf[s].src, s_dst = xf[s].dst, next = xf[s + 1].dst;
+    int cur = -1;
+    float T[12];
+    unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    for (int t0 = c0; t0 < c1; t0 += PGO_TILE) {
+        float4 p[PGO_ITEMS];
+        int seg[PGO_ITEMS];
+#pragma unroll
+        for (int j = 0; j < PGO_ITEMS; ++j) {
+            const int i = t0 + j * 256 + static_cast<int>(threadIdx.x);
+            seg[j] = -1;
+            if (i < c1) {
+                while (i >= next) s_dst = next, s_src = xf[++s].src, next = xf[s + 1].dst;
+                seg[j] = s;
+                p[j] = arena[s_src + (i - s_dst)];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < PGO_ITEMS; ++j) {
+            if (seg[j] < 0) continue;
+            if (seg[j] != cur) {
+                cur = seg[j];
+                const float4* m = reinterpret_cast<const float4*>(xf[cur].m);
+                const float4 a = m[0], b = m[1], c = m[2];
+                T[0] = a.x, T[1] = a.y, T[2] = a.z, T[3] = a.w, T[4] = b.x, T[5] = b.y, T[6] = b.z, T[7] = b.w;
+                T[8] = c.x, T[9] = c.y, T[10] = c.z, T[11] = c.w;
+            }
+            const float x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p[j].x), __fmul_rn(T[1], p[j].y)), __fmul_rn(T[2], p[j].z)), T[3]);
+            const float y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], p[j].x), __fmul_rn(T[5], p[j].y)), __fmul_rn(T[6], p[j].z)), T[7]);
+            const float z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], p[j].x), __fmul_rn(T[9], p[j].y)), __fmul_rn(T[10], p[j].z)), T[11]);
+            const int i = t0 + j * 256 + static_cast<int>(threadIdx.x);
+            ox[i] = x, oy[i] = y, oz[i] = z, ow[i] = p[j].w;
+            const unsigned u[3] = {vox_ordered(x), vox_ordered(y), vox_ordered(z)};
+#pragma unroll
+            for (int a = 0; a < 3; ++a) lo[a] = min(lo[a], u[a]), hi[a] = max(hi[a], u[a]);
+        }
+    }
+    vox_bbox_block_store(parts, blockIdx.x, lo, hi);
+}
+
 namespace {
 
 struct Aff34 {
@@ -140,13 +202,15 @@ void pose6_from(const double q[4], const double t[3], double p6[6]) {
 KeyframeStore::~KeyframeStore() {
     (void)hipSetDevice(device);
     if (vstream) (void)hipStreamSynchronize(vstream);
+    if (mstream) (void)hipStreamSynchronize(mstream);
     if (icp) scal_icp_destroy(icp);
 }
 
-int KeyframeStore::init(int dev, int points, int keyframes) {
-    device = dev, max_points = points, max_keyframes = keyframes;
+int KeyframeStore::init(int dev, int points, int keyframes, int map_points) {
+    device = dev, max_points = points, max_keyframes = keyframes, map_cap = map_points;
     db_of_own.reserve(static_cast<size_t>(keyframes));
     pose6.reserve(static_cast<size_t>(keyframes));
+    upd.reserve(static_cast<size_t>(keyframes));
     if (!keeps_clouds()) return SCAL_OK;
     SCAL_TRY(arena.alloc(static_cast<size_t>(points)));
     SCAL_TRY(d_off.alloc(static_cast<size_t>(keyframes) + 1));
@@ -170,6 +234,19 @@ int KeyframeStore::init(int dev, int points, int keyframes) {
     SCAL_HIP(hipMemsetAsync(d_off.p, 0, sizeof(int), vstream));
     SCAL_HIP(hipMemsetAsync(d_overflow.p, 0, sizeof(int), vstream));
     SCAL_HIP(hipStreamSynchronize(vstream));
+    if (map_cap == 0) return SCAL_OK;
+    // pose-graph map: lane 2 - the pipeline's busy chains are on lanes 0, 1, 3 and 4, and on lane 5 the map would queue behind loop
+    // verifications
+    SCAL_TRY(mstream.acquire(dev, 2));
+    SCAL_TRY(mvf.init(map_cap));
+    mvf.set_tag(".M");
+    SCAL_TRY(d_xf.alloc(static_cast<size_t>(keyframes) + 1));
+    SCAL_TRY(h_xf.alloc(static_cast<size_t>(keyframes) + 1));
+    SCAL_TRY(d_parts.alloc(6 * PGO_MAX_BLOCKS));
+    for (DevBuf<float>* b : {&mx, &my, &mz, &mw, &fx, &fy, &fz, &fw}) SCAL_TRY(b->alloc(static_cast<size_t>(map_cap)));
+    SCAL_TRY(d_map.alloc(static_cast<size_t>(map_cap)));
+    SCAL_TRY(d_mn.alloc(2));
+    SCAL_TRY(h_mn.alloc(2));
     return SCAL_OK;
 }
 
@@ -216,6 +293,7 @@ int KeyframeStore::insert(scal_sc_t* sc, scal_features_t* feat, int db_index, co
     std::lock_guard<std::mutex> lk(mu);
     db_of_own.push_back(db_index);
     pose6.push_back({p6[0], p6[1], p6[2], p6[3], p6[4], p6[5]});
+    upd.emplace_back();
     return SCAL_OK;
 }
 
@@ -257,7 +335,8 @@ int KeyframeStore::verify(const KfLoopJob& job, double fitness_thres, scal_pipel
         j0 = static_cast<int>(std::lower_bound(db_of_own.begin(), db_of_own.end(), job.loop_kf - submap) - db_of_own.begin());
         j1 = static_cast<int>(std::upper_bound(db_of_own.begin(), db_of_own.end(), job.loop_kf + submap) - db_of_own.begin()) - 1;
         j1 = std::min(j1, checked - 1);
-        T = affine_f32(pose6[static_cast<size_t>(jl)].data());  // every keyframe is moved by the ROOT (loop) keyframe's pose (:506-507)
+        // every keyframe is moved by the ROOT (loop) keyframe's pose (:506-507): keyframePosesUpdated's, as it was when scan seq was pushed
+        T = affine_f32(pose_at(jl, job.seq).data());
     }
     const int n_src = h_off.p[jc + 1] - h_off.p[jc], n_tgt = h_off.p[j1 + 1] - h_off.p[j0];
     SCAL_HIP(hipSetDevice(device));
@@ -294,6 +373,118 @@ int KeyframeStore::verify(const KfLoopJob& job, double fitness_thres, scal_pipel
     out->verified = (r.converged && r.fitness <= fitness_thres) ? 1 : 0;  // :531
     relative_pose(r.T, out->q_rel, out->t_rel);
     return SCAL_OK;
+}
+
+const std::array<double, 6>& KeyframeStore::pose_at(int j, long long seq) const {
+    const std::vector<PoseVersion>& v = upd[static_cast<size_t>(j)];
+    for (size_t k = v.size(); k-- > 0;)
+        if (v[k].stamp <= seq) return v[k].p;
+    return pose6[static_cast<size_t>(j)];  // keyframePosesUpdated starts as keyframePoses (:636)
+}
+
+int KeyframeStore::update_poses(const int* db_index, const double* p6, int n, long long stamp, long long floor) {
+    std::lock_guard<std::mutex> lk(mu);
+    std::vector<int> js(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) {
+        auto it = std::lower_bound(db_of_own.begin(), db_of_own.end(), db_index[i]);
+        if (it == db_of_own.end() || *it != db_index[i]) {
+            set_error("scal_pipeline_update_keyframe_poses: %d is not a keyframe of this pipeline", db_index[i]);
+            return SCAL_E_ARG;
+        }
+        for (int k = 0; k < 6; ++k)
+            if (!std::isfinite(p6[6 * i + k])) {
+                set_error("scal_pipeline_update_keyframe_poses: the pose of keyframe %d is not finite", db_index[i]);
+                return SCAL_E_ARG;
+            }
+        js[static_cast<size_t>(i)] = static_cast<int>(it - db_of_own.begin());
+    }
+    for (int i = 0; i < n; ++i) {
+        std::vector<PoseVersion>& v = upd[static_cast<size_t>(js[static_cast<size_t>(i)])];
+        size_t keep = 0;  // the newest version that a loop of seq >= floor can still pick, and everything after it
+        while (keep + 1 < v.size() && v[keep + 1].stamp <= floor) ++keep;
+        v.erase(v.begin(), v.begin() + static_cast<std::ptrdiff_t>(keep));
+        std::array<double, 6> q;
+        std::memcpy(q.data(), p6 + 6 * i, sizeof(double) * 6);
+        if (!v.empty() && v.back().stamp == stamp)
+            v.back().p = q;  // no scan was pushed since the last update: the later one wins
+        else
+            v.push_back(PoseVersion{stamp, q});
+    }
+    return SCAL_OK;
+}
+
+int KeyframeStore::pgo_map(int kf_end, int skip, float leaf, float* out_xyzi, long long cap, long long* n_out) {
+    std::lock_guard<std::mutex> map_lk(map_mu);
+    *n_out = 0;
+    int n_sel = 0;
+    long long n = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        // only keyframes whose append stage D has confirmed (check() synchronised on it): kf_end must not reach past them
+        const int end_ok = checked > 0 ? db_of_own[static_cast<size_t>(checked - 1)] + 1 : 0;
+        if (kf_end > end_ok) {
+            set_error("scal_pipeline_pgo_map: kf_end %d is beyond the confirmed keyframes (%d)", kf_end, end_ok);
+            return SCAL_E_STATE;
+        }
+        const int j_end = static_cast<int>(std::lower_bound(db_of_own.begin(), db_of_own.end(), kf_end) - db_of_own.begin());
+        for (int j = 0; j < j_end; j += skip) n += h_off.p[j + 1] - h_off.p[j];
+        if (n > map_cap) {
+            *n_out = n;
+            set_error("scal_pipeline_pgo_map: the map needs %lld points, pgo_map_max_points is %d", n, map_cap);
+            return SCAL_E_CAPACITY;
+        }
+        int dst = 0;
+        for (int j = 0; j < j_end; j += skip, ++n_sel) {  // updatePoses' result as it stands now (:815-822 under mKF)
+            PgoXf& e = h_xf.p[n_sel];
+            const std::vector<PoseVersion>& v = upd[static_cast<size_t>(j)];
+            const Aff34 T = affine_f32(v.empty() ? pose6[static_cast<size_t>(j)].data() : v.back().p.data());
+            std::memcpy(e.m, T.m, sizeof e.m);
+            e.src = h_off.p[j], e.dst = dst;
+            dst += h_off.p[j + 1] - h_off.p[j];
+        }
+        h_xf.p[n_sel].src = 0, h_xf.p[n_sel].dst = dst;
+    }
+    SCAL_HIP(hipSetDevice(device));
+    hipStream_t s = mstream;
+    if (n == 0) {
+        map_n = 0;
+        return SCAL_OK;
+    }
+    // No event against stage D's appends: the gather reads only the arena ranges of confirmed keyframes, whose appends the host has
+    // already synchronised on (check()), and later appends write behind them.  The verification stream only reads the arena too.
+    const int ni = static_cast<int>(n);
+    SCAL_HIP(hipMemcpyAsync(d_xf.p, h_xf.p, sizeof(PgoXf) * (static_cast<size_t>(n_sel) + 1), hipMemcpyHostToDevice, s));
+    int grid = std::min(PGO_MAX_BLOCKS, div_up(ni, PGO_TILE));
+    const int chunk = div_up(div_up(ni, grid), PGO_TILE) * PGO_TILE;
+    grid = div_up(ni, chunk);  // every workgroup has points
+    SCAL_LAUNCH_PROF("k_pgo_gather", k_pgo_gather, dim3(grid), dim3(256), 0, s, arena.p, d_xf.p, n_sel, ni, chunk, mx.p, my.p, mz.p, mw.p, d_parts.p,
+                     d_mn.p);
+    SCAL_HIP(hipGetLastError());
+    SCAL_TRY(mvf.run(s, CSoA4{mx.p, my.p, mz.p, mw.p}, d_mn.p, ni, leaf, 45, SoA4{fx.p, fy.p, fz.p, fw.p}, d_mn.p + 1, nullptr, d_parts.p, grid));
+    launch_interleave(s, d_mn.p + 1, ni, CSoA4{fx.p, fy.p, fz.p, fw.p}, reinterpret_cast<float*>(d_map.p));
+    VoxMeta hm;
+    SCAL_HIP(hipMemcpyAsync(&hm, mvf.meta.p, sizeof hm, hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipMemcpyAsync(h_mn.p, d_mn.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipStreamSynchronize(s));
+    if (hm.error) {
+        map_n = -1;
+        set_error("scal_pipeline_pgo_map: voxel grid bounding box needs more than 45 key bits");
+        return SCAL_E_CAPACITY;
+    }
+    map_n = h_mn.p[0];
+    *n_out = map_n;
+    const long long m = std::min(map_n, cap);
+    if (m > 0) {  // on the map's stream: a copy on the null stream would wait for the pipeline's lanes
+        SCAL_HIP(hipMemcpyAsync(out_xyzi, d_map.p, sizeof(float4) * static_cast<size_t>(m), hipMemcpyDeviceToHost, s));
+        SCAL_HIP(hipStreamSynchronize(s));
+    }
+    return SCAL_OK;
+}
+
+const float* KeyframeStore::pgo_map_device(long long* n) {
+    std::lock_guard<std::mutex> lk(map_mu);
+    *n = map_n < 0 ? 0 : map_n;
+    return map_n < 0 ? nullptr : reinterpret_cast<const float*>(d_map.p);
 }
 
 int KeyframeStore::read(int db_index, double p6[6], float* xyzi, int cap, int* n) {

@@ -17,6 +17,20 @@ struct KfLoopJob {  // one detected loop handed from stage D to the verification
     double min_dist;
 };
 
+// one version of a keyframe's updated pose (keyframePosesUpdated, :408-431): made by the update call that ran while `stamp` scans had
+// been pushed, so it holds for the loops of scans seq >= stamp
+struct PoseVersion {
+    long long stamp;
+    std::array<double, 6> p;
+};
+
+// one selected keyframe of a pose-graph map (k_pgo_gather's table; entry n_sel holds only dst = the map's size)
+struct PgoXf {
+    float m[12];   // affine_f32 of its current pose
+    int src, dst;  // its first arena record, its first position in the map
+    int pad[2];
+};
+
 // The pose-graph node's keyframeLaserClouds / keyframePoses (:629-637): an AoS xyzi arena of `max_points` records with the per-keyframe
 // offsets on the device (off[j] .. off[j + 1] = the pipeline's keyframe j), the poses and the database index of every keyframe on the
 // host.  Stage D appends (one thread), the verification thread reads: the host metadata is guarded by `mu`.
@@ -32,6 +46,7 @@ struct KeyframeStore {
     std::vector<int> db_of_own;                // database index of the pipeline's keyframe j
     std::vector<std::array<double, 6>> pose6;  // its Pose6D (getOdom)
     int checked = 0;                           // keyframes whose append has been confirmed on the host
+    std::vector<std::vector<PoseVersion>> upd; // keyframe j's updated poses, oldest first (none: its gated pose holds)
     // verification (own stream, lane 5): submaps, their 0.4 m filter, ICP
     LaneStream vstream;
     VoxelFilter vf;
@@ -40,9 +55,23 @@ struct KeyframeStore {
     DevBuf<int> d_n;          // [0] submap size, [1] filtered size
     PinBuf<int> h_cnt;
     scal_icp_t* icp = nullptr;
+    // pose-graph map (pubMap, :810-834; pgo_map_max_points > 0): its own stream (lane 2, which scal_pipeline's layout leaves empty),
+    // filter and buffers; one map at a time (map_mu)
+    int map_cap = 0;
+    std::mutex map_mu;
+    LaneStream mstream;
+    VoxelFilter mvf;
+    DevBuf<PgoXf> d_xf;
+    PinBuf<PgoXf> h_xf;
+    DevBuf<unsigned> d_parts;     // per-workgroup bounding boxes of the gather, reduced by the filter's key kernel
+    DevBuf<float> mx, my, mz, mw, fx, fy, fz, fw;
+    DevBuf<float4> d_map;         // the last map, xyzi
+    DevBuf<int> d_mn;             // [0] points before the filter, [1] after
+    PinBuf<int> h_mn;
+    long long map_n = -1;         // points of the last map, -1 before the first
 
     ~KeyframeStore();
-    int init(int dev, int points, int keyframes);
+    int init(int dev, int points, int keyframes, int map_points);
     bool keeps_clouds() const { return max_points > 0; }
     // stage D: insert the keyframe into ScanContext and (clouds kept) append its 0.4 m cloud behind the descriptor
     int insert(scal_sc_t* sc, scal_features_t* feat, int db_index, const double p6[6]);
@@ -51,6 +80,12 @@ struct KeyframeStore {
     int own_count();
     int verify(const KfLoopJob& job, double fitness_thres, scal_pipeline_loop* out);
     int read(int db_index, double p6[6], float* xyzi, int cap, int* n);
+    // a new version of n keyframes' poses, stamped `stamp`; versions older than the newest one with stamp <= floor (the smallest seq a
+    // loop still to be verified can have) are dropped.  All or nothing.
+    int update_poses(const int* db_index, const double* p6, int n, long long stamp, long long floor);
+    int pgo_map(int kf_end, int skip, float leaf, float* out_xyzi, long long cap, long long* n_out);
+    const float* pgo_map_device(long long* n);
+    const std::array<double, 6>& pose_at(int j, long long seq) const;  // keyframe j's pose for the loop of scan seq; mu held
 };
 
 }  // namespace scal

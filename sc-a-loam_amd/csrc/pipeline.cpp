@@ -19,6 +19,8 @@
 // Nothing here touches the device except through the per-stage C-ABI, so the poses are those of the per-stage calls.
 #include "common.hpp"
 #include "keyframes.hpp"
+#include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <chrono>
@@ -107,6 +109,7 @@ struct scal_pipeline {
     std::deque<KfLoopJob> jobs;
     std::deque<scal_pipeline_loop> loops;
     bool verifying = false;
+    long long verifying_seq = 0;  // the job being verified (verifying)
     long long loops_owed = 0;  // detected and not popped
     std::thread t_verify;
 
@@ -460,7 +463,7 @@ void verify_thread(scal_pipeline* p) {
         if (p->stop || p->err) return;
         const KfLoopJob job = p->jobs.front();
         p->jobs.pop_front();
-        p->verifying = true;
+        p->verifying = true, p->verifying_seq = job.seq;
         lk.unlock();
         scal_pipeline_loop rec;
         const int st = p->kf->verify(job, p->fitness_thres, &rec);
@@ -551,6 +554,10 @@ int create(const scal_pipeline_config* cfg, int n_seqs, scal_pipeline_t** out) {
             return SCAL_E_ARG;
         }
     }
+    if (cfg->pgo_map_max_points < 0 || (cfg->pgo_map_max_points > 0 && (cfg->sc_mode != SCAL_PIPE_SC_KEYFRAME || cfg->kf_max_points == 0))) {
+        set_error("scal_pipeline_create: pgo_map_max_points must be >= 0, and > 0 only in sc_mode 3 with kf_max_points > 0");
+        return SCAL_E_ARG;
+    }
     SCAL_TRY(select_device(cfg->device));
     auto* p = new scal_pipeline();
     p->cfg = *cfg, p->ring = ring, p->depth = depth, p->S = n_seqs;
@@ -559,7 +566,7 @@ int create(const scal_pipeline_config* cfg, int n_seqs, scal_pipeline_t** out) {
     int rc = SCAL_OK;
     if (p->kf_mode()) {
         p->kf = new KeyframeStore();
-        rc = p->kf->init(cfg->device, cfg->kf_max_points, cfg->sc_max_keyframes);
+        rc = p->kf->init(cfg->device, cfg->kf_max_points, cfg->sc_max_keyframes, cfg->pgo_map_max_points);
     }
     scal_features_config fc{};
     fc.lidar_type = cfg->lidar_type, fc.n_scans = cfg->n_scans, fc.minimum_range = cfg->minimum_range, fc.max_points = cfg->max_points;
@@ -760,6 +767,55 @@ extern "C" int scal_pipeline_keyframe(scal_pipeline_t* p, int kf, double pose6[6
         return SCAL_E_STATE;
     }
     return p->kf->read(kf, pose6, xyzi, cap, n);
+}
+
+extern "C" int scal_pipeline_update_keyframe_poses(scal_pipeline_t* p, const int* kf, const double* pose6, int n) {
+    if (!p || n < 0 || (n > 0 && (!kf || !pose6))) {
+        set_error("scal_pipeline_update_keyframe_poses: bad argument");
+        return SCAL_E_ARG;
+    }
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (p->err) return report(p);
+    if (!p->kf_mode()) {
+        set_error("scal_pipeline_update_keyframe_poses: only in sc_mode 3");
+        return SCAL_E_STATE;
+    }
+    // Stamped with the push counter: the loops of scans pushed from now on see this version.  A loop still to be verified belongs to a
+    // queued job, the one being verified, or a scan stage D has not passed yet (seq >= d_coll).
+    long long floor = p->d_coll;
+    if (!p->jobs.empty()) floor = std::min(floor, p->jobs.front().seq);
+    if (p->verifying) floor = std::min(floor, p->verifying_seq);
+    return p->kf->update_poses(kf, pose6, n, p->pushed, floor);
+}
+
+static int pgo_map_state(scal_pipeline_t* p) {
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (p->err) return report(p);
+    if (!p->kf_mode() || p->cfg.pgo_map_max_points == 0) {
+        set_error("scal_pipeline_pgo_map: only in sc_mode 3 with pgo_map_max_points > 0");
+        return SCAL_E_STATE;
+    }
+    return SCAL_OK;
+}
+
+extern "C" int scal_pipeline_pgo_map(scal_pipeline_t* p, int kf_end, int skip, float leaf, float* out_xyzi, long long cap, long long* n_out) {
+    if (!p || !n_out || cap < 0 || (cap > 0 && !out_xyzi)) {
+        set_error("scal_pipeline_pgo_map: bad argument");
+        return SCAL_E_ARG;
+    }
+    *n_out = 0;
+    SCAL_TRY(pgo_map_state(p));
+    if (!(leaf > 0.f) || !std::isfinite(leaf) || skip < 1 || kf_end < 0) {
+        set_error("scal_pipeline_pgo_map: leaf must be finite and > 0, skip >= 1, kf_end >= 0");
+        return SCAL_E_ARG;
+    }
+    return p->kf->pgo_map(kf_end, skip, leaf, out_xyzi, cap, n_out);  // p->mu is not held: the map never waits for the stages
+}
+
+extern "C" const float* scal_pipeline_pgo_map_device(scal_pipeline_t* p, long long* n) {
+    if (n) *n = 0;
+    if (!p || !n || !p->kf_mode() || p->cfg.pgo_map_max_points == 0) return nullptr;
+    return p->kf->pgo_map_device(n);
 }
 
 extern "C" int scal_pipeline_in_flight(scal_pipeline_t* p) {

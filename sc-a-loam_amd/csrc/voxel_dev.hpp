@@ -64,18 +64,10 @@ namespace scal {
 // Bounding box without a launch of its own and without contended atomics: a kernel that reads a cloud anyway (a gather, the
 // curvature pass) lets every 256-thread block store the box of ITS points (order-preserving uint images: min xyz, max xyz) in
 // parts[block][6]; the filter's key kernel reduces the parts (VoxelFilter::run with ext_parts).  Every thread of the block calls
-// it, also in blocks without points (they store the identity); `have` = this thread holds a point.
-__device__ inline void vox_bbox_block_store(unsigned* parts, int block, bool have, float x, float y, float z) {
+// it, also in blocks without points (they store the identity).  This form takes the box of the thread's points (lo / hi:
+// order-preserving images, identity 0xffffffff / 0 for none); the one below a single point, `have` = this thread holds one.
+__device__ inline void vox_bbox_block_store(unsigned* parts, int block, unsigned lo[3], unsigned hi[3]) {
     __shared__ unsigned s_box[4][6];
-    unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-    if (have) {
-        const float v[3] = {x, y, z};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const unsigned u = __float_as_uint(v[a]);
-            lo[a] = hi[a] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-        }
-    }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
 #pragma unroll
@@ -90,6 +82,19 @@ __device__ inline void vox_bbox_block_store(unsigned* parts, int block, bool hav
         parts[block * 6 + threadIdx.x] = min(min(s_box[0][threadIdx.x], s_box[1][threadIdx.x]), min(s_box[2][threadIdx.x], s_box[3][threadIdx.x]));
     else if (threadIdx.x < 6)
         parts[block * 6 + threadIdx.x] = max(max(s_box[0][threadIdx.x], s_box[1][threadIdx.x]), max(s_box[2][threadIdx.x], s_box[3][threadIdx.x]));
+}
+__device__ __forceinline__ unsigned vox_ordered(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline void vox_bbox_block_store(unsigned* parts, int block, bool have, float x, float y, float z) {
+    unsigned lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    if (have) {
+        lo[0] = hi[0] = vox_ordered(x);
+        lo[1] = hi[1] = vox_ordered(y);
+        lo[2] = hi[2] = vox_ordered(z);
+    }
+    vox_bbox_block_store(parts, block, lo, hi);
 }
 #endif
 void launch_deinterleave(hipStream_t s, const float* aos, int n, SoA4 o);

@@ -93,7 +93,8 @@ class PipelineConfig(C.Structure):
                 ("float_math", C.c_int), ("check_finite", C.c_int), ("line_res", C.c_float), ("plane_res", C.c_float),
                 ("max_map_points", C.c_int), ("sc_max_radius", C.c_double), ("sc_dist_thres", C.c_double), ("sc_max_keyframes", C.c_int),
                 ("sc_mode", C.c_int), ("device", C.c_int), ("ring", C.c_int), ("depth", C.c_int), ("d_desc_ring", C.c_void_p),
-                ("keyframe_meter_gap", C.c_double), ("keyframe_deg_gap", C.c_double), ("kf_max_points", C.c_int), ("loop_fitness_thres", C.c_double)]
+                ("keyframe_meter_gap", C.c_double), ("keyframe_deg_gap", C.c_double), ("kf_max_points", C.c_int), ("loop_fitness_thres", C.c_double),
+                ("pgo_map_max_points", C.c_int)]
 
 
 class PipelineResult(C.Structure):
@@ -132,6 +133,7 @@ EXPORTED_SYMBOLS = [
     "scal_pipeline_in_flight", "scal_pipeline_sc", "scal_pipeline_map", "scal_pipeline_odom", "scal_pipeline_features",
     "scal_pipeline_create_multi", "scal_pipeline_seqs", "scal_pipeline_push_device_multi", "scal_pipeline_pop_multi", "scal_pipeline_sc_of", "scal_pipeline_map_of",
     "scal_pipeline_pop_loop", "scal_pipeline_keyframe", "scal_keyframe_gate_init", "scal_keyframe_gate",
+    "scal_pipeline_update_keyframe_poses", "scal_pipeline_pgo_map", "scal_pipeline_pgo_map_device",
 ]
 
 _lib = None
@@ -271,6 +273,10 @@ def lib():
     L.scal_pipeline_pop_multi.argtypes = [vp, C.POINTER(PipelineResult)]
     L.scal_pipeline_pop_loop.argtypes = [vp, C.POINTER(PipelineLoop), C.c_int]
     L.scal_pipeline_keyframe.argtypes = [vp, C.c_int, _f64p, _f32p, C.c_int, _i32p]
+    L.scal_pipeline_update_keyframe_poses.argtypes = [vp, _i32p, _f64p, C.c_int]
+    L.scal_pipeline_pgo_map.argtypes = [vp, C.c_int, C.c_int, C.c_float, _f32p, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.scal_pipeline_pgo_map_device.argtypes = [vp, C.POINTER(C.c_longlong)]
+    L.scal_pipeline_pgo_map_device.restype = C.c_void_p
     L.scal_keyframe_gate_init.argtypes = [C.POINTER(KeyframeGateState), C.c_double, C.c_double]
     L.scal_keyframe_gate.argtypes = [C.POINTER(KeyframeGateState), _f64p, _f64p, _i32p]
     for fn in ("scal_pipeline_sc_of", "scal_pipeline_map_of"):
@@ -906,13 +912,18 @@ class Pipeline:
 
     def __init__(self, lidar_type, minimum_range, max_points=400000, line_res=0.4, plane_res=0.8, max_map_points=4000000, sc_mode=SC_EVERY_SCAN,
                  sc_max_radius=80.0, sc_dist_thres=0.2, sc_max_keyframes=8192, device=0, ring=0, depth=0, float_math=0, check_finite=1, d_desc_ring=None,
-                 n_seqs=1, keyframe_meter_gap=0, keyframe_deg_gap=0, kf_max_points=0, loop_fitness_thres=0):
+                 n_seqs=1, keyframe_meter_gap=0, keyframe_deg_gap=0, kf_max_points=0, loop_fitness_thres=0, pgo_map_max_points=0):
         """sc_mode=SC_KEYFRAME: the pose-graph node's keyframe path - keyframe gate (0 = 2 m / 10 deg), keyframe clouds kept in a store of
-        kf_max_points points (0 = none, no loop is verified), loops verified by ICP (loop_fitness_thres 0 = 0.3): pop_loop(), keyframe()."""
+        kf_max_points points (0 = none, no loop is verified), loops verified by ICP (loop_fitness_thres 0 = 0.3): pop_loop(), keyframe();
+        the caller's optimized poses go in with update_keyframe_poses(), the pose-graph map of up to pgo_map_max_points points (before
+        its filter; 0 = no map) comes out of pgo_map()."""
         self.cfg = PipelineConfig(lidar_type, SCAN_LINES.get(lidar_type, 0), float(minimum_range), max_points, float_math, check_finite, line_res,
                                   plane_res, max_map_points, sc_max_radius, sc_dist_thres, sc_max_keyframes, sc_mode, device, ring, depth, d_desc_ring,
-                                  float(keyframe_meter_gap), float(keyframe_deg_gap), int(kf_max_points), float(loop_fitness_thres))
+                                  float(keyframe_meter_gap), float(keyframe_deg_gap), int(kf_max_points), float(loop_fitness_thres),
+                                  int(pgo_map_max_points))
         self.h = C.c_void_p()
+        self._kf_end = 0  # 1 + the largest keyframe_id popped so far
+        self._map_buf = np.zeros((0, 4), np.float32)
         self.n_seqs = n_seqs
         _check(lib().scal_pipeline_create_multi(C.byref(self.cfg), n_seqs, C.byref(self.h)))
         self.scs = [_borrow(SCManager, lib().scal_pipeline_sc_of(self.h, q)) if sc_mode != SC_OFF else None for q in range(n_seqs)]
@@ -943,6 +954,7 @@ class Pipeline:
     def pop(self):
         r = PipelineResult()
         _check(lib().scal_pipeline_pop(self.h, C.byref(r)))
+        self._kf_end = max(self._kf_end, r.keyframe_id + 1)
         return self._res(r)
 
     def push_device_multi(self, d_ptrs, ns, stride_floats=3):
@@ -979,6 +991,35 @@ class Pipeline:
         cloud = np.zeros((max(n.value, 1), 4), np.float32)
         _check(lib().scal_pipeline_keyframe(self.h, kf, pose.ctypes.data_as(_f64p), cloud.ctypes.data_as(_f32p), n.value, C.byref(n)))
         return pose, cloud[:n.value].copy()
+
+    def update_keyframe_poses(self, ids, poses6):
+        """sc_mode 3: the caller's optimized poses (x y z roll pitch yaw) of keyframes `ids` (database indices), as updatePoses writes
+        them into keyframePosesUpdated; loops of scans pushed from now on are verified with them"""
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+        P = _f64(np.asarray(poses6, np.float64).reshape(-1, 6))
+        if P.shape[0] != ids.shape[0]:
+            raise ValueError("one pose6 per keyframe id")
+        _check(lib().scal_pipeline_update_keyframe_poses(self.h, ids.ctypes.data_as(_i32p), P.ctypes.data_as(_f64p), ids.shape[0]))
+
+    def pgo_map(self, kf_end=None, skip=2, leaf=0.4):
+        """sc_mode 3: the pose-graph map (pubMap): every skip-th own keyframe with database index < kf_end (None: 1 + the largest
+        keyframe_id popped so far) moved by its current pose, concatenated and filtered at `leaf`; an (n, 4) float32 xyzi array"""
+        kf_end = self._kf_end if kf_end is None else int(kf_end)
+        n = C.c_longlong(0)
+        for _ in range(2):  # a map larger than the buffer: grow it and build the map again
+            buf = self._map_buf
+            _check(lib().scal_pipeline_pgo_map(self.h, kf_end, int(skip), float(leaf), buf.ctypes.data_as(_f32p) if buf.shape[0] else None,
+                                               buf.shape[0], C.byref(n)))
+            if n.value <= buf.shape[0]:
+                break
+            self._map_buf = np.zeros((n.value, 4), np.float32)
+        return self._map_buf[:n.value].copy()
+
+    def pgo_map_device(self):
+        """(device pointer, n) of the last map pgo_map built; (None, 0) before the first"""
+        n = C.c_longlong(0)
+        ptr = lib().scal_pipeline_pgo_map_device(self.h, C.byref(n))
+        return ptr, n.value
 
     def in_flight(self):
         return lib().scal_pipeline_in_flight(self.h)

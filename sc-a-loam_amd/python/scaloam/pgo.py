@@ -127,6 +127,14 @@ def local2global_f32(xyzi, pose6):
     return out
 
 
+def pgo_map_cloud(clouds, poses6, n_own, skip):
+    """pubMap's cloud before its VoxelGrid (:815-822): own keyframes 0, skip, 2 skip, ... below n_own (the keyframes with database index
+    < kf_end, counted from the pipeline's first own keyframe: n_own = kf_end - pre-filled entries), each moved by its pose with local2global's
+    f32 arithmetic, concatenated in keyframe order"""
+    parts = [local2global_f32(clouds[j], poses6[j]) for j in range(0, max(0, int(n_own)), int(skip))]
+    return np.concatenate(parts).astype(np.float32) if parts else np.zeros((0, 4), np.float32)
+
+
 def _quat_from_matrix(m):
     """Eigen::Quaterniond(Matrix3d) (gtsam Rot3::toQuaternion), (x, y, z, w)"""
     q = np.zeros(4)
