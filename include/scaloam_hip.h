@@ -567,6 +567,39 @@ int scal_pipeline_pgo_map(scal_pipeline_t* p, int kf_end, int skip, float leaf, 
 /* the last map scal_pipeline_pgo_map built: xyzi records in device memory, valid until the next call or destroy; NULL before the first */
 const float* scal_pipeline_pgo_map_device(scal_pipeline_t* p, long long* n);
 
+/* ---- sc_mode 3: the pose-graph optimisation itself (process_pg :644-690, process_icp :761-768, runISAM2opt :399-406, updatePoses
+ * :408-431) over the pipeline's own keyframes with database index < kf_end (nodes in their own order, node_idx) and the pipeline's
+ * accepted loops (verified == 1) whose curr_kf < kf_end - the pipeline keeps them itself, popped by the caller or not.  The graph is
+ * the one of scal_posegraph below: prior on node 0 at its gated pose (variances 1e-12, :286-288), odometry edges (k-1, k) = between of the
+ * GATED poses (variances 1e-6 x 3 rotation, 1e-4 x 3 translation, :292), one Cauchy(k = 1) loop edge (loop_kf, curr_kf) = (q_rel, t_rel)
+ * with variances 0.5 (:295-300) per accepted loop; no GPS factors (:673-681: the pipeline has no GPS input).  Initial estimate: every
+ * keyframe's current pose (its latest update, else its gated pose).  Deviation: the batch optimum over these factors, where the reference
+ * runs iSAM2 once a second (:791-808).
+ * The call waits until every keyframe < kf_end has passed stage D and every loop detected for one of them has been verified, so the
+ * graph - and, the solver being deterministic, the result bit for bit - does not depend on device timing, ring, depth, the caller's
+ * look-ahead or a drain.  It holds no stage's lock while it waits or solves and queues nothing on the pipeline's four busy streams: the
+ * solver runs on the pose-graph map's stream, one map or optimisation at a time.  Its context is created by the first call.
+ * Outputs: *res (may be NULL); the first min(n_nodes, cap) keyframe ids and poses (x y z roll pitch yaw with RzRyRx(roll, pitch, yaw) =
+ * the optimized rotation, as updatePoses reads them) - SCAL_E_CAPACITY with res->n_nodes set and nothing else done when cap < n_nodes
+ * (kf_ids / pose6 may be NULL with cap 0 to ask for the size that way).  apply = 1: the effect of
+ * scal_pipeline_update_keyframe_poses(kf_ids, pose6, n_nodes) at the moment the call returns; apply = 0 changes nothing.
+ * SCAL_E_STATE: sc_mode is not 3, or kf_end is beyond the keyframes whose append stage D has confirmed (as scal_pipeline_pgo_map).
+ * SCAL_E_ARG: kf_end < 0.  A solve that does not converge is not an error: res->solver.converged = 0, the poses are the last accepted ones. */
+typedef struct {
+    int iterations;           /* Gauss-Newton iterations (linear solves), accepted or not */
+    int converged;            /* 1: a step's max-norm fell below step_tol */
+    double initial_cost, final_cost;
+    int linear_iterations;    /* conjugate-gradient iterations over all solves */
+    int linear_status;        /* of the last solve: 0 converged, 1 hit max_linear_iterations, 2 breakdown (system not positive definite) */
+    double last_step_max;     /* max-norm of the last computed step [rad | m] */
+} scal_posegraph_stats;
+typedef struct {
+    int n_nodes, n_odom_edges, n_loop_edges, applied;
+    scal_posegraph_stats solver;
+} scal_pipeline_pgo_result;
+int scal_pipeline_optimize_keyframes(scal_pipeline_t* p, int kf_end, int apply, int* kf_ids /* [cap] */, double* pose6 /* [cap][6] */, int cap,
+                                     scal_pipeline_pgo_result* res);
+
 /* ---- the keyframe gate (:598-617 with getOdom :312-323 and diffTransformation :325-336), host only, no device needed.  The
  * accumulators start at 1e6 (:67-68), so the first pose is a keyframe; roll/pitch/yaw from tf's getRPY in double, the delta through
  * pcl::getTransformation / getTranslationAndEulerAngles in f32, the rotation summed naively. */
@@ -597,6 +630,48 @@ scal_map_t* scal_pipeline_map_of(scal_pipeline_t* p, int seq);
  * 1 LidarPlaneFactor(j, unit normal), 2 LidarPlaneNormFactor(n, d in pb[0]).  Arrays are [n][3] doubles. */
 int scal_factors_eval(int device, int n, const int* kind, const double* cp, const double* pa, const double* pb,
                       const double* x7 /* qx qy qz qw tx ty tz */, double* cost, double* gradient6, double* hessian6x6);
+
+/* ------------------------------------------------------------------ pose-graph optimisation (batch)
+ * What the pose-graph node asks of GTSAM (laserPosegraphOptimization.cpp: initNoises :284-310, the factors of process_pg :644-690 and
+ * process_icp :761-768, runISAM2opt :399-406), restated from the published algorithms - GTSAM / iSAM2 itself is third-party code and
+ * parity with it is unpinned, like the Ceres and PCL restatements.  Nodes are SE(3) poses (pose7 = qx qy qz qw tx ty tz, the layout of
+ * scal_factors_eval); one prior Log(P^-1 T) and between edges r = Log(Z^-1 Ti^-1 Tj), the full SE(3) logarithm in GTSAM's tangent order
+ * (rotation, then translation), whitened by 1 / sqrt(variance); an edge with cauchy_k > 0 has the cost k^2/2 log(1 + |e|^2/k^2) and is
+ * reweighted as gtsam::noiseModel::Robust does (w = k^2 / (k^2 + |e|^2), row block and right-hand side times sqrt(w)).  No GPS factors.
+ * Deviation: batch Gauss-Newton over all factors (the optimum iSAM2's estimate approaches), not incremental updates.  A step that would
+ * raise the cost is rejected and solved again with Levenberg damping.  Everything is f64 and stays in device memory; the normal
+ * equations are solved by conjugate gradients preconditioned with an exact parallel solve of their block-tridiagonal part (the odometry
+ * chain).  No float atomics: the result is bitwise reproducible.  scaloam.pgo.optimize_pose_graph is the CPU restatement it is held to. */
+typedef struct {
+    int device;
+    int max_nodes, max_edges;   /* capacities (between edges; the prior is extra) */
+} scal_posegraph_config;
+typedef struct {                /* 0 = default */
+    int max_iterations;         /* Gauss-Newton iterations, default 50 */
+    double step_tol;            /* stop when a step's max-norm is below this, default 1e-8 */
+    int max_linear_iterations;  /* conjugate-gradient iterations per solve, default 2000; a solve that hits it ends the optimisation */
+    double linear_rtol;         /* relative residual (in the preconditioner's norm) of a solve, default 1e-12 */
+} scal_posegraph_params;
+typedef struct scal_posegraph scal_posegraph_t;
+int scal_posegraph_create(const scal_posegraph_config* cfg, scal_posegraph_t** g);   /* SCAL_E_NO_DEVICE without a gfx950 device */
+void scal_posegraph_destroy(scal_posegraph_t* g);
+/* the estimate (quaternions are normalised); SCAL_E_ARG: n < 1, a pose that is not finite or has a zero quaternion; SCAL_E_CAPACITY: n > max_nodes */
+int scal_posegraph_set_nodes(scal_posegraph_t* g, const double* pose7 /* [n][7] */, int n);
+/* the one prior (a second call replaces it); SCAL_E_ARG: node outside the nodes set so far, pose not finite, a variance not finite and > 0 */
+int scal_posegraph_set_prior(scal_posegraph_t* g, int node, const double* pose7, const double* variances6);
+/* n more edges, all or nothing; SCAL_E_ARG: an index outside the nodes set so far, i == j, a pose not finite, a variance not finite and
+ * > 0, cauchy_k negative or not finite (cauchy_k NULL = none robust); SCAL_E_CAPACITY: more than max_edges in all */
+int scal_posegraph_add_between(scal_posegraph_t* g, int n, const int* i, const int* j, const double* pose7_rel /* [n][7] */,
+                               const double* variances6 /* [n][6] */, const double* cauchy_k /* [n] */);
+int scal_posegraph_clear_edges(scal_posegraph_t* g);   /* the between edges; nodes and prior stay */
+/* SCAL_E_STATE: no nodes, no prior, or an edge / the prior names a node beyond the current nodes.  A solve that does not converge is not
+ * an error (stats->converged = 0, the nodes are the last accepted estimate).  params and stats may be NULL. */
+int scal_posegraph_optimize(scal_posegraph_t* g, const scal_posegraph_params* params, scal_posegraph_stats* stats);
+int scal_posegraph_get_nodes(scal_posegraph_t* g, double* pose7 /* [n][7] */, int n);   /* SCAL_E_ARG unless n = the number of nodes */
+/* robust weights of the between edges at the current estimate, in the order they were added (1 for edges that are not robust): which
+ * loops were down-weighted.  SCAL_E_ARG unless n = the number of edges; SCAL_E_STATE before the first optimize on these edges. */
+int scal_posegraph_get_edge_weights(scal_posegraph_t* g, double* w /* [n] */, int n);
+
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,8 @@ int map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t** out
 int sc_create(const scal_sc_config* cfg, StreamLayout layout, scal_sc_t** out);
 // scal_icp_create on a given lane (scal_pipeline's loop verification keeps off the four busy lanes)
 int icp_create_on_lane(const scal_icp_config* cfg, int lane, scal_icp_t** out);
+// scal_posegraph_create on a given lane (scal_pipeline_optimize_keyframes solves on the pose-graph map's lane)
+int posegraph_create_on_lane(const scal_posegraph_config* cfg, int lane, scal_posegraph_t** out);
 // scal_sc_insert_features with a hook queued on the ScanContext stream behind the descriptor and before the next keyframe filter may
 // overwrite the 0.4 m filter output: after(stream, x, y, z, intensity, device count, capacity) (scal_pipeline's keyframe store)
 struct ScFilterOut {

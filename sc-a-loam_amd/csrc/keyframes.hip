@@ -481,6 +481,23 @@ int KeyframeStore::pgo_map(int kf_end, int skip, float leaf, float* out_xyzi, lo
     return SCAL_OK;
 }
 
+int KeyframeStore::pgo_snapshot(int kf_end, std::vector<int>* ids, std::vector<std::array<double, 6>>* gated, std::vector<std::array<double, 6>>* current) {
+    std::lock_guard<std::mutex> lk(mu);
+    // a store without clouds has no appends to confirm: its keyframes count once stage D has inserted them
+    const int conf = keeps_clouds() ? checked : static_cast<int>(db_of_own.size());
+    const int end_ok = conf > 0 ? db_of_own[static_cast<size_t>(conf - 1)] + 1 : 0;
+    if (kf_end > end_ok) {
+        set_error("scal_pipeline_optimize_keyframes: kf_end %d is beyond the confirmed keyframes (%d)", kf_end, end_ok);
+        return SCAL_E_STATE;
+    }
+    const size_t j_end = static_cast<size_t>(std::lower_bound(db_of_own.begin(), db_of_own.end(), kf_end) - db_of_own.begin());
+    ids->assign(db_of_own.begin(), db_of_own.begin() + static_cast<std::ptrdiff_t>(j_end));
+    gated->assign(pose6.begin(), pose6.begin() + static_cast<std::ptrdiff_t>(j_end));
+    current->resize(j_end);
+    for (size_t j = 0; j < j_end; ++j) (*current)[j] = upd[j].empty() ? pose6[j] : upd[j].back().p;
+    return SCAL_OK;
+}
+
 const float* KeyframeStore::pgo_map_device(long long* n) {
     std::lock_guard<std::mutex> lk(map_mu);
     *n = map_n < 0 ? 0 : map_n;

@@ -85,6 +85,9 @@ struct KeyframeStore {
     int update_poses(const int* db_index, const double* p6, int n, long long stamp, long long floor);
     int pgo_map(int kf_end, int skip, float leaf, float* out_xyzi, long long cap, long long* n_out);
     const float* pgo_map_device(long long* n);
+    // scal_pipeline_optimize_keyframes: the own keyframes with database index < kf_end - database index, gated pose and current pose (the
+    // latest update, else the gated one); SCAL_E_STATE by pgo_map's rule when kf_end is beyond the confirmed keyframes
+    int pgo_snapshot(int kf_end, std::vector<int>* ids, std::vector<std::array<double, 6>>* gated, std::vector<std::array<double, 6>>* current);
     const std::array<double, 6>& pose_at(int j, long long seq) const;  // keyframe j's pose for the loop of scan seq; mu held
 };
 

@@ -112,6 +112,16 @@ struct scal_pipeline {
     long long verifying_seq = 0;  // the job being verified (verifying)
     long long loops_owed = 0;  // detected and not popped
     std::thread t_verify;
+    // sc_mode 3, scal_pipeline_optimize_keyframes: the accepted loops in detection order (kept whether or not the caller pops them), how
+    // far stage D has got in keyframes, and the optimizer (created by the first call, used under the keyframe store's map_mu)
+    struct AcceptedLoop {
+        int curr_kf, loop_kf;
+        double q[4], t[3];
+    };
+    std::vector<AcceptedLoop> accepted;
+    int verifying_kf = -1;   // curr_kf of the job being verified (verifying)
+    int kf_passed_end = 0;   // database index + 1 of the newest own keyframe that has left stage D (its loop, if any, is in `jobs` or further)
+    scal_posegraph_t* pg = nullptr;
 
     bool sc_on() const { return cfg.sc_mode != SCAL_PIPE_SC_OFF; }
     bool side_sc() const { return cfg.sc_mode == SCAL_PIPE_SC_EVERY_SCAN || cfg.sc_mode == SCAL_PIPE_SC_DESCRIPTOR; }  // ScanContext behind stage A
@@ -450,6 +460,7 @@ void keyframe_thread(scal_pipeline* p) {
             p->jobs.push_back(KfLoopJob{k, R.keyframe_id, R.loop.loop_id, R.loop.yaw_rad, R.loop.min_dist});
             p->loops_owed++;
         }
+        if (is_kf) p->kf_passed_end = R.keyframe_id + 1;
         p->d_coll = k + 1;
         p->cv.notify_all();
     }
@@ -463,7 +474,7 @@ void verify_thread(scal_pipeline* p) {
         if (p->stop || p->err) return;
         const KfLoopJob job = p->jobs.front();
         p->jobs.pop_front();
-        p->verifying = true, p->verifying_seq = job.seq;
+        p->verifying = true, p->verifying_seq = job.seq, p->verifying_kf = job.curr_kf;
         lk.unlock();
         scal_pipeline_loop rec;
         const int st = p->kf->verify(job, p->fitness_thres, &rec);
@@ -474,6 +485,10 @@ void verify_thread(scal_pipeline* p) {
             return;
         }
         p->loops.push_back(rec);
+        if (rec.verified == 1) {
+            scal_pipeline::AcceptedLoop a{rec.curr_kf, rec.loop_kf, {rec.q_rel[0], rec.q_rel[1], rec.q_rel[2], rec.q_rel[3]}, {rec.t_rel[0], rec.t_rel[1], rec.t_rel[2]}};
+            p->accepted.push_back(a);
+        }
         p->cv.notify_all();
     }
 }
@@ -658,6 +673,7 @@ extern "C" void scal_pipeline_destroy(scal_pipeline_t* p) {
     }
     for (int q = 0; q < SMAX; ++q)
         for (auto* f : p->regs[q]) scal_features_destroy(f);
+    if (p->pg) scal_posegraph_destroy(p->pg);
     delete p->kf;  // after the ScanContext context, whose stream appended to it
     if (p->d_desc && p->own_desc) (void)hipFree(p->d_desc);
     delete p;
@@ -769,6 +785,8 @@ extern "C" int scal_pipeline_keyframe(scal_pipeline_t* p, int kf, double pose6[6
     return p->kf->read(kf, pose6, xyzi, cap, n);
 }
 
+static int update_poses_locked(scal_pipeline_t* p, const int* kf, const double* pose6, int n);
+
 extern "C" int scal_pipeline_update_keyframe_poses(scal_pipeline_t* p, const int* kf, const double* pose6, int n) {
     if (!p || n < 0 || (n > 0 && (!kf || !pose6))) {
         set_error("scal_pipeline_update_keyframe_poses: bad argument");
@@ -780,6 +798,10 @@ extern "C" int scal_pipeline_update_keyframe_poses(scal_pipeline_t* p, const int
         set_error("scal_pipeline_update_keyframe_poses: only in sc_mode 3");
         return SCAL_E_STATE;
     }
+    return update_poses_locked(p, kf, pose6, n);
+}
+
+static int update_poses_locked(scal_pipeline_t* p, const int* kf, const double* pose6, int n) {  // mu held
     // Stamped with the push counter: the loops of scans pushed from now on see this version.  A loop still to be verified belongs to a
     // queued job, the one being verified, or a scan stage D has not passed yet (seq >= d_coll).
     long long floor = p->d_coll;
@@ -816,6 +838,133 @@ extern "C" const float* scal_pipeline_pgo_map_device(scal_pipeline_t* p, long lo
     if (n) *n = 0;
     if (!p || !n || !p->kf_mode() || p->cfg.pgo_map_max_points == 0) return nullptr;
     return p->kf->pgo_map_device(n);
+}
+
+namespace {
+// Pose6DtoGTSAMPose3 (:193-196): Rot3::RzRyRx(roll, pitch, yaw) as a quaternion + translation -> pose7 (qx qy qz qw tx ty tz)
+void pose7_from6(const double* p6, double* p7) {
+    const double cr = std::cos(p6[3] / 2), sr = std::sin(p6[3] / 2), cp = std::cos(p6[4] / 2), sp = std::sin(p6[4] / 2);
+    const double cy = std::cos(p6[5] / 2), sy = std::sin(p6[5] / 2);
+    p7[0] = sr * cp * cy - cr * sp * sy, p7[1] = cr * sp * cy + sr * cp * sy, p7[2] = cr * cp * sy - sr * sp * cy, p7[3] = cr * cp * cy + sr * sp * sy;
+    p7[4] = p6[0], p7[5] = p6[1], p7[6] = p6[2];
+}
+// poseFrom.between(poseTo) (:664-671): a^-1 b
+void pose7_between(const double* a, const double* b, double* o) {
+    const double x = -a[0], y = -a[1], z = -a[2], w = a[3];  // a's rotation inverted
+    o[0] = w * b[0] + x * b[3] + y * b[2] - z * b[1];
+    o[1] = w * b[1] - x * b[2] + y * b[3] + z * b[0];
+    o[2] = w * b[2] + x * b[1] - y * b[0] + z * b[3];
+    o[3] = w * b[3] - x * b[0] - y * b[1] - z * b[2];
+    const double d[3] = {b[4] - a[4], b[5] - a[5], b[6] - a[6]};
+    const double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)},
+                            {2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)},
+                            {2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)}};
+    for (int r = 0; r < 3; ++r) o[4 + r] = (R[r][0] * d[0] + R[r][1] * d[1]) + R[r][2] * d[2];
+}
+}  // namespace
+
+extern "C" int scal_pipeline_optimize_keyframes(scal_pipeline_t* p, int kf_end, int apply, int* kf_ids, double* pose6, int cap, scal_pipeline_pgo_result* res) {
+    if (res) std::memset(res, 0, sizeof *res);
+    if (!p || cap < 0 || (cap > 0 && (!kf_ids || !pose6))) {
+        set_error("scal_pipeline_optimize_keyframes: bad argument");
+        return SCAL_E_ARG;
+    }
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->err) return report(p);
+        if (!p->kf_mode()) {
+            set_error("scal_pipeline_optimize_keyframes: only in sc_mode 3");
+            return SCAL_E_STATE;
+        }
+    }
+    if (kf_end < 0) {
+        set_error("scal_pipeline_optimize_keyframes: kf_end must be >= 0");
+        return SCAL_E_ARG;
+    }
+    std::vector<int> ids;
+    std::vector<std::array<double, 6>> gated, current;
+    SCAL_TRY(p->kf->pgo_snapshot(kf_end, &ids, &gated, &current));
+    const int n = static_cast<int>(ids.size());
+    if (res) res->n_nodes = n;
+    if (cap < n) {
+        set_error("scal_pipeline_optimize_keyframes: %d keyframes, room for %d", n, cap);
+        return SCAL_E_CAPACITY;
+    }
+    if (n == 0) return SCAL_OK;
+    // every keyframe of the graph has left stage D and every loop detected for one of them is verified: the graph no longer depends on timing
+    std::vector<scal_pipeline::AcceptedLoop> loops;
+    {
+        std::unique_lock<std::mutex> lk(p->mu);
+        const int need = ids.back() + 1;
+        auto pending = [&] {
+            if (p->verifying && p->verifying_kf < kf_end) return true;
+            for (const KfLoopJob& j : p->jobs)
+                if (j.curr_kf < kf_end) return true;
+            return false;
+        };
+        p->cv.wait(lk, [&] { return p->err || p->stop || (p->kf_passed_end >= need && !pending()); });
+        if (p->err) return report(p);
+        if (p->stop) {  // the pipeline is being destroyed under the call: the graph may be incomplete
+            set_error("scal_pipeline_optimize_keyframes: the pipeline is being destroyed");
+            return SCAL_E_STATE;
+        }
+        for (const auto& a : p->accepted)
+            if (a.curr_kf < kf_end) loops.push_back(a);
+    }
+    // Solved on the pose-graph map's lane (2), which carries none of the pipeline's four busy chains, under the map builder's mutex: a map
+    // and an optimisation would only queue behind each other on that stream, and the optimizer is one object.  p->mu is not held.
+    std::vector<double> x7(7 * static_cast<size_t>(n)), g7(7 * static_cast<size_t>(n));
+    scal_posegraph_stats st{};
+    {
+        std::lock_guard<std::mutex> map_lk(p->kf->map_mu);
+        // The poses as they stand now.  The node set is the one of the first snapshot: kf_end lies within the confirmed keyframes, and
+        // keyframes are only ever appended behind those, so the own keyframes below kf_end (and n) cannot change.
+        SCAL_TRY(p->kf->pgo_snapshot(kf_end, &ids, &gated, &current));
+        for (int k = 0; k < n; ++k) pose7_from6(gated[static_cast<size_t>(k)].data(), &g7[7 * static_cast<size_t>(k)]), pose7_from6(current[static_cast<size_t>(k)].data(), &x7[7 * static_cast<size_t>(k)]);
+        if (!p->pg) {
+            scal_posegraph_config pc{};
+            pc.device = p->cfg.device, pc.max_nodes = p->cfg.sc_max_keyframes, pc.max_edges = 2 * p->cfg.sc_max_keyframes;  // a chain + at most one loop per keyframe
+            SCAL_TRY(posegraph_create_on_lane(&pc, 2, &p->pg));
+        }
+        const double var_prior[6] = {1e-12, 1e-12, 1e-12, 1e-12, 1e-12, 1e-12};  // :286-288
+        const double var_odom[6] = {1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4};         // :292
+        const double var_loop[6] = {0.5, 0.5, 0.5, 0.5, 0.5, 0.5};               // :295
+        const size_t m = static_cast<size_t>(n - 1) + loops.size();
+        std::vector<int> ei(m), ej(m);
+        std::vector<double> ez(7 * m), ev(6 * m), ek(m);
+        for (int k = 1; k < n; ++k) {
+            const size_t e = static_cast<size_t>(k - 1);
+            ei[e] = k - 1, ej[e] = k, ek[e] = 0.0;
+            pose7_between(&g7[7 * e], &g7[7 * (e + 1)], &ez[7 * e]);
+            std::memcpy(&ev[6 * e], var_odom, sizeof var_odom);
+        }
+        size_t e = static_cast<size_t>(n - 1);
+        for (const auto& a : loops) {
+            const auto node = [&](int db) { return static_cast<int>(std::lower_bound(ids.begin(), ids.end(), db) - ids.begin()); };
+            ei[e] = node(a.loop_kf), ej[e] = node(a.curr_kf), ek[e] = 1.0;  // Cauchy(1), :297
+            std::memcpy(&ez[7 * e], a.q, sizeof a.q), std::memcpy(&ez[7 * e + 4], a.t, sizeof a.t);
+            std::memcpy(&ev[6 * e], var_loop, sizeof var_loop);
+            ++e;
+        }
+        SCAL_TRY(scal_posegraph_set_nodes(p->pg, x7.data(), n));
+        SCAL_TRY(scal_posegraph_clear_edges(p->pg));
+        SCAL_TRY(scal_posegraph_set_prior(p->pg, 0, g7.data(), var_prior));
+        SCAL_TRY(scal_posegraph_add_between(p->pg, static_cast<int>(m), ei.data(), ej.data(), ez.data(), ev.data(), ek.data()));
+        SCAL_TRY(scal_posegraph_optimize(p->pg, nullptr, &st));
+        SCAL_TRY(scal_posegraph_get_nodes(p->pg, x7.data(), n));
+    }
+    for (int k = 0; k < n; ++k) {
+        kf_ids[k] = ids[static_cast<size_t>(k)];
+        pose6_from(&x7[7 * static_cast<size_t>(k)], &x7[7 * static_cast<size_t>(k) + 4], pose6 + 6 * static_cast<size_t>(k));
+    }
+    if (res) res->n_odom_edges = n - 1, res->n_loop_edges = static_cast<int>(loops.size()), res->solver = st;
+    if (apply) {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->err) return report(p);
+        SCAL_TRY(update_poses_locked(p, kf_ids, pose6, n));
+        if (res) res->applied = 1;
+    }
+    return SCAL_OK;
 }
 
 extern "C" int scal_pipeline_in_flight(scal_pipeline_t* p) {

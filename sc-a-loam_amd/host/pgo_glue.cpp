@@ -1,6 +1,7 @@
-// The three places where alaserPGO (laserPosegraphOptimization.cpp) touches the hot path, as drop-in functions (source only, see
+// The places where alaserPGO (laserPosegraphOptimization.cpp) touches the hot path, as drop-in functions (source only, see
 // README.md).  Everything else of that node - queues, GTSAM factors and iSAM2 (:433-444, :646-690, :791-808), savers, rviz - stays
-// the reference's own code and keeps calling these at the cited lines.
+// the reference's own code and keeps calling these at the cited lines; optimize_poses at the end is the optional replacement of the
+// iSAM2 update by the library's batch optimizer.
 #include <cmath>
 #include <vector>
 #include <Eigen/Geometry>
@@ -62,6 +63,27 @@ inline bool verify_loop(scal_icp_t* icp, const float* src_xyzi, int n_src, const
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) (*T)(i, j) = static_cast<float>(r.T[4 * i + j]);
     return true;  // the caller turns T into the gtsam::Pose3 pair of :539-547
+}
+
+// ---- runISAM2opt + updatePoses (:399-431), optional: the batch optimum of the node's factors on the GPU instead of iSAM2.  The caller
+// keeps collecting its factors as it does for gtSAMgraph (:654 prior, :664-671 odometry, :765 loops) but as arrays: node indices, the
+// measured relative pose as qx qy qz qw tx ty tz and the noise variances (rotation first, as gtsam::Pose3), cauchy 1.0 for loop edges
+// and 0 for the others.  estimate: in = keyframePosesUpdated, out = the optimized poses (:414-428 turn each into x y z roll pitch yaw).
+struct PoseGraphEdges {
+    std::vector<int> i, j;
+    std::vector<double> pose7, variances6, cauchy;
+};
+inline bool optimize_poses(scal_posegraph_t* pg, std::vector<double>& estimate7, const double prior_pose7[7], const PoseGraphEdges& e) {
+    const int n = static_cast<int>(estimate7.size() / 7);
+    const double var_prior[6] = {1e-12, 1e-12, 1e-12, 1e-12, 1e-12, 1e-12};  // priorNoise (:286-288)
+    SCAL_CHECK(scal_posegraph_set_nodes(pg, estimate7.data(), n));
+    SCAL_CHECK(scal_posegraph_set_prior(pg, 0, prior_pose7, var_prior));
+    SCAL_CHECK(scal_posegraph_clear_edges(pg));
+    SCAL_CHECK(scal_posegraph_add_between(pg, static_cast<int>(e.i.size()), e.i.data(), e.j.data(), e.pose7.data(), e.variances6.data(), e.cauchy.data()));
+    scal_posegraph_stats st;
+    SCAL_CHECK(scal_posegraph_optimize(pg, nullptr, &st));
+    SCAL_CHECK(scal_posegraph_get_nodes(pg, estimate7.data(), n));
+    return st.converged != 0;  // not converged: the last accepted estimate, never worse than the one given
 }
 
 }  // namespace scal_pgo

@@ -109,6 +109,23 @@ class PipelineLoop(C.Structure):
                 ("T", C.c_double * 16), ("n_src", C.c_int), ("n_tgt", C.c_int), ("q_rel", C.c_double * 4), ("t_rel", C.c_double * 3)]
 
 
+class PoseGraphConfig(C.Structure):
+    _fields_ = [("device", C.c_int), ("max_nodes", C.c_int), ("max_edges", C.c_int)]
+
+
+class PoseGraphParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("step_tol", C.c_double), ("max_linear_iterations", C.c_int), ("linear_rtol", C.c_double)]
+
+
+class PoseGraphStats(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("linear_iterations", C.c_int), ("linear_status", C.c_int), ("last_step_max", C.c_double)]
+
+
+class PipelinePgoResult(C.Structure):
+    _fields_ = [("n_nodes", C.c_int), ("n_odom_edges", C.c_int), ("n_loop_edges", C.c_int), ("applied", C.c_int), ("solver", PoseGraphStats)]
+
+
 class KeyframeGateState(C.Structure):
     _fields_ = [("meter_gap", C.c_double), ("rad_gap", C.c_double), ("translation_accumulated", C.c_double),
                 ("rotation_accumulated", C.c_double), ("curr", C.c_double * 6)]
@@ -134,6 +151,8 @@ EXPORTED_SYMBOLS = [
     "scal_pipeline_create_multi", "scal_pipeline_seqs", "scal_pipeline_push_device_multi", "scal_pipeline_pop_multi", "scal_pipeline_sc_of", "scal_pipeline_map_of",
     "scal_pipeline_pop_loop", "scal_pipeline_keyframe", "scal_keyframe_gate_init", "scal_keyframe_gate",
     "scal_pipeline_update_keyframe_poses", "scal_pipeline_pgo_map", "scal_pipeline_pgo_map_device",
+    "scal_pipeline_optimize_keyframes", "scal_posegraph_create", "scal_posegraph_destroy", "scal_posegraph_set_nodes", "scal_posegraph_set_prior",
+    "scal_posegraph_add_between", "scal_posegraph_clear_edges", "scal_posegraph_optimize", "scal_posegraph_get_nodes", "scal_posegraph_get_edge_weights",
 ]
 
 _lib = None
@@ -277,6 +296,18 @@ def lib():
     L.scal_pipeline_pgo_map.argtypes = [vp, C.c_int, C.c_int, C.c_float, _f32p, C.c_longlong, C.POINTER(C.c_longlong)]
     L.scal_pipeline_pgo_map_device.argtypes = [vp, C.POINTER(C.c_longlong)]
     L.scal_pipeline_pgo_map_device.restype = C.c_void_p
+    if hasattr(L, "scal_posegraph_create"):  # absent from older builds compared through SCALOAM_LIB
+        L.scal_pipeline_optimize_keyframes.argtypes = [vp, C.c_int, C.c_int, _i32p, _f64p, C.c_int, C.POINTER(PipelinePgoResult)]
+        L.scal_posegraph_create.argtypes = [C.POINTER(PoseGraphConfig), C.POINTER(vp)]
+        L.scal_posegraph_destroy.argtypes = [vp]
+        L.scal_posegraph_destroy.restype = None
+        L.scal_posegraph_set_nodes.argtypes = [vp, _f64p, C.c_int]
+        L.scal_posegraph_set_prior.argtypes = [vp, C.c_int, _f64p, _f64p]
+        L.scal_posegraph_add_between.argtypes = [vp, C.c_int, _i32p, _i32p, _f64p, _f64p, _f64p]
+        L.scal_posegraph_clear_edges.argtypes = [vp]
+        L.scal_posegraph_optimize.argtypes = [vp, C.POINTER(PoseGraphParams), C.POINTER(PoseGraphStats)]
+        L.scal_posegraph_get_nodes.argtypes = [vp, _f64p, C.c_int]
+        L.scal_posegraph_get_edge_weights.argtypes = [vp, _f64p, C.c_int]
     L.scal_keyframe_gate_init.argtypes = [C.POINTER(KeyframeGateState), C.c_double, C.c_double]
     L.scal_keyframe_gate.argtypes = [C.POINTER(KeyframeGateState), _f64p, _f64p, _i32p]
     for fn in ("scal_pipeline_sc_of", "scal_pipeline_map_of"):
@@ -879,6 +910,75 @@ def factors_eval(kind, cp, pa, pb, x7, device=0):
     return cost[0], g, H
 
 
+def _pg_stats(s):
+    return dict(iterations=s.iterations, converged=s.converged, initial_cost=s.initial_cost, final_cost=s.final_cost,
+                linear_iterations=s.linear_iterations, linear_status=s.linear_status, last_step_max=s.last_step_max)
+
+
+class PoseGraph:
+    """scal_posegraph: batch pose-graph optimisation on the GPU (one prior, between edges, Cauchy-robust where cauchy_k > 0); poses are
+    pose7 rows qx qy qz qw tx ty tz.  scaloam.pgo.optimize_pose_graph is its CPU restatement."""
+
+    def __init__(self, max_nodes, max_edges, device=0):
+        self.h = C.c_void_p()
+        cfg = PoseGraphConfig(device, int(max_nodes), int(max_edges))
+        _check(lib().scal_posegraph_create(C.byref(cfg), C.byref(self.h)))
+        self.n_nodes, self.n_edges = 0, 0
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.scal_posegraph_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def set_nodes(self, pose7):
+        P = _f64(np.asarray(pose7, np.float64).reshape(-1, 7))
+        _check(lib().scal_posegraph_set_nodes(self.h, _p(P, _f64p), P.shape[0]))
+        self.n_nodes = P.shape[0]
+
+    def set_prior(self, node, pose7, variances6):
+        P, V = _f64(np.asarray(pose7, np.float64).reshape(7)), _f64(np.asarray(variances6, np.float64).reshape(6))
+        _check(lib().scal_posegraph_set_prior(self.h, int(node), _p(P, _f64p), _p(V, _f64p)))
+
+    def add_between(self, i, j, pose7_rel, variances6, cauchy_k=None):
+        i = np.ascontiguousarray(np.asarray(i, np.int32).reshape(-1))
+        j = np.ascontiguousarray(np.asarray(j, np.int32).reshape(-1))
+        m = i.shape[0]
+        Z = _f64(np.asarray(pose7_rel, np.float64).reshape(-1, 7))
+        V = _f64(np.broadcast_to(np.asarray(variances6, np.float64), (m, 6)))
+        K = None if cauchy_k is None else _f64(np.broadcast_to(np.asarray(cauchy_k, np.float64), (m,)))
+        if j.shape[0] != m or Z.shape[0] != m:
+            raise ValueError("one j and one pose7 per edge")
+        _check(lib().scal_posegraph_add_between(self.h, m, _p(i, _i32p), _p(j, _i32p), _p(Z, _f64p), _p(V, _f64p), _p(K, _f64p)))
+        self.n_edges += m
+
+    def add_edges(self, edges):
+        """edges as scaloam.pgo.make_edges builds them"""
+        self.add_between(edges["i"], edges["j"], edges["z"], edges["var"], edges["k"])
+
+    def clear_edges(self):
+        _check(lib().scal_posegraph_clear_edges(self.h))
+        self.n_edges = 0
+
+    def optimize(self, max_iterations=0, step_tol=0.0, max_linear_iterations=0, linear_rtol=0.0):
+        """0 = the library's default; returns the statistics as a dict"""
+        prm = PoseGraphParams(int(max_iterations), float(step_tol), int(max_linear_iterations), float(linear_rtol))
+        st = PoseGraphStats()
+        _check(lib().scal_posegraph_optimize(self.h, C.byref(prm), C.byref(st)))
+        return _pg_stats(st)
+
+    def nodes(self):
+        out = np.zeros((self.n_nodes, 7))
+        _check(lib().scal_posegraph_get_nodes(self.h, _p(out, _f64p), self.n_nodes))
+        return out
+
+    def edge_weights(self):
+        out = np.zeros(max(self.n_edges, 1))
+        _check(lib().scal_posegraph_get_edge_weights(self.h, _p(out, _f64p), self.n_edges))
+        return out[:self.n_edges]
+
+
 # ---------------------------------------------------------------------------------------------- the four stages as one object
 SC_OFF, SC_EVERY_SCAN, SC_DESCRIPTOR, SC_KEYFRAME = 0, 1, 2, 3
 
@@ -1014,6 +1114,19 @@ class Pipeline:
                 break
             self._map_buf = np.zeros((n.value, 4), np.float32)
         return self._map_buf[:n.value].copy()
+
+    def optimize_keyframes(self, kf_end=None, apply=True):
+        """sc_mode 3: optimise the pose graph of the own keyframes with database index < kf_end (None: 1 + the largest keyframe_id popped
+        so far) and the accepted loops among them on the GPU; apply=True also does update_keyframe_poses(ids, poses6).  Returns ids,
+        poses6 (x y z roll pitch yaw), stats (n_nodes, n_odom_edges, n_loop_edges, applied + the solver's statistics)"""
+        kf_end = self._kf_end if kf_end is None else int(kf_end)
+        cap = max(int(self.cfg.sc_max_keyframes), 1)
+        ids, P = np.zeros(cap, np.int32), np.zeros((cap, 6))
+        res = PipelinePgoResult()
+        _check(lib().scal_pipeline_optimize_keyframes(self.h, kf_end, 1 if apply else 0, _p(ids, _i32p), _p(P, _f64p), cap, C.byref(res)))
+        st = dict(n_nodes=res.n_nodes, n_odom_edges=res.n_odom_edges, n_loop_edges=res.n_loop_edges, applied=res.applied)
+        st.update(_pg_stats(res.solver))
+        return ids[:res.n_nodes].copy(), P[:res.n_nodes].copy(), st
 
     def pgo_map_device(self):
         """(device pointer, n) of the last map pgo_map built; (None, 0) before the first"""

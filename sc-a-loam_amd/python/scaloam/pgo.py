@@ -1,6 +1,7 @@
 """Host-side glue of the pose-graph node around the hot path (laserPosegraphOptimization.cpp): the keyframe gate in front of the
 ScanContext insert (:598-617, with getOdom :312-323 and diffTransformation :325-336) and the g2o text of the saved pose graph
-(:147-175, :198-216).  No GPU work here; GTSAM / iSAM2 itself stays with the caller (out of scope)."""
+(:147-175, :198-216), and - further down - the CPU restatement of the pose graph and its batch optimisation that csrc/posegraph.hip is
+held to.  No GPU work here; GTSAM / iSAM2 itself is third-party code and is restated, not reproduced."""
 import numpy as np
 
 
@@ -175,3 +176,358 @@ def relative_pose_from_icp(T):
     Rt = R.T
     t = -(Rt @ np.array([float(x), float(y), float(z)]))
     return _quat_from_matrix(Rt), t
+
+
+# ------------------------------------------------------------------------------------------------ pose-graph optimisation
+# CPU restatement of the pose graph the node builds (initNoises :284-310, process_pg :644-690, process_icp :761-768) and of a batch
+# Gauss-Newton optimiser over it: the yardstick of csrc/posegraph.hip.  Poses are pose7 rows (qx qy qz qw tx ty tz, the layout
+# scal_factors_eval uses); tangent vectors are [omega, v] (rotation first, as GTSAM's Pose3); Exp / Log are the full SE(3) maps.
+# Parity with GTSAM is unpinned: which Pose3 chart the reference's build used cannot be found out.
+SERIES_THETA = 0.1     # below: the coefficient functions of Exp / Log / Jr^-1 by their series (4 terms, error < 1e-15 relative)
+SERIES_SINE = 1e-4     # below (|vector part| of the quaternion): atan by its series in the rotation logarithm
+PG_DEFAULTS = dict(max_iterations=50, step_tol=1e-8, lambda_first=1e-4, lambda_factor=10.0, lambda_max=1e8)
+PRIOR_VARIANCES = (1e-12,) * 6                              # :286-288
+ODOM_VARIANCES = (1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4)       # :292
+LOOP_VARIANCES = (0.5,) * 6                                 # :295
+LOOP_CAUCHY_K = 1.0                                         # :297
+
+
+def _hat(w):
+    w = np.asarray(w, np.float64)
+    H = np.zeros(w.shape[:-1] + (3, 3))
+    H[..., 0, 1], H[..., 0, 2], H[..., 1, 0] = -w[..., 2], w[..., 1], w[..., 2]
+    H[..., 1, 2], H[..., 2, 0], H[..., 2, 1] = -w[..., 0], -w[..., 1], w[..., 0]
+    return H
+
+
+def _qmul(a, b):
+    ax, ay, az, aw = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    bx, by, bz, bw = b[..., 0], b[..., 1], b[..., 2], b[..., 3]
+    return np.stack([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
+                     aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz], -1)
+
+
+def _qconj(q):
+    return q * np.array([-1.0, -1.0, -1.0, 1.0])
+
+
+def _qmat(q):
+    x, y, z, w = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    R = np.empty(q.shape[:-1] + (3, 3))
+    R[..., 0, 0], R[..., 0, 1], R[..., 0, 2] = 1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)
+    R[..., 1, 0], R[..., 1, 1], R[..., 1, 2] = 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)
+    R[..., 2, 0], R[..., 2, 1], R[..., 2, 2] = 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)
+    return R
+
+
+def _coeffs(th2):
+    """the coefficient functions of theta (given theta^2): a = (1 - cos)/t^2, b = (t - sin)/t^3, c = (1 - (t/2) cot(t/2))/t^2,
+    c2 = (t^2 + 2 cos - 2)/(2 t^4), c3 = (2 t - 3 sin + t cos)/(2 t^5); series below SERIES_THETA"""
+    th2 = np.asarray(th2, np.float64)
+    small = th2 < SERIES_THETA * SERIES_THETA
+    t2 = np.where(small, 1.0, th2)
+    t = np.sqrt(t2)
+    s, co = np.sin(t), np.cos(t)
+    a = (1 - co) / t2
+    b = (t - s) / (t2 * t)
+    c = (1 - 0.5 * t * np.cos(0.5 * t) / np.sin(0.5 * t)) / t2
+    c2 = (t2 + 2 * co - 2) / (2 * t2 * t2)
+    c3 = (2 * t - 3 * s + t * co) / (2 * t2 * t2 * t)
+    x = np.where(small, th2, 0.0)
+    a = np.where(small, 1 / 2 + x * (-1 / 24 + x * (1 / 720 - x / 40320)), a)
+    b = np.where(small, 1 / 6 + x * (-1 / 120 + x * (1 / 5040 - x / 362880)), b)
+    c = np.where(small, 1 / 12 + x * (1 / 720 + x * (1 / 30240 + x / 1209600)), c)
+    c2 = np.where(small, 1 / 24 + x * (-1 / 720 + x * (1 / 40320 - x / 3628800)), c2)
+    c3 = np.where(small, 1 / 120 + x * (-1 / 2520 + x * (1 / 120960 - x / 9979200)), c3)
+    return a, b, c, c2, c3
+
+
+def se3_exp(xi):
+    """Exp of [omega, v] (shape (..., 6)) -> pose7: q = (sin(t/2)/t omega, cos(t/2)), t = V(omega) v, V = I + a W + b W^2"""
+    xi = np.asarray(xi, np.float64)
+    w, v = xi[..., :3], xi[..., 3:]
+    th2 = np.sum(w * w, -1)
+    a, b, _, _, _ = _coeffs(th2)
+    small = th2 < SERIES_THETA * SERIES_THETA
+    t = np.sqrt(np.where(small, 1.0, th2))
+    x = np.where(small, th2, 0.0)
+    sh = np.where(small, 1 / 2 + x * (-1 / 48 + x * (1 / 3840 - x / 645120)), np.sin(0.5 * t) / t)
+    ch = np.where(small, 1 + x * (-1 / 8 + x * (1 / 384 - x / 46080)), np.cos(0.5 * t))
+    wv = np.cross(w, v)
+    wwv = np.cross(w, wv)
+    tr = v + a[..., None] * wv + b[..., None] * wwv
+    return np.concatenate([sh[..., None] * w, ch[..., None], tr], -1)
+
+
+def _rot_log(q):
+    """rotation vector of a unit quaternion (x y z w), angle in [0, pi]"""
+    q = np.where(q[..., 3:4] < 0, -q, q)
+    v, w = q[..., :3], q[..., 3]
+    s2 = np.sum(v * v, -1)
+    small = s2 < SERIES_SINE * SERIES_SINE
+    s = np.sqrt(np.where(small, 1.0, s2))
+    k = 2 * np.arctan2(s, w) / s
+    x = np.where(small, s2 / (w * w), 0.0)
+    k = np.where(small, 2 / w * (1 + x * (-1 / 3 + x / 5)), k)
+    return k[..., None] * v
+
+
+def se3_log(p):
+    """Log of pose7 -> [omega, v]: v = V^-1 t, V^-1 = I - W/2 + c W^2"""
+    p = np.asarray(p, np.float64)
+    w = _rot_log(p[..., :4])
+    t = p[..., 4:]
+    _, _, c, _, _ = _coeffs(np.sum(w * w, -1))
+    wt = np.cross(w, t)
+    return np.concatenate([w, t - 0.5 * wt + c[..., None] * np.cross(w, wt)], -1)
+
+
+def se3_compose(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    q = _qmul(a[..., :4], b[..., :4])
+    t = a[..., 4:] + np.einsum("...rc,...c->...r", _qmat(a[..., :4]), b[..., 4:])
+    return np.concatenate([q, t], -1)
+
+
+def se3_inverse(a):
+    a = np.asarray(a, np.float64)
+    qi = _qconj(a[..., :4])
+    return np.concatenate([qi, -np.einsum("...cr,...c->...r", _qmat(a[..., :4]), a[..., 4:])], -1)
+
+
+def se3_between(a, b):
+    """a^-1 b (gtsam Pose3::between)"""
+    return se3_compose(se3_inverse(a), b)
+
+
+def se3_adjoint(p):
+    """Ad(T) for [omega, v]: [[R, 0], [t^ R, R]]"""
+    p = np.asarray(p, np.float64)
+    R = _qmat(p[..., :4])
+    A = np.zeros(p.shape[:-1] + (6, 6))
+    A[..., :3, :3] = R
+    A[..., 3:, 3:] = R
+    A[..., 3:, :3] = _hat(p[..., 4:]) @ R
+    return A
+
+
+def se3_right_jacobian_inverse(xi):
+    """Jr^-1(xi) = Jl^-1(-xi), Jl^-1 = [[J, 0], [-J Q J, J]] with J = I - W/2 + c W^2 and Q as in Barfoot, State Estimation for
+    Robotics, eq. 7.86 (phi = omega, rho = v)"""
+    xi = -np.asarray(xi, np.float64)
+    w, v = xi[..., :3], xi[..., 3:]
+    _, b, c, c2, c3 = _coeffs(np.sum(w * w, -1))
+    W, V = _hat(w), _hat(v)
+    I = np.eye(3)
+    J = I - 0.5 * W + c[..., None, None] * (W @ W)
+    WV, VW = W @ V, V @ W
+    WVW = WV @ W
+    Q = (0.5 * V + b[..., None, None] * (WV + VW + WVW) + c2[..., None, None] * (W @ WV + VW @ W - 3 * WVW)
+         + c3[..., None, None] * (WVW @ W + W @ WVW))
+    out = np.zeros(xi.shape[:-1] + (6, 6))
+    out[..., :3, :3] = J
+    out[..., 3:, 3:] = J
+    out[..., 3:, :3] = -(J @ Q @ J)
+    return out
+
+
+def between_residual(Ti, Tj, Z, jacobians=False):
+    """r = Log(Z^-1 Ti^-1 Tj); with jacobians the derivatives for right perturbations T <- T Exp(d): dr/ddj = Jr^-1(r),
+    dr/ddi = -Jr^-1(r) Ad((Ti^-1 Tj)^-1)"""
+    rel = se3_between(Ti, Tj)
+    r = se3_log(se3_between(Z, rel))
+    if not jacobians:
+        return r
+    Jj = se3_right_jacobian_inverse(r)
+    Ji = -(Jj @ se3_adjoint(se3_inverse(rel)))
+    return r, Ji, Jj
+
+
+def prior_residual(T, P, jacobians=False):
+    """r = Log(P^-1 T), dr/dd = Jr^-1(r)"""
+    r = se3_log(se3_between(P, T))
+    return (r, se3_right_jacobian_inverse(r)) if jacobians else r
+
+
+def se3_retract(T, d):
+    p = se3_compose(T, se3_exp(d))
+    p[..., :4] /= np.linalg.norm(p[..., :4], axis=-1, keepdims=True)
+    return p
+
+
+def pose7_from_pose6(p6):
+    """x y z roll pitch yaw (Pose6D) -> pose7, Pose6DtoGTSAMPose3 (:193-196)"""
+    p6 = np.asarray(p6, np.float64).reshape(-1, 6)
+    return np.array([list(quat_from_rpy(p[3], p[4], p[5])) + [p[0], p[1], p[2]] for p in p6]).reshape(-1, 7)
+
+
+def pose6_from_pose7(p7):
+    """pose7 -> x y z roll pitch yaw with RzRyRx(roll, pitch, yaw) = the rotation (updatePoses, :408-431)"""
+    p7 = np.asarray(p7, np.float64).reshape(-1, 7)
+    return np.array([[p[4], p[5], p[6]] + list(rpy_from_quat(p[:4])) for p in p7]).reshape(-1, 6)
+
+
+def make_edges(i, j, z, variances, cauchy_k):
+    """between edges as the arrays scal_posegraph_add_between takes; cauchy_k 0 = not robust"""
+    i = np.asarray(i, np.int32).reshape(-1)
+    m = len(i)
+    return dict(i=i, j=np.asarray(j, np.int32).reshape(-1), z=np.asarray(z, np.float64).reshape(m, 7),
+                var=np.broadcast_to(np.asarray(variances, np.float64), (m, 6)).copy(),
+                k=np.broadcast_to(np.asarray(cauchy_k, np.float64), (m,)).copy())
+
+
+def concat_edges(a, b):
+    return {key: np.concatenate([a[key], b[key]]) for key in ("i", "j", "z", "var", "k")}
+
+
+def whitened_residuals(poses, prior, edges, jacobians=False):
+    """e = r / sigma for the prior (first) and every edge, the robust weights w = k^2 / (k^2 + |e|^2) (1 where k = 0) and the cost
+    sum(|e|^2 / 2) over the plain rows + sum(k^2 / 2 log(1 + |e|^2 / k^2)) over the robust ones"""
+    poses = np.asarray(poses, np.float64)
+    sp = 1.0 / np.sqrt(np.asarray(prior["var"], np.float64))
+    se = 1.0 / np.sqrt(edges["var"])
+    Ti, Tj = poses[edges["i"]], poses[edges["j"]]
+    if jacobians:
+        rp, Jp = prior_residual(poses[prior["node"]], np.asarray(prior["pose7"], np.float64), True)
+        r, Ji, Jj = between_residual(Ti, Tj, edges["z"], True)
+    else:
+        rp = prior_residual(poses[prior["node"]], np.asarray(prior["pose7"], np.float64))
+        r = between_residual(Ti, Tj, edges["z"])
+    ep, e = rp * sp, r * se
+    e2 = np.sum(e * e, -1)
+    k2 = edges["k"] * edges["k"]
+    robust = k2 > 0
+    k2s = np.where(robust, k2, 1.0)
+    w = np.where(robust, k2s / (k2s + e2), 1.0)
+    cost = 0.5 * float(ep @ ep) + float(np.sum(np.where(robust, 0.5 * k2s * np.log1p(e2 / k2s), 0.5 * e2)))
+    if not jacobians:
+        return ep, e, w, cost
+    return ep, e, w, cost, Jp * sp[:, None], Ji * se[:, :, None], Jj * se[:, :, None]
+
+
+def optimize_pose_graph(poses, prior, edges, params=None):
+    """Batch Gauss-Newton over the graph, robust rows reweighted as gtsam's noiseModel::Robust does (row block and right-hand side
+    times sqrt(w), no second-order term); exact sparse solve of the normal equations.  A step that raises the cost is rejected and
+    solved again with Levenberg damping lambda diag(H) (lambda_first, then times lambda_factor); damping is dropped after an accepted
+    step.  Stops (converged) when a step's max-norm is below step_tol.  Returns poses, stats(costs per iteration starting with the
+    initial one, step_norms, weights at the returned estimate, iterations, converged)."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spl
+    P = dict(PG_DEFAULTS)
+    P.update(params or {})
+    x = np.array(poses, np.float64).reshape(-1, 7)
+    n, m = len(x), len(edges["i"])
+    _, _, _, cost = whitened_residuals(x, prior, edges)
+    costs, steps = [cost], []
+    converged, lam, it = 0, 0.0, 0
+    ar6 = np.arange(6)
+    rows_e = (6 * np.arange(m)[:, None, None] + ar6[None, :, None] + 6) + np.zeros((1, 1, 6), np.int64)
+    cols_i = 6 * edges["i"].astype(np.int64)[:, None, None] + ar6[None, None, :] + np.zeros((1, 6, 1), np.int64)
+    cols_j = 6 * edges["j"].astype(np.int64)[:, None, None] + ar6[None, None, :] + np.zeros((1, 6, 1), np.int64)
+    rows_p = ar6[:, None] + np.zeros((1, 6), np.int64)
+    cols_p = 6 * int(prior["node"]) + ar6[None, :] + np.zeros((6, 1), np.int64)
+    while it < P["max_iterations"]:
+        ep, e, w, cost, Jp, Ji, Jj = whitened_residuals(x, prior, edges, True)
+        sw = np.sqrt(w)
+        b = np.concatenate([ep, (e * sw[:, None]).reshape(-1)])
+        J = sp.csr_matrix((np.concatenate([Jp.reshape(-1), (Ji * sw[:, None, None]).reshape(-1), (Jj * sw[:, None, None]).reshape(-1)]),
+                           (np.concatenate([rows_p.reshape(-1), rows_e.reshape(-1), rows_e.reshape(-1)]),
+                            np.concatenate([cols_p.reshape(-1), cols_i.reshape(-1), cols_j.reshape(-1)]))), shape=(6 * m + 6, 6 * n))
+        H = (J.T @ J).tocsc()
+        g = J.T @ b
+        while True:
+            it += 1
+            A = H if lam == 0 else (H + lam * sp.diags(H.diagonal())).tocsc()
+            d = spl.splu(A).solve(-g).reshape(n, 6)
+            step = float(np.abs(d).max()) if n else 0.0
+            xn = se3_retract(x, d)
+            _, _, _, cn = whitened_residuals(xn, prior, edges)
+            ok = np.isfinite(cn) and cn <= cost
+            if ok:
+                x, lam = xn, 0.0
+                costs.append(cn)
+                steps.append(step)
+            else:
+                lam = P["lambda_first"] if lam == 0 else lam * P["lambda_factor"]
+            if step < P["step_tol"]:
+                converged = 1
+            if ok or converged or it >= P["max_iterations"] or lam > P["lambda_max"]:
+                break
+        if converged or lam > P["lambda_max"]:
+            break
+    _, _, w, cost = whitened_residuals(x, prior, edges)
+    return x, dict(costs=costs, step_norms=steps, weights=w, iterations=it, converged=converged, final_cost=cost)
+
+
+def build_pipeline_graph(gated_poses6, loop_records, kf_ids=None):
+    """The node's graph over scal_pipeline's own keyframes (node k = the k-th own keyframe): prior on node 0 at its gated pose
+    (:286-288, :654), odometry edges (k-1, k) = between of the gated poses (:664-671, :292), one Cauchy(k = 1) loop edge (loop_kf,
+    curr_kf) = (q_rel, t_rel) for every record with verified == 1 (:540-547, :765, :295-300).  loop_records: dicts (or objects) with
+    verified, curr_kf, loop_kf, q_rel, t_rel; kf_ids: database index of every own keyframe (default 0, 1, ...: no pre-filled
+    entries).  Records whose keyframes are not both among kf_ids are left out.  No GPS factors (:673-681): the pipeline has no GPS."""
+    p7 = pose7_from_pose6(gated_poses6)
+    n = len(p7)
+    ids = list(range(n)) if kf_ids is None else [int(v) for v in kf_ids]
+    node = {db: k for k, db in enumerate(ids)}
+    prior = dict(node=0, pose7=p7[0].copy(), var=np.array(PRIOR_VARIANCES))
+    a = np.arange(max(n - 1, 0))
+    edges = make_edges(a, a + 1, se3_between(p7[:-1], p7[1:]) if n > 1 else np.zeros((0, 7)), ODOM_VARIANCES, 0.0)
+    get = (lambda r, k: r[k]) if (len(loop_records) and isinstance(loop_records[0], dict)) else getattr
+    L = [r for r in loop_records if int(get(r, "verified")) == 1 and int(get(r, "curr_kf")) in node and int(get(r, "loop_kf")) in node]
+    if L:
+        z = np.array([list(get(r, "q_rel")) + list(get(r, "t_rel")) for r in L], np.float64)
+        edges = concat_edges(edges, make_edges([node[int(get(r, "loop_kf"))] for r in L], [node[int(get(r, "curr_kf"))] for r in L], z,
+                                               LOOP_VARIANCES, LOOP_CAUCHY_K))
+    return prior, edges
+
+
+def synthetic_graph(true6, li, lj, seed=0, noise=1.0, bad_offset=(8.0, -5.0, 1.0), perturb=0.0):
+    """Test graph over the true poses true6 (x y z roll pitch yaw): odometry edges with drift (noise scales it; 0 = exact), loop edges
+    (li[k], lj[k]) measured from the true poses with small noise, the middle loop's translation displaced by bad_offset (None: all loops
+    consistent).  Initial poses: the dead-reckoned odometry, each moved by a random tangent step of size perturb.  Returns initial
+    poses, prior, edges, index of the displaced loop among the loop edges (-1: none)."""
+    rng = np.random.default_rng(seed)
+    T = pose7_from_pose6(true6)
+    n, n_loops = len(T), len(li)
+    no = np.concatenate([rng.normal(0, 2e-4, (n - 1, 3)) + 1e-4, rng.normal(0, 2e-3, (n - 1, 3))], 1) * noise
+    zo = se3_compose(se3_between(T[:-1], T[1:]), se3_exp(no))
+    init = np.empty_like(T)
+    init[0] = T[0]
+    for k in range(1, n):
+        init[k] = se3_compose(init[k - 1], zo[k - 1])
+    init[:, :4] /= np.linalg.norm(init[:, :4], axis=1, keepdims=True)
+    if perturb:
+        init[1:] = se3_retract(init[1:], rng.normal(0, perturb, (n - 1, 6)))
+    a = np.arange(n - 1)
+    edges = make_edges(a, a + 1, zo, ODOM_VARIANCES, 0.0)
+    li, lj = np.asarray(li, np.int64), np.asarray(lj, np.int64)
+    nl = np.concatenate([rng.normal(0, 1e-3, (n_loops, 3)), rng.normal(0, 1e-2, (n_loops, 3))], 1) * noise
+    zl = se3_compose(se3_between(T[li], T[lj]), se3_exp(nl)).reshape(n_loops, 7)
+    bad = -1
+    if bad_offset is not None and n_loops:
+        bad = n_loops // 2
+        zl[bad, 4:] += np.asarray(bad_offset)
+    if n_loops:
+        edges = concat_edges(edges, make_edges(li, lj, zl, LOOP_VARIANCES, LOOP_CAUCHY_K))
+    prior = dict(node=0, pose7=T[0].copy(), var=np.array(PRIOR_VARIANCES))
+    return init, prior, edges, bad
+
+
+def two_lap_graph(n_nodes, n_loops, **kw):
+    """two laps of a circle (radius 50 m, gentle climb), loops from the second lap onto the first; see synthetic_graph"""
+    half = n_nodes // 2
+    ang = 2 * np.pi * np.arange(n_nodes) / half
+    true6 = np.stack([50 * np.cos(ang), 50 * np.sin(ang), 0.002 * np.arange(n_nodes), 0.01 * np.sin(3 * ang), 0.01 * np.cos(2 * ang), ang + np.pi / 2], 1)
+    lj = half + (np.arange(n_loops) * (n_nodes - half - 1)) // max(n_loops, 1) + 1
+    return synthetic_graph(true6, lj - half, lj, **kw)
+
+
+def out_and_back_graph(n_nodes, n_loops, **kw):
+    """a straight drive out, a turn and the same way back, loops from the way back onto the outbound leg; see synthetic_graph"""
+    half = n_nodes // 2
+    k = np.arange(n_nodes)
+    x = np.where(k < half, k, 2 * half - k) * 0.5
+    yaw = np.where(k < half, 0.0, np.pi)
+    true6 = np.stack([x, 0.3 * (k >= half) + 0.0 * k, 0.001 * k, 0.0 * k, 0.005 * np.sin(0.1 * k), yaw], 1)
+    lj = half + 2 + (np.arange(n_loops) * (n_nodes - half - 3)) // max(n_loops, 1)
+    return synthetic_graph(true6, 2 * half - lj, lj, **kw)
