@@ -25,7 +25,7 @@
 #include "device_utils.hpp"
 #include "voxel_dev.hpp"
 #include "radix_sort.hpp"
-#include "lm_dev.hpp"
+#include "lm_host.hpp"
 #include "features_dev.hpp"
 #include <cmath>
 #include <cstdlib>
@@ -513,19 +513,6 @@ struct NNBuf {
     int cap;
 };
 
-__host__ __device__ inline void m_qmul(const double* a, const double* b, double* o) {
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-__host__ __device__ inline void m_rot(const double* q, const double* v, double* o) {
-    double ux = q[1] * v[2] - q[2] * v[1], uy = q[2] * v[0] - q[0] * v[2], uz = q[0] * v[1] - q[1] * v[0];
-    ux += ux, uy += uy, uz += uz;
-    const double cx = q[1] * uz - q[2] * uy, cy = q[2] * ux - q[0] * uz, cz = q[0] * uy - q[1] * ux;
-    o[0] = (v[0] + q[3] * ux) + cx, o[1] = (v[1] + q[3] * uy) + cy, o[2] = (v[2] + q[3] * uz) + cz;
-}
-
 struct MapPoseIn {
     double q_wodom[4], t_wodom[3];
 };
@@ -557,9 +544,9 @@ __device__ __forceinline__ void map_begin_eval(const MapState* S, const MapCount
     // what the previous step's merge write left for this one (MergeArgs::prebuild)
     o.nv0 = S->next_valid[0], o.nv1 = S->next_valid[1], o.drifted = S->next_unsorted;
     const int over = S->next_over;
-    m_qmul(S->q_wmap_wodom, in.q_wodom, o.x0);
+    q_mul(S->q_wmap_wodom, in.q_wodom, o.x0);
     double rt[3];
-    m_rot(S->q_wmap_wodom, in.t_wodom, rt);
+    q_rot(S->q_wmap_wodom, in.t_wodom, rt);
     o.x0[4] = rt[0] + S->t_wmap_wodom[0], o.x0[5] = rt[1] + S->t_wmap_wodom[1], o.x0[6] = rt[2] + S->t_wmap_wodom[2];
     int cenW = S->mp.cenW, cenH = S->mp.cenH, cenD = S->mp.cenD;
     // :313-322
@@ -1411,9 +1398,9 @@ struct MapPoseDone {
             const double n2 = q_wodom[0] * q_wodom[0] + q_wodom[1] * q_wodom[1] + q_wodom[2] * q_wodom[2] + q_wodom[3] * q_wodom[3];
             const double qi[4] = {-q_wodom[0] / n2, -q_wodom[1] / n2, -q_wodom[2] / n2, q_wodom[3] / n2};
             double qn[4];
-            m_qmul(x, qi, qn);
+            q_mul(x, qi, qn);
             double r2[3];
-            m_rot(qn, S->t_wodom, r2);
+            q_rot(qn, S->t_wodom, r2);
 #pragma unroll
             for (int i = 0; i < 4; ++i) S->q_wmap_wodom[i] = qn[i];
 #pragma unroll
@@ -1448,19 +1435,6 @@ __device__ __forceinline__ void k_map_end_body(MapState* S, const MapCounters* C
     if (threadIdx.x == 0) __hip_atomic_store(&host->seq_done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 SCAL_KERNEL(256, k_map_end)
-
-struct SoAStore {
-    DevBuf<float> x, y, z, w;
-    int alloc(size_t n) {
-        SCAL_TRY(x.alloc(n));
-        SCAL_TRY(y.alloc(n));
-        SCAL_TRY(z.alloc(n));
-        SCAL_TRY(w.alloc(n));
-        return SCAL_OK;
-    }
-    SoA4 v() { return SoA4{x.p, y.p, z.p, w.p}; }
-    CSoA4 cv() const { return CSoA4{x.p, y.p, z.p, w.p}; }
-};
 
 struct MapStore {
     SoAStore pts[2];  // double buffered
@@ -1548,17 +1522,14 @@ struct scal_map {
     // Ceres-adapter mode (scal_map_adapter_begin ... _finish): the step whose solve the caller drives
     bool adapter_active = false;
     MapStep adapter_step;
-    DevBuf<int> bl_live, bl_rowoff, bl_counts;
-    DevBuf<double> d_x7, d_res, d_jac, d_blocks;
-    PinBuf<int> h_counts;
-    BlockList block_list() { return BlockList{bl_live.p, bl_rowoff.p, bl_counts.p}; }
+    BlockAdapter blocks;
     int n_fast = 0, n_general = 0, n_recover_pose = 0, n_recover_insert = 0;  // scal_map_get_path_counters
     bool poll_on_enqueue = true;  // scal_map_set_poll
     int cur = 0;                // parity of the map buffers once every queued step has been inserted
     bool initialised = false;   // at least one step went through the general path
     // map <- odometry correction after the last step whose insertion is confirmed: what an abandoned solve is rolled back to
     double good_q[4] = {0, 0, 0, 1}, good_t[3] = {0, 0, 0};
-    int scan_cap = 0, map_cap = 0, slot_cap = 0;
+    int scan_cap = 0, map_cap = 0;
     // host mirrors (laserMapping.cpp:110-120), refreshed when a pose is collected
     double q_wmap_wodom[4] = {0, 0, 0, 1}, t_wmap_wodom[3] = {0, 0, 0};
     bool have_mp = false;
@@ -1593,12 +1564,9 @@ struct scal_map {
     MergeNew merge_new(int k) {
         return MergeNew{mnew[k].x.p, mnew[k].y.p, mnew[k].z.p, mnew[k].w.p, mcube[k].p, mpkey[k].p, msorted[k].p, msamp[k].p, mpre[k].p, mlb[k].p, mhm[k].p, mblocktot[k].p};
     }
-    DevBuf<int> fvalid, fkind;
-    DevBuf<double> fcp, fpa, fpb, partials;
-    DevBuf<LMSync> lm_sync;
+    LMStore lm;  // residual-block slots (one per stack point), exchange and state of the solve
     DevBuf<float> nnrec;
-    NNBuf nnbuf() { return NNBuf{nnrec.p, slot_cap}; }
-    DevBuf<LMState> d_st;
+    NNBuf nnbuf() { return NNBuf{nnrec.p, lm.slot_cap}; }
     DevBuf<MapCounters> d_C2[NSETS];
     DevBuf<unsigned> surf_parts[NSETS];  // per-block bounding boxes of surf_in (written by the prefetch's gather)
     DevBuf<MapCounters>& d_C(int st) { return d_C2[st]; }
@@ -1606,7 +1574,6 @@ struct scal_map {
     PinBuf<MapCounters> h_C;
     PinBuf<MapState> h_S;
     PinBuf<int> h_misc;
-    FactorSoA factors() { return FactorSoA{fvalid.p, fkind.p, fcp.p, fpa.p, fpb.p, slot_cap}; }
     int alloc_set() {
         const int st = next_set;
         next_set = (next_set + 1) % NSETS;
@@ -1629,7 +1596,6 @@ int scal::map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t
     c->cfg = *cfg;
     c->scan_cap = cfg->max_scan_points;
     c->map_cap = cfg->max_map_points;
-    c->slot_cap = cfg->max_scan_points;
     int rc = SCAL_OK;
     auto A = [&](int r) { if (rc == SCAL_OK) rc = r; };
     const size_t sc = c->scan_cap, mc = c->map_cap;
@@ -1659,13 +1625,10 @@ int scal::map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t
         A(c->msorted[k].alloc(MERGE_MAX)); A(c->mhm[k].alloc(MERGE_MAX)); A(c->mblocktot[k].alloc(MERGE_CHUNKS));
         A(c->mpkey[k].alloc(MERGE_MAX)); A(c->msamp[k].alloc(MERGE_MAX / 8));
     }
-    A(c->fvalid.alloc(sc)); A(c->fkind.alloc(sc)); A(c->fcp.alloc(3 * sc)); A(c->fpa.alloc(3 * sc)); A(c->fpb.alloc(3 * sc));
+    A(c->lm.alloc(c->scan_cap));
     A(c->nnrec.alloc(16 * sc));
-    A(c->partials.alloc(LM_PARTIAL_WORDS));
-    A(c->lm_sync.alloc(1));
-    A(c->d_st.alloc(1)); A(c->d_S.alloc(1)); A(c->d_nfull.alloc(4)); A(c->d_done.alloc(1));
-    A(c->bl_live.alloc(sc)); A(c->bl_rowoff.alloc(sc + 1)); A(c->bl_counts.alloc(2)); A(c->h_counts.alloc(2)); A(c->d_x7.alloc(8));
-    A(c->d_res.alloc(3 * sc)); A(c->d_jac.alloc(21 * sc)); A(c->d_blocks.alloc(10 * sc));
+    A(c->d_S.alloc(1)); A(c->d_nfull.alloc(4)); A(c->d_done.alloc(1));
+    A(c->blocks.alloc(c->scan_cap));
     A(c->h_C.alloc(1)); A(c->h_S.alloc(1)); A(c->h_misc.alloc(4)); A(c->res.alloc(scal_map::NSLOTS));
     // Optional, and therefore LAST (after every mandatory buffer, so that a device where they do not fit still gets a working context
     // with the three-launch build): fixed-slice pools of the one-launch grid build, two sets of 16 B x voxels per cell x 9.4 M cells = 10.5 GB at
@@ -1708,9 +1671,7 @@ int scal::map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t
         // Everything is initialised on the context's own stream (the legacy null stream is not ordered against it).
         // The cell counters obey a zero invariant: every step clears exactly the cells it touched.
         for (int k = 0; k < 4 && rc == SCAL_OK; ++k) rc = c->grid[k & 1].cell[k >> 1].zero(c->stream);
-        if (rc == SCAL_OK && op_memset_async(c->d_st.p, 0, sizeof(LMState), c->stream) != hipSuccess) rc = SCAL_E_HIP;
-        if (rc == SCAL_OK && op_memset_async(c->lm_sync.p, 0, sizeof(LMSync), c->stream) != hipSuccess) rc = SCAL_E_HIP;
-        if (rc == SCAL_OK) rc = c->partials.zero(c->stream);  // sequence number 0 = never published
+        if (rc == SCAL_OK) rc = c->lm.init(c->stream);
         if (rc == SCAL_OK) rc = c->d_done.zero(c->stream);
         MapState& H = *c->h_S.p;
         std::memset(&H, 0, sizeof H);
@@ -1782,7 +1743,7 @@ GridArgs grid_args(scal_map* c, int par, bool fixed_pool = false) {
 int insert_full_sort(scal_map* c, const MapStep& e, const int* n_map) {
     hipStream_t s = c->stream;
     MapCounters* C = c->d_C(e.set).p;
-    LMState* st = c->d_st.p;
+    LMState* st = c->lm.d_st.p;
     for (int k = 0; k < 2; ++k) {
         MapStore& M = c->map[k];
         const int n_tot_max = std::min(c->map_cap, n_map[k] + c->scan_cap);
@@ -1828,12 +1789,12 @@ int launch_insert_merge(scal_map* c, const MapStep& e, bool fused = false) {
     // built by the three general launches - the general path, and queued steps of a context without fixed pools (filters finer than
     // 48 voxels per cell pair) - they are computed here
     if (!(fused && c->grid_fixed)) SCAL_LAUNCH("k_merge_okeys", k_merge_okeys, dim3(MERGE_KB0 + MERGE_KB1), dim3(1024), 0, s, a, c->d_S.p, C);
-    SCAL_LAUNCH("k_merge_keys", k_merge_keys, dim3(MERGE_KEYS_GRID), dim3(1024), lds, s, a, c->d_st.p, c->d_S.p, C);
+    SCAL_LAUNCH("k_merge_keys", k_merge_keys, dim3(MERGE_KEYS_GRID), dim3(1024), lds, s, a, c->lm.d_st.p, c->d_S.p, C);
     SCAL_LAUNCH("k_merge_lookup", k_merge_lookup, dim3(2 * MERGE_CHUNKS), dim3(512), 0, s, a, c->d_S.p, C);
     MergeTail t{};
     int grid = MERGE_WRITE_GRID;
     if (fused) {
-        t.fused = 1, t.seq = e.seq, t.st = c->d_st.p, t.full_out = c->full_out.v(), t.full_cap = c->scan_cap;
+        t.fused = 1, t.seq = e.seq, t.st = c->lm.d_st.p, t.full_out = c->full_out.v(), t.full_cap = c->scan_cap;
         if (e.have_full && e.feat) {
             FeatDeviceView v = features_view(e.feat);
             t.full = CSoA4{v.x, v.y, v.z, v.i}, t.d_nfull = &v.P->n_kept;
@@ -1858,10 +1819,10 @@ int launch_tail(scal_map* c, const MapStep& e, bool registered = false) {
         const int nb = std::max(1, div_up(c->scan_cap, 256));
         if (e.feat) {
             FeatDeviceView v = features_view(e.feat);
-            SCAL_LAUNCH("k_transform_cloud", k_transform_cloud, dim3(nb), dim3(256), 0, s, CSoA4{v.x, v.y, v.z, v.i}, &v.P->n_kept, c->scan_cap, c->d_st.p, c->d_S.p,
+            SCAL_LAUNCH("k_transform_cloud", k_transform_cloud, dim3(nb), dim3(256), 0, s, CSoA4{v.x, v.y, v.z, v.i}, &v.P->n_kept, c->scan_cap, c->lm.d_st.p, c->d_S.p,
                                c->full_out.v());
         } else {
-            SCAL_LAUNCH("k_transform_cloud", k_transform_cloud, dim3(nb), dim3(256), 0, s, c->full_in.cv(), c->d_nfull.p, c->scan_cap, c->d_st.p, c->d_S.p,
+            SCAL_LAUNCH("k_transform_cloud", k_transform_cloud, dim3(nb), dim3(256), 0, s, c->full_in.cv(), c->d_nfull.p, c->scan_cap, c->lm.d_st.p, c->d_S.p,
                                c->full_out.v());
         }
     }
@@ -1876,7 +1837,7 @@ MapPoseDone make_pose_done(scal_map* c, const MapStep& e) {
     MapCounters* C = c->d_C(e.set).p;
     MapPoseDone pd;
     pd.active = 1, pd.seq = e.seq;
-    pd.S = c->d_S.p, pd.st = c->d_st.p, pd.C = C, pd.host = c->res.p + e.slot;
+    pd.S = c->d_S.p, pd.st = c->lm.d_st.p, pd.C = C, pd.host = c->res.p + e.slot;
     for (int k = 0; k < 2; ++k) {
         pd.nw.stack[k] = k == 0 ? c->corner_stack(e.set).cv() : c->surf_stack(e.set).cv();
         pd.nw.d_ns[k] = k == 0 ? &C->n_corner_stack : &C->n_surf_stack;
@@ -1893,7 +1854,7 @@ int launch_pose_part(scal_map* c, const MapStep& e, bool prepare_only = false) {
     hipStream_t s = c->stream;
     const int st_ = e.set;
     MapCounters* C = c->d_C(st_).p;
-    LMState* st = c->d_st.p;
+    LMState* st = c->lm.d_st.p;
     MapState* S = c->d_S.p;
     if (e.feat) {
         if (e.prefetched) {
@@ -1912,7 +1873,7 @@ int launch_pose_part(scal_map* c, const MapStep& e, bool prepare_only = false) {
     if (!e.prefetched) SCAL_TRY(enqueue_stack_filters(c, c->vf, c->vf, s, e.n_corner_bound, e.n_surf_bound, st_, false));
     MapBeginArgs mb;
     mb.active = 0, mb.in = e.pose, mb.allow_window_change = e.fast ? 0 : 1, mb.inv_line = 1.0f / c->cfg.line_res, mb.inv_plane = 1.0f / c->cfg.plane_res;
-    mb.slot_cap = c->slot_cap, mb.prebuilt = e.prebuilt ? 1 : 0, mb.S = S;
+    mb.slot_cap = c->lm.slot_cap, mb.prebuilt = e.prebuilt ? 1 : 0, mb.S = S;
     // a queued step whose grid the previous merge write left has no launch between its start and the first neighbour search: the
     // start rides on that launch
     const bool begin_in_knn = e.fast && e.prebuilt && c->grid_fixed && !prepare_only;
@@ -1932,8 +1893,8 @@ int launch_pose_part(scal_map* c, const MapStep& e, bool prepare_only = false) {
         return SCAL_OK;
     }
     // two outer iterations (:563)
-    FactorSoA F = c->factors();
-    const int assoc_blocks = std::max(1, std::min(3072, div_up(c->slot_cap, 8)));
+    FactorSoA F = c->lm.factors();
+    const int assoc_blocks = std::max(1, std::min(3072, div_up(c->lm.slot_cap, 8)));
     MapPoseDone pd = make_pose_done(c, e);
     const AssocFit fit{c->corner_stack(st_).cv(), c->surf_stack(st_).cv(), c->nnbuf(), C, F};
     for (int outer = 0; outer < 2; ++outer) {
@@ -1946,7 +1907,7 @@ int launch_pose_part(scal_map* c, const MapStep& e, bool prepare_only = false) {
         // copy + the insertion keys: one launch.  (The fit had a launch of its own while it took 17 us at one thread per slot; at 3 us
         // - closed-form eigenpair, register-only QR - it fits in front of the first evaluation.)
         pd.active = outer == 1;
-        launch_lm_solve(s, F, &C->n_slots, st, &C->solve_on, c->partials.p, c->lm_sync.p, outer, &S->abort, fit, pd, "k_lm_solve_map");
+        launch_lm_solve(s, F, &C->n_slots, st, &C->solve_on, c->lm.partials.p, c->lm.lm_sync.p, outer, &S->abort, fit, pd, "k_lm_solve_map");
     }
     SCAL_HIP(hipGetLastError());
     if (!e.fast) SCAL_HIP(op_event_record(c->ev_pose[e.slot], s));  // a queued step announces its pose through MapResult::seq_pose
@@ -2002,16 +1963,11 @@ constexpr int MAP_RC_LM = 1000;  // internal: launch sequence fine, solve abando
 bool lm_gave_up(const MapResult& R) { return R.st.termination == 5 || R.S1.abort == MAP_ABORT_LM; }
 int lm_reset(scal_map* c, bool restore_pose) {
     hipStream_t s = c->stream;
-    SCAL_HIP(op_stream_synchronize(s));
-    SCAL_HIP(op_memset_async(c->lm_sync.p, 0, sizeof(LMSync), s));
-    SCAL_TRY(c->partials.zero(s));
+    SCAL_TRY(c->lm.clear_exchange(s));
     SCAL_HIP(op_memset_async(&c->d_S.p->abort, 0, sizeof(int), s));
     if (restore_pose) {
-        double* h = reinterpret_cast<double*>(c->h_S.p);  // pinned scratch
-        for (int i = 0; i < 4; ++i) h[i] = c->good_q[i];
-        for (int i = 0; i < 3; ++i) h[4 + i] = c->good_t[i];
         static_assert(offsetof(MapState, t_wmap_wodom) == offsetof(MapState, q_wmap_wodom) + 4 * sizeof(double), "pose fields are contiguous");
-        SCAL_HIP(op_memcpy_async(c->d_S.p->q_wmap_wodom, h, 7 * sizeof(double), hipMemcpyHostToDevice, s));
+        SCAL_TRY(c->blocks.set_pose(s, c->d_S.p->q_wmap_wodom, c->good_q, c->good_t));
     }
     SCAL_HIP(op_stream_synchronize(s));
     return SCAL_OK;
@@ -2700,21 +2656,13 @@ extern "C" int scal_map_adapter_begin(scal_map_t* c, const float* corner_last, i
     SCAL_TRY(launch_pose_part(c, e, true));  // stack filters, transformAssociateToMap + window, cell grids
     hipStream_t s = c->stream;
     SCAL_HIP(op_memcpy_async(c->h_S.p, c->d_S.p, sizeof(MapState), hipMemcpyDeviceToHost, s));
-    SCAL_HIP(op_memcpy_async(c->res.p + e.slot, c->d_st.p, sizeof(LMState), hipMemcpyDeviceToHost, s));  // MapResult::st is its first member
+    SCAL_HIP(op_memcpy_async(c->res.p + e.slot, c->lm.d_st.p, sizeof(LMState), hipMemcpyDeviceToHost, s));  // MapResult::st is its first member
     SCAL_HIP(op_stream_synchronize(s));
     const double* x = c->res.p[e.slot].st.x;
     for (int i = 0; i < 4; ++i) q_w_curr[i] = x[i];
     for (int i = 0; i < 3; ++i) t_w_curr[i] = x[4 + i];
     c->adapter_step = e;
     c->adapter_active = true;
-    return SCAL_OK;
-}
-
-static int adapter_set_pose(scal_map* c, const double* q, const double* t) {
-    double* h = reinterpret_cast<double*>(c->h_S.p);  // pinned scratch (MapState is larger than 7 doubles)
-    for (int i = 0; i < 4; ++i) h[i] = q[i];
-    for (int i = 0; i < 3; ++i) h[4 + i] = t[i];
-    SCAL_HIP(op_memcpy_async(c->d_st.p->x, h, sizeof(double) * 7, hipMemcpyHostToDevice, c->stream));
     return SCAL_OK;
 }
 
@@ -2731,21 +2679,18 @@ extern "C" int scal_map_associate(scal_map_t* c, const double* q_w_curr, const d
     hipStream_t s = c->stream;
     const MapStep& e = c->adapter_step;
     MapCounters* C = c->d_C(e.set).p;
-    SCAL_TRY(adapter_set_pose(c, q_w_curr, t_w_curr));
-    SCAL_HIP(op_stream_synchronize(s));  // the pinned scratch is reused
-    FactorSoA F = c->factors();
-    const int assoc_blocks = std::max(1, std::min(3072, div_up(c->slot_cap, 8)));
+    SCAL_TRY(c->blocks.set_pose(s, c->lm.d_st.p->x, q_w_curr, t_w_curr));
+    FactorSoA F = c->lm.factors();
+    const int assoc_blocks = std::max(1, std::min(3072, div_up(c->lm.slot_cap, 8)));
     SCAL_LAUNCH("k_assoc_knn", k_assoc_knn, dim3(assoc_blocks), dim3(256), 0, s, c->corner_stack(e.set).cv(), c->surf_stack(e.set).cv(), c->d_S.p,
-                     c->grid[0].cell[e.par].p, c->grid[0].pts(e.par), c->grid[1].cell[e.par].p, c->grid[1].pts(e.par), c->d_st.p, C, c->nnbuf(), MapBeginArgs{});
+                     c->grid[0].cell[e.par].p, c->grid[0].pts(e.par), c->grid[1].cell[e.par].p, c->grid[1].pts(e.par), c->lm.d_st.p, C, c->nnbuf(), MapBeginArgs{});
     const AssocFit fit{c->corner_stack(e.set).cv(), c->surf_stack(e.set).cv(), c->nnbuf(), C, F};
-    SCAL_LAUNCH("k_assoc_fit", k_assoc_fit, dim3(std::max(1, div_up(c->slot_cap, 64))), dim3(64), 0, s, fit, c->d_S.p);
-    SCAL_LAUNCH("k_blocks_compact", k_blocks_compact, dim3(1), dim3(1024), 0, s, F, &C->n_slots, c->block_list());
-    SCAL_HIP(hipGetLastError());
-    SCAL_HIP(op_memcpy_async(c->h_counts.p, c->bl_counts.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    SCAL_LAUNCH("k_assoc_fit", k_assoc_fit, dim3(std::max(1, div_up(c->lm.slot_cap, 64))), dim3(64), 0, s, fit, c->d_S.p);
+    SCAL_TRY(c->blocks.compact(s, F, &C->n_slots));
     SCAL_HIP(op_memcpy_async(c->h_C.p, C, sizeof(MapCounters), hipMemcpyDeviceToHost, s));
     SCAL_HIP(op_stream_synchronize(s));
-    if (!c->h_C.p->solve_on) c->h_counts.p[0] = c->h_counts.p[1] = 0;  // map too small (:555): no residual blocks, the caller skips the solve
-    *n_blocks = c->h_counts.p[0], *n_residuals = c->h_counts.p[1];
+    if (!c->h_C.p->solve_on) c->blocks.set_empty();  // map too small (:555): no residual blocks, the caller skips the solve
+    *n_blocks = c->blocks.n_blocks(), *n_residuals = c->blocks.n_residuals();
     return SCAL_OK;
 }
 
@@ -2758,15 +2703,8 @@ extern "C" int scal_map_get_blocks(scal_map_t* c, scal_block* out, int cap) {
         set_error("scal_map_get_blocks: no scal_map_adapter_begin");
         return SCAL_E_STATE;
     }
-    static_assert(sizeof(scal_block) == 80, "scal_block layout");
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    const int n = std::min(cap, c->h_counts.p[0]);
-    if (n <= 0) return 0;
-    hipStream_t s = c->stream;
-    SCAL_LAUNCH("k_blocks_export", k_blocks_export, dim3(div_up(c->h_counts.p[0], 256)), dim3(256), 0, s, c->factors(), c->block_list(), c->d_blocks.p);
-    SCAL_HIP(op_memcpy_async(out, c->d_blocks.p, sizeof(scal_block) * n, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(op_stream_synchronize(s));
-    return n;
+    return c->blocks.get_blocks(c->stream, c->lm.factors(), out, cap);
 }
 
 extern "C" int scal_map_eval_blocks(scal_map_t* c, const double* x7, int want_jac, double* residuals, double* jacobians) {
@@ -2779,17 +2717,7 @@ extern "C" int scal_map_eval_blocks(scal_map_t* c, const double* x7, int want_ja
         return SCAL_E_STATE;
     }
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    const int nb = c->h_counts.p[0], nr = c->h_counts.p[1];
-    if (nb == 0) return SCAL_OK;
-    hipStream_t s = c->stream;
-    SCAL_HIP(op_memcpy_async(c->d_x7.p, x7, sizeof(double) * 7, hipMemcpyHostToDevice, s));
-    SCAL_LAUNCH("k_blocks_eval", k_blocks_eval, dim3(div_up(nb, 256)), dim3(256), 0, s, c->factors(), c->block_list(), c->d_x7.p, want_jac ? 1 : 0,
-                     c->d_res.p, c->d_jac.p);
-    SCAL_HIP(hipGetLastError());
-    SCAL_HIP(op_memcpy_async(residuals, c->d_res.p, sizeof(double) * nr, hipMemcpyDeviceToHost, s));
-    if (want_jac) SCAL_HIP(op_memcpy_async(jacobians, c->d_jac.p, sizeof(double) * 7 * nr, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(op_stream_synchronize(s));
-    return SCAL_OK;
+    return c->blocks.eval_blocks(c->stream, c->lm.factors(), x7, want_jac, residuals, jacobians);
 }
 
 extern "C" int scal_map_adapter_finish(scal_map_t* c, const double* q_w_curr, const double* t_w_curr, float* registered, scal_map_stats* stats) {
@@ -2805,7 +2733,7 @@ extern "C" int scal_map_adapter_finish(scal_map_t* c, const double* q_w_curr, co
     hipStream_t s = c->stream;
     MapStep& e = c->adapter_step;
     c->adapter_active = false;
-    SCAL_TRY(adapter_set_pose(c, q_w_curr, t_w_curr));
+    SCAL_TRY(c->blocks.set_pose(s, c->lm.d_st.p->x, q_w_curr, t_w_curr));
     // transformUpdate (:735), host copy, insertion keys: what the second solve's launch does on the all-device path
     SCAL_LAUNCH("k_map_pose_done", k_map_pose_done, dim3(64), dim3(256), 0, s, make_pose_done(c, e));
     SCAL_HIP(hipGetLastError());

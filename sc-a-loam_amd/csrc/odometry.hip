@@ -17,7 +17,7 @@
 #include <deque>
 #include "device_utils.hpp"
 #include "voxel_dev.hpp"
-#include "lm_dev.hpp"
+#include "lm_host.hpp"
 #include "features_dev.hpp"
 #include <cmath>
 #include <algorithm>
@@ -478,19 +478,6 @@ __device__ __forceinline__ void k_odom_gather_body(const OdomGatherArgs& a, Odom
 }
 SCAL_KERNEL(256, k_odom_gather)
 
-struct OSoA {
-    DevBuf<float> x, y, z, w;
-    int alloc(size_t n) {
-        SCAL_TRY(x.alloc(n));
-        SCAL_TRY(y.alloc(n));
-        SCAL_TRY(z.alloc(n));
-        SCAL_TRY(w.alloc(n));
-        return SCAL_OK;
-    }
-    SoA4 v() { return SoA4{x.p, y.p, z.p, w.p}; }
-    CSoA4 cv() const { return CSoA4{x.p, y.p, z.p, w.p}; }
-};
-
 }  // namespace scal
 
 using namespace scal;
@@ -499,7 +486,7 @@ struct scal_odom {
     scal_odom_config cfg;
     // the stream and the events are released by `delete c`, after scal_odom_destroy has synchronised the stream
     LaneStream stream;
-    int cap = 0, feat_cap = 0, slot_cap = 0;
+    int cap = 0, feat_cap = 0;
     bool systemInited = false;
     // steps enqueued and not collected yet: B(k+1) only needs B(k)'s device state, so it can be queued right behind it
     static constexpr int MAX_STEPS = 4;
@@ -512,11 +499,9 @@ struct scal_odom {
     int next_slot = 0;
     double q_w_curr[4] = {0, 0, 0, 1}, t_w_curr[3] = {0, 0, 0};  // :93-94
     DevBuf<float> aos;
-    OSoA sharp, flat, less_sharp, less_flat;  // current scan
-    OSoA corner_last, surf_last;              // previous scan (kd-tree inputs, :567-568)
-    DevBuf<int> fvalid, fkind;
-    DevBuf<double> fcp, fpa, fpb, partials;
-    DevBuf<LMSync> lm_sync;
+    SoAStore sharp, flat, less_sharp, less_flat;  // current scan
+    SoAStore corner_last, surf_last;              // previous scan (kd-tree inputs, :567-568)
+    LMStore lm;  // residual-block slots, exchange and state of the solve
     DevBuf<int> cell_cnt, cell_start, cell_rank;  // NN(1) bucket index of corner_last | surf_last (see CellIndex)
     DevBuf<float4> cell_pts;
     // tables are laid out [cloud][level]; point arrays [level][corner | surf]
@@ -531,20 +516,14 @@ struct scal_odom {
     }
     DevBuf<int> ring_tab;  // 2 sets of [corner first | corner last | surf first | surf last] x RING_TAB (double-buffered)
     int tab_cur = 0;       // set read by this scan's association
-    DevBuf<LMState> d_st;
     DevBuf<OdomCounters> d_C;
     PinBuf<LMState> h_st;       // [MAX_STEPS]
     PinBuf<OdomCounters> h_up;  // upload staging of scal_odom_step
     HostStage hs;               // pinned staging of its four host clouds (first call)
     // Ceres-adapter mode (scal_odom_adapter_begin ... _finish)
     bool adapter_active = false, adapter_solve = false;
-    DevBuf<int> bl_live, bl_rowoff, bl_counts;
-    DevBuf<double> d_x7, d_res, d_jac, d_blocks;
-    PinBuf<int> h_counts;
-    PinBuf<double> h_x7;
+    BlockAdapter blocks;
     int outer_next = 0;
-    BlockList block_list() { return BlockList{bl_live.p, bl_rowoff.p, bl_counts.p}; }
-    FactorSoA factors() { return FactorSoA{fvalid.p, fkind.p, fcp.p, fpa.p, fpb.p, slot_cap}; }
 };
 
 int scal::odom_create(const scal_odom_config* cfg, StreamLayout layout, scal_odom_t** out) {
@@ -558,35 +537,28 @@ int scal::odom_create(const scal_odom_config* cfg, StreamLayout layout, scal_odo
     c->cfg = *cfg;
     c->cap = cfg->max_points;
     c->feat_cap = 120 * 64;  // lessSharp <= 20 per segment, 6 segments per ring (scanRegistration.cpp:314-328)
-    c->slot_cap = 36 * 64;   // sharp <= 2, flat <= 4 per segment
     int rc = SCAL_OK;
     auto A = [&](int r) { if (rc == SCAL_OK) rc = r; };
+    A(c->lm.alloc(36 * 64));  // slot_cap: sharp <= 2, flat <= 4 per segment
     A(c->aos.alloc((size_t)c->cap * 4));
-    A(c->sharp.alloc(c->slot_cap)); A(c->flat.alloc(c->slot_cap));
+    A(c->sharp.alloc(c->lm.slot_cap)); A(c->flat.alloc(c->lm.slot_cap));
     A(c->less_sharp.alloc(c->feat_cap)); A(c->corner_last.alloc(c->feat_cap));
     A(c->less_flat.alloc(c->cap)); A(c->surf_last.alloc(c->cap));
-    A(c->fvalid.alloc(c->slot_cap)); A(c->fkind.alloc(c->slot_cap));
-    A(c->fcp.alloc(3 * (size_t)c->slot_cap)); A(c->fpa.alloc(3 * (size_t)c->slot_cap)); A(c->fpb.alloc(3 * (size_t)c->slot_cap));
-    A(c->partials.alloc(LM_PARTIAL_WORDS));
-    A(c->lm_sync.alloc(1));
     A(c->cell_cnt.alloc(2 * OD_LEVELS * OD_H)); A(c->cell_start.alloc(2 * OD_LEVELS * OD_START_STRIDE));
     A(c->cell_rank.alloc(OD_LEVELS * ((size_t)c->feat_cap + c->cap))); A(c->cell_pts.alloc(OD_LEVELS * ((size_t)c->feat_cap + c->cap)));
     A(c->ring_tab.alloc(8 * RING_TAB));
-    A(c->bl_live.alloc(c->slot_cap)); A(c->bl_rowoff.alloc(c->slot_cap + 1)); A(c->bl_counts.alloc(2)); A(c->h_counts.alloc(2)); A(c->h_x7.alloc(8));
-    A(c->d_x7.alloc(8)); A(c->d_res.alloc(3 * (size_t)c->slot_cap)); A(c->d_jac.alloc(21 * (size_t)c->slot_cap)); A(c->d_blocks.alloc(10 * (size_t)c->slot_cap));
-    A(c->d_st.alloc(1)); A(c->d_C.alloc(1)); A(c->h_st.alloc(scal_odom::MAX_STEPS)); A(c->h_up.alloc(1));
+    A(c->blocks.alloc(c->lm.slot_cap));
+    A(c->d_C.alloc(1)); A(c->h_st.alloc(scal_odom::MAX_STEPS)); A(c->h_up.alloc(1));
     if (rc == SCAL_OK) rc = lm_check_residency<LMNoHook, LMNoHook>(c->cfg.device);
     if (rc == SCAL_OK) rc = c->stream.acquire(c->cfg.device, stage_lane(layout, STAGE_ODOM));
     for (int k = 0; k < scal_odom::MAX_STEPS && rc == SCAL_OK; ++k) rc = c->ev[k].create(hipEventDisableTiming);
     if (rc == SCAL_OK) {
         // everything is initialised on the context's own stream (the legacy null stream is not ordered against it)
-        if (op_memset_async(c->lm_sync.p, 0, sizeof(LMSync), c->stream) != hipSuccess) rc = SCAL_E_HIP;
-        if (rc == SCAL_OK) rc = c->partials.zero(c->stream);  // sequence number 0 = never published
-        if (rc == SCAL_OK && op_memset_async(c->d_st.p, 0, sizeof(LMState), c->stream) != hipSuccess) rc = SCAL_E_HIP;
+        rc = c->lm.init(c->stream);
         if (rc == SCAL_OK && op_memset_async(c->d_C.p, 0, sizeof(OdomCounters), c->stream) != hipSuccess) rc = SCAL_E_HIP;
         if (rc == SCAL_OK) rc = c->cell_cnt.zero(c->stream);
         if (rc == SCAL_OK) rc = c->cell_start.zero(c->stream);
-        SCAL_LAUNCH("k_odom_init_pose", k_odom_init_pose, dim3(1), dim3(256), 0, c->stream, c->d_st.p, c->ring_tab.p);
+        SCAL_LAUNCH("k_odom_init_pose", k_odom_init_pose, dim3(1), dim3(256), 0, c->stream, c->lm.d_st.p, c->ring_tab.p);
         if (rc == SCAL_OK && op_stream_synchronize(c->stream) != hipSuccess) rc = SCAL_E_HIP;
     }
     if (rc != SCAL_OK) {
@@ -609,26 +581,13 @@ extern "C" void scal_odom_destroy(scal_odom_t* c) {
 
 namespace {
 
-void o_qmul(const double* a, const double* b, double* o) {
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-void o_rot(const double* q, const double* v, double* o) {
-    double ux = q[1] * v[2] - q[2] * v[1], uy = q[2] * v[0] - q[0] * v[2], uz = q[0] * v[1] - q[1] * v[0];
-    ux += ux, uy += uy, uz += uz;
-    const double cx = q[1] * uz - q[2] * uy, cy = q[2] * ux - q[0] * uz, cz = q[0] * uy - q[1] * ux;
-    o[0] = (v[0] + q[3] * ux) + cx, o[1] = (v[1] + q[3] * uy) + cy, o[2] = (v[2] + q[3] * uz) + cz;
-}
-
 int launch_handover(scal_odom* c, int slot, hipEvent_t ev);
 // inputs already in sharp / flat / less_sharp / less_flat with counts in d_C
 int odom_enqueue(scal_odom* c) {
     hipStream_t s = c->stream;
     OdomCounters* C = c->d_C.p;
-    LMState* st = c->d_st.p;
-    FactorSoA F = c->factors();
+    LMState* st = c->lm.d_st.p;
+    FactorSoA F = c->lm.factors();
     const bool solve = c->systemInited;  // first frame: no optimisation (:267-271)
     c->systemInited = true;
     const int slot = c->next_slot;
@@ -636,11 +595,11 @@ int odom_enqueue(scal_odom* c) {
     if (solve) {
         for (int outer = 0; outer < 2; ++outer) {  // :278
             {
-                SCAL_LAUNCH("k_odom_assoc", k_odom_assoc, dim3(std::max(1, c->slot_cap)), dim3(256), 0, s, c->sharp.cv(), c->flat.cv(),
+                SCAL_LAUNCH("k_odom_assoc", k_odom_assoc, dim3(std::max(1, c->lm.slot_cap)), dim3(256), 0, s, c->sharp.cv(), c->flat.cv(),
                                    c->corner_last.cv(), c->surf_last.cv(), st, C, outer, F, c->cell_index(0), c->cell_index(1), c->ring_tab.p + c->tab_cur * 4 * RING_TAB);
             }
             {
-                                launch_lm_solve(s, F, &C->n_slots, st, &C->enable, c->partials.p, c->lm_sync.p, outer, nullptr, LMNoHook(), LMNoHook(), "k_lm_solve_odom");
+                                launch_lm_solve(s, F, &C->n_slots, st, &C->enable, c->lm.partials.p, c->lm.lm_sync.p, outer, nullptr, LMNoHook(), LMNoHook(), "k_lm_solve_odom");
             }
         }
     }
@@ -653,7 +612,7 @@ int odom_enqueue(scal_odom* c) {
 int launch_handover(scal_odom* c, int slot, hipEvent_t ev) {
     hipStream_t s = c->stream;
     OdomCounters* C = c->d_C.p;
-    LMState* st = c->d_st.p;
+    LMState* st = c->lm.d_st.p;
     {
         HandoverArgs h;
         h.in[0] = c->less_sharp.cv(), h.in[1] = c->less_flat.cv();
@@ -664,7 +623,7 @@ int launch_handover(scal_odom* c, int slot, hipEvent_t ev) {
         h.nb0 = std::max(1, div_up(c->feat_cap, 256));
         h.tab_write = c->ring_tab.p + (c->tab_cur ^ 1) * 4 * RING_TAB;
         h.tab_reset = c->ring_tab.p + c->tab_cur * 4 * RING_TAB;
-        h.st = st, h.host_st = c->h_st.p + slot, h.sync = c->lm_sync.p;
+        h.st = st, h.host_st = c->h_st.p + slot, h.sync = c->lm.lm_sync.p;
         for (int k = 0; k < 2; ++k)
             for (int l = 0; l < OD_LEVELS; ++l) h.cell_cnt[k][l] = c->cell_cnt_of(k, l), h.cell_rank[k][l] = c->cell_rank_of(k, l);
         const dim3 grid(h.nb0 + std::max(1, div_up(c->cap, 256)));
@@ -700,20 +659,17 @@ int odom_collect(scal_odom* c, double* q_lc, double* t_lc, double* q_w, double* 
         // A workgroup of this step's solve - or of a step queued in front of it: the flag is sticky on the device and every solve
         // behind it returned at once - ran out of polls.  Never seen outside the test hook, but the pose cannot be trusted: the step
         // is reported as failed (the pose keeps its last good value), and the exchange is cleared once everything queued has drained.
-        (void)op_stream_synchronize(c->stream);
-        (void)op_memset_async(c->lm_sync.p, 0, sizeof(LMSync), c->stream);
-        (void)c->partials.zero(c->stream);
-        (void)op_stream_synchronize(c->stream);
+        (void)c->lm.clear_exchange(c->stream);
         set_error("LM solve abandoned: grid barrier timed out");
         return SCAL_E_HIP;
     }
     const double* x = L.x;
     if (solve) {  // :504-505
         double r[3];
-        o_rot(c->q_w_curr, x + 4, r);
+        q_rot(c->q_w_curr, x + 4, r);
         for (int i = 0; i < 3; ++i) c->t_w_curr[i] = c->t_w_curr[i] + r[i];
         double qn[4];
-        o_qmul(c->q_w_curr, x, qn);
+        q_mul(c->q_w_curr, x, qn);
         for (int i = 0; i < 4; ++i) c->q_w_curr[i] = qn[i];
     }
     for (int i = 0; i < 4; ++i) q_lc[i] = x[i], q_w[i] = c->q_w_curr[i];
@@ -738,7 +694,7 @@ static int odom_upload(scal_odom* c, const float* sharp, int n_sharp, const floa
     hipStream_t s = c->stream;
     SCAL_HIP(op_stream_synchronize(s));  // the upload staging may still feed the previous call's copy
     c->hs.finish();
-    (void)c->hs.reserve(((size_t)2 * c->slot_cap + c->feat_cap + c->cap) * 16 + 4096);
+    (void)c->hs.reserve(((size_t)2 * c->lm.slot_cap + c->feat_cap + c->cap) * 16 + 4096);
     OdomCounters& H = *c->h_up.p;
     // keep the device-resident n_corner_last / n_surf_last, refresh the per-scan part from pinned memory
     OdomCounters fresh;
@@ -748,7 +704,7 @@ static int odom_upload(scal_odom* c, const float* sharp, int n_sharp, const floa
     const size_t off = offsetof(OdomCounters, n_sharp);
     SCAL_HIP(op_memcpy_async(reinterpret_cast<char*>(c->d_C.p) + off, reinterpret_cast<char*>(&H) + off, sizeof(OdomCounters) - off,
                             hipMemcpyHostToDevice, s));
-    auto up = [&](const float* src, int n, OSoA& dst) -> int {
+    auto up = [&](const float* src, int n, SoAStore& dst) -> int {
         if (n > 0) {
             SCAL_HIP(c->hs.h2d(c->aos.p, src, sizeof(float) * 4 * n, s));
             launch_deinterleave(s, c->aos.p, n, dst.v());
@@ -770,8 +726,8 @@ extern "C" int scal_odom_step(scal_odom_t* c, const float* sharp, int n_sharp, c
         set_error("scal_odom_step: bad argument");
         return SCAL_E_ARG;
     }
-    if (n_sharp + n_flat > c->slot_cap || n_sharp > c->slot_cap || n_flat > c->slot_cap || n_less_sharp > c->feat_cap || n_less_flat > c->cap) {
-        set_error("scal_odom_step: cloud larger than the context capacity (sharp+flat <= %d, lessSharp <= %d, lessFlat <= %d)", c->slot_cap,
+    if (n_sharp + n_flat > c->lm.slot_cap || n_sharp > c->lm.slot_cap || n_flat > c->lm.slot_cap || n_less_sharp > c->feat_cap || n_less_flat > c->cap) {
+        set_error("scal_odom_step: cloud larger than the context capacity (sharp+flat <= %d, lessSharp <= %d, lessFlat <= %d)", c->lm.slot_cap,
                   c->feat_cap, c->cap);
         return SCAL_E_TOO_MANY;
     }
@@ -806,8 +762,8 @@ extern "C" int scal_odom_enqueue_features(scal_odom_t* c, scal_features_t* feat)
     a.less_flat = CSoA4{v.lfx, v.lfy, v.lfz, v.lfi};
     a.n_sharp = &v.P->n_sharp, a.n_flat = &v.P->n_flat, a.n_less = &v.P->n_less_sharp, a.n_less_flat = &v.P->n_less_flat;
     a.o_sharp = c->sharp.v(), a.o_flat = c->flat.v(), a.o_less = c->less_sharp.v(), a.o_less_flat = c->less_flat.v();
-    a.slot_cap = c->slot_cap, a.feat_cap = c->feat_cap, a.cap = std::min(c->cap, v.cap);
-    a.nbs = std::max(1, div_up(c->slot_cap, 256)), a.nbf = std::max(1, div_up(c->feat_cap, 256));
+    a.slot_cap = c->lm.slot_cap, a.feat_cap = c->feat_cap, a.cap = std::min(c->cap, v.cap);
+    a.nbs = std::max(1, div_up(c->lm.slot_cap, 256)), a.nbf = std::max(1, div_up(c->feat_cap, 256));
     SCAL_TRY(features_wait_done(feat, s));
     SCAL_LAUNCH("k_odom_gather", k_odom_gather, dim3(2 * a.nbs + a.nbf + std::max(1, div_up(a.cap, 256))), dim3(256), 0, s, a, c->d_C.p);
     SCAL_TRY(features_note_reader(feat, s));  // everything stage B needs has been copied out of the features context
@@ -843,7 +799,7 @@ extern "C" int scal_odom_adapter_begin(scal_odom_t* c, const float* sharp, int n
         set_error("scal_odom_adapter_begin: bad argument");
         return SCAL_E_ARG;
     }
-    if (n_sharp + n_flat > c->slot_cap || n_less_sharp > c->feat_cap || n_less_flat > c->cap) {
+    if (n_sharp + n_flat > c->lm.slot_cap || n_less_sharp > c->feat_cap || n_less_flat > c->cap) {
         set_error("scal_odom_adapter_begin: cloud larger than the context capacity");
         return SCAL_E_TOO_MANY;
     }
@@ -855,7 +811,7 @@ extern "C" int scal_odom_adapter_begin(scal_odom_t* c, const float* sharp, int n
     hipStream_t s = c->stream;
     SCAL_HIP(op_stream_synchronize(s));
     SCAL_TRY(odom_upload(c, sharp, n_sharp, less_sharp, n_less_sharp, flat, n_flat, less_flat, n_less_flat));
-    SCAL_HIP(op_memcpy_async(c->h_st.p, c->d_st.p, sizeof(LMState), hipMemcpyDeviceToHost, s));
+    SCAL_HIP(op_memcpy_async(c->h_st.p, c->lm.d_st.p, sizeof(LMState), hipMemcpyDeviceToHost, s));
     SCAL_HIP(op_stream_synchronize(s));
     for (int i = 0; i < 4; ++i) q_last_curr[i] = c->h_st.p->x[i];   // para_q / para_t persist across scans (:97-101)
     for (int i = 0; i < 3; ++i) t_last_curr[i] = c->h_st.p->x[4 + i];
@@ -864,14 +820,6 @@ extern "C" int scal_odom_adapter_begin(scal_odom_t* c, const float* sharp, int n
     *need_solve = c->adapter_solve ? 1 : 0;
     c->adapter_active = true;
     c->outer_next = 0;
-    return SCAL_OK;
-}
-
-static int odom_set_pose(scal_odom* c, const double* q, const double* t) {
-    SCAL_HIP(op_stream_synchronize(c->stream));
-    for (int i = 0; i < 4; ++i) c->h_x7.p[i] = q[i];
-    for (int i = 0; i < 3; ++i) c->h_x7.p[4 + i] = t[i];
-    SCAL_HIP(op_memcpy_async(c->d_st.p->x, c->h_x7.p, sizeof(double) * 7, hipMemcpyHostToDevice, c->stream));
     return SCAL_OK;
 }
 
@@ -887,17 +835,15 @@ extern "C" int scal_odom_associate(scal_odom_t* c, const double* q_last_curr, co
     SCAL_HIP(hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
     OdomCounters* C = c->d_C.p;
-    LMState* st = c->d_st.p;
-    FactorSoA F = c->factors();
-    SCAL_TRY(odom_set_pose(c, q_last_curr, t_last_curr));
-    SCAL_LAUNCH("k_odom_assoc", k_odom_assoc, dim3(std::max(1, c->slot_cap)), dim3(256), 0, s, c->sharp.cv(), c->flat.cv(), c->corner_last.cv(),
+    LMState* st = c->lm.d_st.p;
+    FactorSoA F = c->lm.factors();
+    SCAL_TRY(c->blocks.set_pose(c->stream, c->lm.d_st.p->x, q_last_curr, t_last_curr));
+    SCAL_LAUNCH("k_odom_assoc", k_odom_assoc, dim3(std::max(1, c->lm.slot_cap)), dim3(256), 0, s, c->sharp.cv(), c->flat.cv(), c->corner_last.cv(),
                      c->surf_last.cv(), st, C, std::min(c->outer_next, 1), F, c->cell_index(0), c->cell_index(1), c->ring_tab.p + c->tab_cur * 4 * RING_TAB);
     c->outer_next++;
-    SCAL_LAUNCH("k_blocks_compact", k_blocks_compact, dim3(1), dim3(1024), 0, s, F, &C->n_slots, c->block_list());
-    SCAL_HIP(hipGetLastError());
-    SCAL_HIP(op_memcpy_async(c->h_counts.p, c->bl_counts.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    SCAL_TRY(c->blocks.compact(s, F, &C->n_slots));
     SCAL_HIP(op_stream_synchronize(s));
-    *n_blocks = c->h_counts.p[0], *n_residuals = c->h_counts.p[1];
+    *n_blocks = c->blocks.n_blocks(), *n_residuals = c->blocks.n_residuals();
     return SCAL_OK;
 }
 
@@ -911,13 +857,7 @@ extern "C" int scal_odom_get_blocks(scal_odom_t* c, scal_block* out, int cap) {
         return SCAL_E_STATE;
     }
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    const int n = std::min(cap, c->h_counts.p[0]);
-    if (n <= 0) return 0;
-    hipStream_t s = c->stream;
-    SCAL_LAUNCH("k_blocks_export", k_blocks_export, dim3(div_up(c->h_counts.p[0], 256)), dim3(256), 0, s, c->factors(), c->block_list(), c->d_blocks.p);
-    SCAL_HIP(op_memcpy_async(out, c->d_blocks.p, sizeof(scal_block) * n, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(op_stream_synchronize(s));
-    return n;
+    return c->blocks.get_blocks(c->stream, c->lm.factors(), out, cap);
 }
 
 extern "C" int scal_odom_eval_blocks(scal_odom_t* c, const double* x7, int want_jac, double* residuals, double* jacobians) {
@@ -930,19 +870,7 @@ extern "C" int scal_odom_eval_blocks(scal_odom_t* c, const double* x7, int want_
         return SCAL_E_STATE;
     }
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    const int nb = c->h_counts.p[0], nr = c->h_counts.p[1];
-    if (nb == 0) return SCAL_OK;
-    hipStream_t s = c->stream;
-    SCAL_HIP(op_stream_synchronize(s));
-    for (int i = 0; i < 7; ++i) c->h_x7.p[i] = x7[i];
-    SCAL_HIP(op_memcpy_async(c->d_x7.p, c->h_x7.p, sizeof(double) * 7, hipMemcpyHostToDevice, s));
-    SCAL_LAUNCH("k_blocks_eval", k_blocks_eval, dim3(div_up(nb, 256)), dim3(256), 0, s, c->factors(), c->block_list(), c->d_x7.p, want_jac ? 1 : 0,
-                     c->d_res.p, c->d_jac.p);
-    SCAL_HIP(hipGetLastError());
-    SCAL_HIP(op_memcpy_async(residuals, c->d_res.p, sizeof(double) * nr, hipMemcpyDeviceToHost, s));
-    if (want_jac) SCAL_HIP(op_memcpy_async(jacobians, c->d_jac.p, sizeof(double) * 7 * nr, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(op_stream_synchronize(s));
-    return SCAL_OK;
+    return c->blocks.eval_blocks(c->stream, c->lm.factors(), x7, want_jac, residuals, jacobians);
 }
 
 extern "C" int scal_odom_adapter_finish(scal_odom_t* c, const double* q_last_curr, const double* t_last_curr, double* q_w_curr, double* t_w_curr) {
@@ -956,7 +884,7 @@ extern "C" int scal_odom_adapter_finish(scal_odom_t* c, const double* q_last_cur
     }
     SCAL_HIP(hipSetDevice(c->cfg.device));
     c->adapter_active = false;
-    SCAL_TRY(odom_set_pose(c, q_last_curr, t_last_curr));  // para_q / para_t of the next scan's initial guess
+    SCAL_TRY(c->blocks.set_pose(c->stream, c->lm.d_st.p->x, q_last_curr, t_last_curr));  // para_q / para_t of the next scan's initial guess
     const int slot = c->next_slot;
     c->next_slot = (c->next_slot + 1) % scal_odom::MAX_STEPS;
     SCAL_TRY(launch_handover(c, slot, c->ev[slot]));

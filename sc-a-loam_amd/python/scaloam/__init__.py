@@ -602,10 +602,39 @@ def merge_candidates(cands, dist_thres):
                 cand=np.array(r.cand_idx[:]), cand_d=np.array(r.cand_keydist[:], np.float32))
 
 
+class _CeresAdapter:
+    """Ceres-adapter mode of stages B and C, between the class's adapter_begin and adapter_finish: per outer iteration
+    associate() at the solver's pose, then blocks() / eval_blocks().  `_prefix` names the context's entry points."""
+
+    def associate(self, q, t):
+        nb, nr = C.c_int(0), C.c_int(0)
+        _check(getattr(lib(), self._prefix + "_associate")(self.h, _p(_f64(q), _f64p), _p(_f64(t), _f64p), C.byref(nb), C.byref(nr)))
+        self._adapter_n = (nb.value, nr.value)
+        return nb.value, nr.value
+
+    def blocks(self, cap=None):
+        """(kind [n], cp [n][3], pa [n][3], pb [n][3]) of the residual blocks of the last associate(), the first `cap` if given"""
+        nb = self._adapter_n[0] if cap is None else cap
+        raw = np.zeros((max(nb, 1), 10), np.float64)
+        n = getattr(lib(), self._prefix + "_get_blocks")(self.h, raw.ctypes.data, nb)
+        if n < 0:
+            _check(n)
+        raw = raw[:n]
+        kind = raw[:, 0].copy().view(np.int32)[::2].copy()
+        return kind, raw[:, 1:4].copy(), raw[:, 4:7].copy(), raw[:, 7:10].copy()
+
+    def eval_blocks(self, x7, want_jac=True):
+        nr = self._adapter_n[1]
+        r, J = np.zeros(max(nr, 1)), np.zeros((max(nr, 1), 7))
+        _check(getattr(lib(), self._prefix + "_eval_blocks")(self.h, _p(_f64(x7), _f64p), 1 if want_jac else 0, _p(r, _f64p), _p(J, _f64p)))
+        return r[:nr], (J[:nr] if want_jac else None)
+
+
 # ---------------------------------------------------------------------------------------------- stage C
-class LaserMapping:
+class LaserMapping(_CeresAdapter):
     """Mirror of the reference's laserMapping node state (mapping_line_resolution / mapping_plane_resolution,
     laserMapping.cpp:915-916) with one process() pass as `process`."""
+    _prefix = "scal_map"
 
     def __init__(self, line_res=0.4, plane_res=0.8, max_scan_points=400000, max_map_points=4000000, device=0):
         self.cfg = MapConfig(line_res, plane_res, max_scan_points, max_map_points, device)
@@ -675,7 +704,7 @@ class LaserMapping:
     def prefetch_features(self, feat):
         _check(lib().scal_map_prefetch_features(self.h, feat.h))
 
-    # ---- Ceres-adapter mode (the caller owns the solver): begin -> per outer iteration associate / blocks / eval -> finish
+    # ---- Ceres-adapter mode (the caller owns the solver): begin -> per outer iteration associate / blocks / eval (_CeresAdapter) -> finish
     def adapter_begin(self, corner_last, surf_last, full_res, q_wodom, t_wodom):
         c = _f32(corner_last).reshape(-1, 4)
         s = _f32(surf_last).reshape(-1, 4)
@@ -685,30 +714,6 @@ class LaserMapping:
         _check(lib().scal_map_adapter_begin(self.h, _p(c, _f32p), c.shape[0], _p(s, _f32p), s.shape[0], _p(f, _f32p), 0 if f is None else f.shape[0],
                                             _p(_f64(q_wodom), _f64p), _p(_f64(t_wodom), _f64p), _p(q, _f64p), _p(t, _f64p)))
         return q, t
-
-    def associate(self, q_w_curr, t_w_curr):
-        nb, nr = C.c_int(0), C.c_int(0)
-        _check(lib().scal_map_associate(self.h, _p(_f64(q_w_curr), _f64p), _p(_f64(t_w_curr), _f64p), C.byref(nb), C.byref(nr)))
-        self._adapter_n = (nb.value, nr.value)
-        return nb.value, nr.value
-
-    def blocks(self):
-        """(kind [n], cp [n][3], pa [n][3], pb [n][3]) of the residual blocks of the last associate()"""
-        nb = self._adapter_n[0]
-        raw = np.zeros((max(nb, 1), 10), np.float64)
-        n = lib().scal_map_get_blocks(self.h, raw.ctypes.data, nb)
-        if n < 0:
-            _check(n)
-        raw = raw[:n]
-        kind = raw[:, 0].copy().view(np.int32)[::2].copy()
-        return kind, raw[:, 1:4].copy(), raw[:, 4:7].copy(), raw[:, 7:10].copy()
-
-    def eval_blocks(self, x7, want_jac=True):
-        nb, nr = self._adapter_n
-        r = np.zeros(max(nr, 1))
-        J = np.zeros((max(nr, 1), 7))
-        _check(lib().scal_map_eval_blocks(self.h, _p(_f64(x7), _f64p), 1 if want_jac else 0, _p(r, _f64p), _p(J, _f64p)))
-        return r[:nr], (J[:nr] if want_jac else None)
 
     def adapter_finish(self, q_w_curr, t_w_curr, want_registered=False):
         f = self._adapter_full
@@ -743,7 +748,9 @@ class LaserMapping:
 
 
 # ---------------------------------------------------------------------------------------------- stage B
-class LaserOdometry:
+class LaserOdometry(_CeresAdapter):
+    _prefix = "scal_odom"
+
     def __init__(self, max_points=400000, device=0):
         self.cfg = OdomConfig(max_points, device)
         self.h = C.c_void_p()
@@ -780,27 +787,6 @@ class LaserOdometry:
         _check(lib().scal_odom_adapter_begin(self.h, _p(a[0], _f32p), a[0].shape[0], _p(a[1], _f32p), a[1].shape[0], _p(a[2], _f32p), a[2].shape[0],
                                              _p(a[3], _f32p), a[3].shape[0], _p(q, _f64p), _p(t, _f64p), C.byref(need)))
         return q, t, bool(need.value)
-
-    def associate(self, q_lc, t_lc):
-        nb, nr = C.c_int(0), C.c_int(0)
-        _check(lib().scal_odom_associate(self.h, _p(_f64(q_lc), _f64p), _p(_f64(t_lc), _f64p), C.byref(nb), C.byref(nr)))
-        self._adapter_n = (nb.value, nr.value)
-        return nb.value, nr.value
-
-    def blocks(self):
-        nb = self._adapter_n[0]
-        raw = np.zeros((max(nb, 1), 10), np.float64)
-        n = lib().scal_odom_get_blocks(self.h, raw.ctypes.data, nb)
-        if n < 0:
-            _check(n)
-        raw = raw[:n]
-        return raw[:, 0].copy().view(np.int32)[::2].copy(), raw[:, 1:4].copy(), raw[:, 4:7].copy(), raw[:, 7:10].copy()
-
-    def eval_blocks(self, x7, want_jac=True):
-        nb, nr = self._adapter_n
-        r, J = np.zeros(max(nr, 1)), np.zeros((max(nr, 1), 7))
-        _check(lib().scal_odom_eval_blocks(self.h, _p(_f64(x7), _f64p), 1 if want_jac else 0, _p(r, _f64p), _p(J, _f64p)))
-        return r[:nr], (J[:nr] if want_jac else None)
 
     def adapter_finish(self, q_lc, t_lc):
         qw, tw = np.zeros(4), np.zeros(3)

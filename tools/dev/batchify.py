@@ -5,7 +5,7 @@ Kept for the record; the transformed sources are what is committed."""
 import re
 import sys
 
-FILES = ["features.hip", "mapping.hip", "odometry.hip", "voxel.hip", "radix_sort.hip", "scancontext.hip", "lm_dev.hpp"]
+FILES = ["features.hip", "mapping.hip", "odometry.hip", "voxel.hip", "radix_sort.hip", "scancontext.hip", "lm_dev.hpp", "lm_host.hpp"]
 OPS = [("hipEventRecord(", "op_event_record("), ("hipStreamWaitEvent(", "op_stream_wait_event("), ("hipMemcpyAsync(", "op_memcpy_async("),
        ("hipMemsetAsync(", "op_memset_async("), ("hipEventSynchronize(", "op_event_synchronize("), ("hipStreamSynchronize(", "op_stream_synchronize("),
        ("hipEventQuery(", "op_event_query(")]
