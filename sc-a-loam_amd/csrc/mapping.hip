@@ -1,24 +1,42 @@
-// Stage C on gfx950: scan-to-map registration.  Replaces process(), /root/reference/src/laserMapping.cpp:310-802,
-// :845-849 (see include/scaloam_hip.h).
+// Stage C on gfx950: scan-to-map registration.  Replaces process() of the reference's src/laserMapping.cpp, :310-802 and
+// :845-849 (see include/scaloam_hip.h); ":NNN" in this file are line numbers of that source.
 //
 // Map layout in HBM.  The reference keeps 21x21x11 cubes of 50 m, each a separate PointCloud (:74-104).  Here each
-// feature class (corner, surf) is ONE SoA array x[] y[] z[] i[] plus a packed absolute cube coordinate per point;
-// the rolling window (:313-508) is index arithmetic on the host (cen offsets), never a copy: points whose cube
-// leaves the window are dropped by the next re-filter pass, which is exactly the slab the reference clears.
+// feature class (corner, surf; index k = 0, 1 in every per-class array below) is ONE SoA array x[] y[] z[] i[] plus a packed
+// absolute cube coordinate per point, double buffered; the rolling window (:313-508) is index arithmetic on the device
+// (k_map_begin: cen offsets in MapState), never a copy: points whose cube leaves the window are dropped by the next
+// re-filter pass, which is exactly the slab the reference clears.
 //
-// Per scan, one stream, one host sync at the end (pose + statistics read-back):
-//   stack downsample (:543-551)        VoxelFilter (voxel.hip) on the incoming corner / surf clouds
-//   submap gather + kd-tree (:510-560) replaced by a 1 m uniform cell grid over the 5x5x3 valid cubes
-//                                      (250x250x150 cells): k_grid_count / k_grid_alloc / k_grid_fill bin the valid
-//                                      map points with atomics; both acceptance gates need the 5th neighbour
-//                                      within 1 m (:585, :653) so the 27 surrounding cells hold every candidate
-//   association (:578-688)             k_assoc_edge / k_assoc_plane: exact 5-NN by f32 (dx^2+dy^2)+dz^2, ties by map
-//                                      index; closed-form largest eigenpair (edge) or pivoted Householder QR
-//                                      (plane) in f64 registers -> residual blocks
-//   solve (:713-721) x2 (:563)         lm_dev.hpp, all on the device
-//   insert + per-cube voxel (:738-802) k_insert_keys -> radix sort by (cube, voxel) -> k_map_reduce; cubes outside
-//                                      the 5x5x3 valid set keep raw points in arrival order, as the reference does
-//   registration (:845-849)            k_transform_cloud
+// One step (= one process() pass), all on the context's stream:
+//   stack downsample (:543-551)        VoxelFilter (voxel.hip) on the incoming corner / surf clouds; for a prefetched step it
+//                                      has run ahead, on the features stream (corner) and the side stream (surf)
+//   submap gather + kd-tree (:510-560) replaced by a 1 m uniform cell grid over the 5x5x3 valid cubes (250x250x150 cells),
+//                                      two sets (one per map buffer parity) that obey a zero invariant.  General path:
+//                                      k_grid_count / k_grid_alloc / k_grid_fill into a compact pool.  Queued chain:
+//                                      fixed slices per cell, built in one launch (k_grid_build) or left in place by the
+//                                      previous step's merge write.  Both acceptance gates need the 5th neighbour within
+//                                      1 m (:585, :653), so the 27 surrounding cells hold every candidate
+//   association (:578-688)             k_assoc_knn: exact 5-NN by f32 (dx^2+dy^2)+dz^2, ties by map index, neighbours to
+//                                      NNBuf.  The fit - closed-form largest eigenpair (edge) or pivoted Householder QR
+//                                      (plane) in f64 registers -> residual blocks - runs inside the solve launch (AssocFit)
+//   solve (:713-721) x2 (:563)         lm_dev.hpp, all on the device; the second solve's launch ends with transformUpdate,
+//                                      the host copy of pose + statistics and the insertion keys (MapPoseDone)
+//   insert + per-cube voxel (:738-802) merge insert (k_merge_okeys / _keys / _lookup / _write) while the window stands, else
+//                                      k_insert_keys -> radix sort by (cube, voxel) -> k_map_heads / k_map_reduce; cubes
+//                                      outside the 5x5x3 valid set keep raw points in arrival order, as the reference does
+//   registration (:845-849)            k_transform_cloud, or extra blocks of the fused k_merge_write
+//   commit                             k_map_end: new map sizes, counters and state to the host
+//
+// The queued chain.  Steps fed from a features context are queued speculatively behind each other, nothing read back.
+// Each publishes two words in its pinned MapResult slot, last and behind a system-scope fence: seq_pose (pose and
+// statistics are in the slot) and seq_done (the insertion is committed).  A case the chain does not cover raises
+// MapState::abort on the device; everything queued behind drains as no-ops and the host redoes the stopped step on
+// the general path (recover()).
+//
+// Where the host waits.  General path (first step, host-array entry points, every redo): synchronously, on ev_pose
+// and ev_done.  Queued chain: an enqueue only looks at seq_done words that are already there (scal_map_set_poll) and
+// waits for an insertion only when MAX_STEPS steps are in the queue; scal_map_collect spins on seq_pose of the oldest
+// uncollected step; scal_map_finish and the exports spin on seq_done.  A stop found at any of these is recovered there.
 #include "common.hpp"
 #include <mutex>
 #include <atomic>
@@ -30,6 +48,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <algorithm>
+#include <deque>
 
 namespace scal {
 
@@ -103,10 +122,8 @@ __device__ __forceinline__ int grid_cell(const MapParams& mp, float x, float y, 
     return cx + GX * (cy + GY * cz);
 }
 
-struct MapCounters;
 __device__ __forceinline__ unsigned long long map_key(const MapParams& mp, float inv_leaf, float x, float y, float z, int pc, MapCounters* C);
-constexpr unsigned long long MAP_NOMERGE_SLOT = 127ull;
-__device__ __forceinline__ bool key_nomerge(unsigned long long k) { return (k >> 27) == MAP_NOMERGE_SLOT; }
+__device__ __forceinline__ bool key_nomerge(unsigned long long k) { return (k >> 27) == MAP_NOMERGE; }
 
 __device__ __forceinline__ bool cube_valid(const MapParams& mp, int packed) {
     int ai, aj, ak;
@@ -930,7 +947,6 @@ constexpr int MERGE_NEW_BLOCKS = MERGE_MAX / 256;
 constexpr int MERGE_WB0 = 256, MERGE_WB1 = 1536;
 constexpr int MERGE_WRITE_GRID = MERGE_WB0 + MERGE_WB1 + 2 * MERGE_NEW_BLOCKS;
 
-static_assert(MAP_NOMERGE_SLOT == MAP_NOMERGE, "one constant");
 
 // Old points: their keys, the sortedness check, the zero invariant of the cell grid.  New points: every sorting block stages ALL
 // new keys of its class in LDS (written by k_map_pose_done), sorts the 512-chunks in registers (one wave each), then ranks the
@@ -1459,7 +1475,6 @@ SCAL_DEFINE_STAMP_READER(scal_debug_stamps_map)
 }  // namespace scal
 
 using namespace scal;
-#include <deque>
 
 // filter voxels (leaf `leaf`, lattice = multiples of the leaf) that can intersect a 1 m cell, per axis
 int voxels_per_cell_axis(float leaf) {
@@ -1479,7 +1494,7 @@ int voxels_per_cell_axis(float leaf) {
 struct MapStep {
     scal_features_t* feat = nullptr;  // null: inputs came from host arrays
     MapPoseIn pose{};
-    int set = 0;          // input set (corner_in / surf_in / stacks / counters)
+    int set = 0;          // input set (scal_map::sets)
     int slot = 0;         // result slot + events
     int par = 0;          // map buffer parity before this step's insertion
     bool prefetched = false, have_full = false, fast = false;
@@ -1491,6 +1506,29 @@ struct MapStep {
     unsigned feat_generation = 0; // run of `feat` this step was enqueued for: a replay must find the same scan in the context
     int n_corner_bound = 0, n_surf_bound = 0;
     int insert_path = 0;
+};
+
+// What a step reads up to its pose, per feature class k (0 corner, 1 surf) as on the device.  MapCounters keeps its named
+// fields: this is the one place that maps k to them.
+struct InputSet {
+    SoAStore in[2], stack[2];     // incoming clouds; after the stack voxel grid
+    DevBuf<MapCounters> C;
+    DevBuf<unsigned> surf_parts;  // per-block bounding boxes of in[1] (written by the prefetch's gather)
+    Event ev_pre;                 // side stream: surf stack ready
+    Event ev_pre_a;               // features stream: corner stack ready
+    int* n_in(int k) const { return k == 0 ? &C.p->n_corner_in : &C.p->n_surf_in; }
+    int* n_stack(int k) const { return k == 0 ? &C.p->n_corner_stack : &C.p->n_surf_stack; }
+};
+
+// fixed-capacity FIFO; the caller checks the capacity before it pushes
+template <class T, int N>
+struct Fifo {
+    T item[N];
+    int n = 0;
+    void push(const T& v) { item[n++] = v; }
+    const T& front() const { return item[0]; }
+    void pop() { std::copy(item + 1, item + n, item), --n; }
+    void clear() { n = 0; }
 };
 
 struct scal_map {
@@ -1508,13 +1546,9 @@ struct scal_map {
         unsigned generation;  // run of `feat` the inputs were taken from
     };
     std::mutex pf_mu;  // prefetches may come from a second host thread
-    Prefetch pf[MAX_PF];
-    int n_pf = 0;
-    Prefetch pf_half[MAX_PF];  // scal_map_prefetch_begin done, scal_map_prefetch_finish still to come (FIFO)
-    int n_half = 0;
+    Fifo<Prefetch, MAX_PF> pf_half;  // scal_map_prefetch_begin done, scal_map_prefetch_finish still to come
+    Fifo<Prefetch, MAX_PF> pf;       // both halves done: waiting for their steps
     int next_set = 0;  // ring allocation of input sets
-    Event ev_pre[NSETS];    // side stream: surf stack ready
-    Event ev_pre_a[NSETS];  // features stream: corner stack ready
     std::deque<MapStep> steps;
     Event ev_pose[NSLOTS], ev_done[NSLOTS];
     int next_slot = 0;
@@ -1537,12 +1571,10 @@ struct scal_map {
     DevBuf<MapState> d_S;
     DevBuf<float> aos;  // upload staging
     DevBuf<float> export_buf;  // map-sized staging of scal_map_export / _export_all (allocated by the first export)
-    SoAStore corner_in2[NSETS], surf_in2[NSETS], corner_stack2[NSETS], surf_stack2[NSETS];
+    InputSet sets[NSETS];
     SoAStore full_in, full_out;
-    SoAStore& corner_in(int st) { return corner_in2[st]; }
-    SoAStore& surf_in(int st) { return surf_in2[st]; }
-    SoAStore& corner_stack(int st) { return corner_stack2[st]; }
-    SoAStore& surf_stack(int st) { return surf_stack2[st]; }
+    float leaf(int k) const { return k == 0 ? cfg.line_res : cfg.plane_res; }  // mapping_line_resolution / mapping_plane_resolution
+    float inv_leaf(int k) const { return 1.0f / leaf(k); }                     // 1/leaf as PCL computes it (f32)
     VoxelFilter vf, vf_side, vf_corner;  // main stream / prefetch (surf, side stream) / prefetch (corner, behind stage A): no shared scratch
     MapStore map[2];  // corner, surf
     GridStore grid[2];
@@ -1567,10 +1599,7 @@ struct scal_map {
     LMStore lm;  // residual-block slots (one per stack point), exchange and state of the solve
     DevBuf<float> nnrec;
     NNBuf nnbuf() { return NNBuf{nnrec.p, lm.slot_cap}; }
-    DevBuf<MapCounters> d_C2[NSETS];
-    DevBuf<unsigned> surf_parts[NSETS];  // per-block bounding boxes of surf_in (written by the prefetch's gather)
-    DevBuf<MapCounters>& d_C(int st) { return d_C2[st]; }
-    DevBuf<int> d_nfull, d_done;
+    DevBuf<int> d_nfull;
     PinBuf<MapCounters> h_C;
     PinBuf<MapState> h_S;
     PinBuf<int> h_misc;
@@ -1600,10 +1629,10 @@ int scal::map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t
     auto A = [&](int r) { if (rc == SCAL_OK) rc = r; };
     const size_t sc = c->scan_cap, mc = c->map_cap;
     A(c->aos.alloc(sc * 4));
-    for (int k = 0; k < scal_map::NSETS; ++k) {
-        A(c->corner_in2[k].alloc(sc)); A(c->surf_in2[k].alloc(sc)); A(c->corner_stack2[k].alloc(sc)); A(c->surf_stack2[k].alloc(sc));
-        A(c->d_C2[k].alloc(1));
-        A(c->surf_parts[k].alloc((size_t)6 * (div_up(c->scan_cap, 256) + 1)));
+    for (InputSet& I : c->sets) {
+        A(I.in[0].alloc(sc)); A(I.in[1].alloc(sc)); A(I.stack[0].alloc(sc)); A(I.stack[1].alloc(sc));
+        A(I.C.alloc(1));
+        A(I.surf_parts.alloc((size_t)6 * (div_up(c->scan_cap, 256) + 1)));
     }
     A(c->full_in.alloc(sc)); A(c->full_out.alloc(sc));
     A(c->vf.init(c->scan_cap));
@@ -1627,7 +1656,7 @@ int scal::map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t
     }
     A(c->lm.alloc(c->scan_cap));
     A(c->nnrec.alloc(16 * sc));
-    A(c->d_S.alloc(1)); A(c->d_nfull.alloc(4)); A(c->d_done.alloc(1));
+    A(c->d_S.alloc(1)); A(c->d_nfull.alloc(4));
     A(c->blocks.alloc(c->scan_cap));
     A(c->h_C.alloc(1)); A(c->h_S.alloc(1)); A(c->h_misc.alloc(4)); A(c->res.alloc(scal_map::NSLOTS));
     // Optional, and therefore LAST (after every mandatory buffer, so that a device where they do not fit still gets a working context
@@ -1637,7 +1666,7 @@ int scal::map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t
     if (rc == SCAL_OK && !(fixed_env && fixed_env[0] == '0')) {
         int cap[2];
         for (int k = 0; k < 2; ++k) {
-            const int a = voxels_per_cell_axis(k == 0 ? c->cfg.line_res : c->cfg.plane_res);
+            const int a = voxels_per_cell_axis(c->leaf(k));
             cap[k] = a * a * a;
         }
         if (cap[0] + cap[1] <= 48) {  // 10.5 GB at the reference's 0.4 / 0.8 m; finer filters keep the three-launch build
@@ -1672,7 +1701,6 @@ int scal::map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t
         // The cell counters obey a zero invariant: every step clears exactly the cells it touched.
         for (int k = 0; k < 4 && rc == SCAL_OK; ++k) rc = c->grid[k & 1].cell[k >> 1].zero(c->stream);
         if (rc == SCAL_OK) rc = c->lm.init(c->stream);
-        if (rc == SCAL_OK) rc = c->d_done.zero(c->stream);
         MapState& H = *c->h_S.p;
         std::memset(&H, 0, sizeof H);
         H.q_wmap_wodom[3] = 1.0;
@@ -1701,30 +1729,24 @@ extern "C" void scal_map_destroy(scal_map_t* c) {
 
 namespace {
 
-// stack downsample (:543-551) of corner_in / surf_in into corner_stack / surf_stack; independent of the pose.  The filters'
-// verdicts land in the counters from inside their last kernels.
-// surf_box_done: the gather has already folded the surf cloud's bounding box into vfs.meta.
+// a pose as this interface passes it: quaternion (x, y, z, w) and translation
+void copy_pose(double* q, double* t, const double* q_from, const double* t_from) {
+    std::copy(q_from, q_from + 4, q);
+    std::copy(t_from, t_from + 3, t);
+}
+
+// stack downsample (:543-551) of class k of input set `st`, in[k] into stack[k]; independent of the pose.  The filter's verdict
+// lands in the counters from inside its last kernel.
+// surf_box_done (surf only): the gather has already stored per-block bounding boxes of the cloud, which stand in for the filter's own pass.
 // Key bits: a stack cloud spans the sensor's range, <= 1024 voxels per axis at the launch files' resolutions -> three radix passes.
-int enqueue_corner_filter(scal_map* c, VoxelFilter& vf, hipStream_t s, int n_corner_bound, int st) {
-    MapCounters* C = c->d_C(st).p;
-    VoxTail tc;
-    tc.err_out = &C->error;
-    const int bits_c = c->cfg.line_res >= 0.35f ? 30 : 40;
-    return vf.run(s, c->corner_in(st).cv(), &C->n_corner_in, n_corner_bound, c->cfg.line_res, bits_c, c->corner_stack(st).v(), &C->n_corner_stack, &tc);
-}
-int enqueue_surf_filter(scal_map* c, VoxelFilter& vf, hipStream_t s, int n_surf_bound, int st, bool surf_box_done) {
-    MapCounters* C = c->d_C(st).p;
-    VoxTail ts;
-    ts.err_out = &C->error;
-    const int bits_s = c->cfg.plane_res >= 0.35f ? 30 : 40;
-    const bool box = surf_box_done && n_surf_bound > 8192;  // the gather stored per-block boxes of the surf cloud
-    return vf.run(s, c->surf_in(st).cv(), &C->n_surf_in, n_surf_bound, c->cfg.plane_res, bits_s, c->surf_stack(st).v(), &C->n_surf_stack, &ts,
-                  box ? c->surf_parts[st].p : nullptr, box ? std::max(1, div_up(n_surf_bound, 256)) : 0);
-}
-int enqueue_stack_filters(scal_map* c, VoxelFilter& vfc, VoxelFilter& vfs, hipStream_t s, int n_corner_bound, int n_surf_bound, int st,
-                          bool surf_box_done) {
-    SCAL_TRY(enqueue_corner_filter(c, vfc, s, n_corner_bound, st));
-    return enqueue_surf_filter(c, vfs, s, n_surf_bound, st, surf_box_done);
+int enqueue_stack_filter(scal_map* c, int k, VoxelFilter& vf, hipStream_t s, int n_bound, int st, bool surf_box_done = false) {
+    InputSet& I = c->sets[st];
+    VoxTail t;
+    t.err_out = &I.C.p->error;
+    const int bits = c->leaf(k) >= 0.35f ? 30 : 40;
+    const bool box = k == 1 && surf_box_done && n_bound > 8192;
+    return vf.run(s, I.in[k].cv(), I.n_in(k), n_bound, c->leaf(k), bits, I.stack[k].v(), I.n_stack(k), &t, box ? I.surf_parts.p : nullptr,
+                  box ? std::max(1, div_up(n_bound, 256)) : 0);
 }
 
 GridArgs grid_args(scal_map* c, int par, bool fixed_pool = false) {
@@ -1734,7 +1756,7 @@ GridArgs grid_args(scal_map* c, int par, bool fixed_pool = false) {
         ga.m[k] = c->map[k].cloud(par);
         ga.cell[k] = G.cell[par].p, ga.rank[k] = G.rank[par].p, ga.g[k] = G.pts(par, fixed_pool);
         ga.okeys[k] = G.okeys[par].p;
-        ga.inv_leaf[k] = 1.0f / (k == 0 ? c->cfg.line_res : c->cfg.plane_res);
+        ga.inv_leaf[k] = c->inv_leaf(k);
     }
     return ga;
 }
@@ -1742,16 +1764,15 @@ GridArgs grid_args(scal_map* c, int par, bool fixed_pool = false) {
 // insert + re-filter (:738-802) by a full stable sort of the pool; general path only: n_map[] = host copy of the map sizes
 int insert_full_sort(scal_map* c, const MapStep& e, const int* n_map) {
     hipStream_t s = c->stream;
-    MapCounters* C = c->d_C(e.set).p;
+    const InputSet& I = c->sets[e.set];
+    MapCounters* C = I.C.p;
     LMState* st = c->lm.d_st.p;
     for (int k = 0; k < 2; ++k) {
         MapStore& M = c->map[k];
         const int n_tot_max = std::min(c->map_cap, n_map[k] + c->scan_cap);
         const int nb = std::max(1, div_up(n_tot_max, 256));
         MapCloud in = M.cloud(e.par), outc = M.cloud(e.par ^ 1);
-        const CSoA4 stack = k == 0 ? c->corner_stack(e.set).cv() : c->surf_stack(e.set).cv();
-        const int* d_ns = k == 0 ? &C->n_corner_stack : &C->n_surf_stack;
-        SCAL_LAUNCH("k_insert_keys", k_insert_keys, dim3(nb), dim3(256), 0, s, in, c->d_S.p, stack, d_ns, st, 1.0f / (k == 0 ? c->cfg.line_res : c->cfg.plane_res),
+        SCAL_LAUNCH("k_insert_keys", k_insert_keys, dim3(nb), dim3(256), 0, s, in, c->d_S.p, I.stack[k].cv(), I.n_stack(k), st, c->inv_leaf(k),
                            c->map_cap, c->keys.p, c->vals.p, C, k);
         SortedPairs sp;
         SCAL_TRY(c->sorter.sort(s, c->keys.p, c->vals.p, &C->n_total[k], n_tot_max, 36, nullptr, &sp));
@@ -1763,18 +1784,31 @@ int insert_full_sort(scal_map* c, const MapStep& e, const int* n_map) {
     return SCAL_OK;
 }
 
+// the step's full-resolution cloud, where the registration reads it: in the features context, or uploaded (also the stand-in of a
+// step without one)
+struct FullCloud {
+    CSoA4 pts;
+    const int* d_n;
+};
+FullCloud full_cloud(scal_map* c, const MapStep& e) {
+    if (!(e.have_full && e.feat)) return FullCloud{c->full_in.cv(), c->d_nfull.p};
+    FeatDeviceView v = features_view(e.feat);
+    return FullCloud{CSoA4{v.x, v.y, v.z, v.i}, &v.P->n_kept};
+}
+
 // merge insert of the step's stack points (k_merge_*): no host-side sizes, stops the chain (MapState::abort) if it cannot be done.
 // fused: registration of the full-resolution cloud, commit and host copy ride in the last launch (see k_merge_write)
 int launch_insert_merge(scal_map* c, const MapStep& e, bool fused = false) {
     hipStream_t s = c->stream;
-    MapCounters* C = c->d_C(e.set).p;
+    const InputSet& I = c->sets[e.set];
+    MapCounters* C = I.C.p;
     MergeArgs a;
     for (int k = 0; k < 2; ++k) {
         MapStore& M = c->map[k];
         a.in[k] = M.cloud(e.par), a.out[k] = M.cloud(e.par ^ 1);
-        a.stack[k] = k == 0 ? c->corner_stack(e.set).cv() : c->surf_stack(e.set).cv();
-        a.d_ns[k] = k == 0 ? &C->n_corner_stack : &C->n_surf_stack;
-        a.inv_leaf[k] = 1.0f / (k == 0 ? c->cfg.line_res : c->cfg.plane_res);
+        a.stack[k] = I.stack[k].cv();
+        a.d_ns[k] = I.n_stack(k);
+        a.inv_leaf[k] = c->inv_leaf(k);
         GridStore& G = c->grid[k];
         a.okeys[k] = G.okeys[e.par].p;
         a.nw[k] = c->merge_new(k);
@@ -1795,21 +1829,32 @@ int launch_insert_merge(scal_map* c, const MapStep& e, bool fused = false) {
     int grid = MERGE_WRITE_GRID;
     if (fused) {
         t.fused = 1, t.seq = e.seq, t.st = c->lm.d_st.p, t.full_out = c->full_out.v(), t.full_cap = c->scan_cap;
-        if (e.have_full && e.feat) {
-            FeatDeviceView v = features_view(e.feat);
-            t.full = CSoA4{v.x, v.y, v.z, v.i}, t.d_nfull = &v.P->n_kept;
-            grid += std::max(1, div_up(c->scan_cap, 256));
-        } else if (e.have_full) {
-            t.full = c->full_in.cv(), t.d_nfull = c->d_nfull.p;
-            grid += std::max(1, div_up(c->scan_cap, 256));
-        } else {
-            t.full = c->full_in.cv(), t.d_nfull = c->d_nfull.p, t.full_cap = 0;
-        }
+        const FullCloud f = full_cloud(c, e);
+        t.full = f.pts, t.d_nfull = f.d_n;
+        if (e.have_full) grid += std::max(1, div_up(c->scan_cap, 256));
+        else t.full_cap = 0;
     }
     SCAL_LAUNCH("k_merge_write", k_merge_write, dim3(grid), dim3(256), 0, s, a, c->d_S.p, C, t);
     SCAL_HIP(hipGetLastError());
     return SCAL_OK;
 }
+
+// the recovery vocabulary: one home for each operation the paths below share
+void launch_grid_clear(scal_map* c, int par) {  // restores the zero invariant of the cell counters of grid set `par`
+    SCAL_LAUNCH("k_grid_clear", k_grid_clear, dim3(GRID_BLOCKS), dim3(256), 0, c->stream, grid_args(c, par), c->d_S.p);
+}
+int clear_abort(scal_map* c) {
+    hipStream_t s = c->stream;
+    SCAL_HIP(op_memset_async(&c->d_S.p->abort, 0, sizeof(int), s));
+    return SCAL_OK;
+}
+void launch_map_end(scal_map* c, const MapStep& e) {
+    SCAL_LAUNCH("k_map_end", k_map_end, dim3(1), dim3(256), 0, c->stream, c->d_S.p, c->sets[e.set].C.p, c->res.p + e.slot, e.seq);
+}
+// what a step's result slot says about a stop of the chain: before its pose stood (nothing of the step stands), or - asked of a
+// step that did not stop there - in its insertion (the pose stands)
+bool stopped_before_pose(const MapResult& R) { return R.S1.abort || R.st.termination == 5; }
+bool stopped_in_insertion(const MapResult& R) { return R.S2.abort != 0; }
 
 // registration of the full-resolution cloud (:845-849), commit of the new map sizes, counters to the host; fires ev_done.
 // registered: the fused merge write of the step's speculative run has registered the cloud already - the features context is not read.
@@ -1817,16 +1862,10 @@ int launch_tail(scal_map* c, const MapStep& e, bool registered = false) {
     hipStream_t s = c->stream;
     if (e.have_full && !registered) {
         const int nb = std::max(1, div_up(c->scan_cap, 256));
-        if (e.feat) {
-            FeatDeviceView v = features_view(e.feat);
-            SCAL_LAUNCH("k_transform_cloud", k_transform_cloud, dim3(nb), dim3(256), 0, s, CSoA4{v.x, v.y, v.z, v.i}, &v.P->n_kept, c->scan_cap, c->lm.d_st.p, c->d_S.p,
-                               c->full_out.v());
-        } else {
-            SCAL_LAUNCH("k_transform_cloud", k_transform_cloud, dim3(nb), dim3(256), 0, s, c->full_in.cv(), c->d_nfull.p, c->scan_cap, c->lm.d_st.p, c->d_S.p,
-                               c->full_out.v());
-        }
+        const FullCloud f = full_cloud(c, e);
+        SCAL_LAUNCH("k_transform_cloud", k_transform_cloud, dim3(nb), dim3(256), 0, s, f.pts, f.d_n, c->scan_cap, c->lm.d_st.p, c->d_S.p, c->full_out.v());
     }
-    SCAL_LAUNCH("k_map_end", k_map_end, dim3(1), dim3(256), 0, s, c->d_S.p, c->d_C(e.set).p, c->res.p + e.slot, e.seq);
+    launch_map_end(c, e);
     SCAL_HIP(hipGetLastError());
     SCAL_HIP(op_event_record(c->ev_done[e.slot], s));
     if (e.feat && !registered) SCAL_TRY(features_note_reader(e.feat, s));  // the registration transform reads the full-resolution cloud last
@@ -1834,14 +1873,14 @@ int launch_tail(scal_map* c, const MapStep& e, bool registered = false) {
 }
 
 MapPoseDone make_pose_done(scal_map* c, const MapStep& e) {
-    MapCounters* C = c->d_C(e.set).p;
+    const InputSet& I = c->sets[e.set];
     MapPoseDone pd;
     pd.active = 1, pd.seq = e.seq;
-    pd.S = c->d_S.p, pd.st = c->lm.d_st.p, pd.C = C, pd.host = c->res.p + e.slot;
+    pd.S = c->d_S.p, pd.st = c->lm.d_st.p, pd.C = I.C.p, pd.host = c->res.p + e.slot;
     for (int k = 0; k < 2; ++k) {
-        pd.nw.stack[k] = k == 0 ? c->corner_stack(e.set).cv() : c->surf_stack(e.set).cv();
-        pd.nw.d_ns[k] = k == 0 ? &C->n_corner_stack : &C->n_surf_stack;
-        pd.nw.inv_leaf[k] = 1.0f / (k == 0 ? c->cfg.line_res : c->cfg.plane_res);
+        pd.nw.stack[k] = I.stack[k].cv();
+        pd.nw.d_ns[k] = I.n_stack(k);
+        pd.nw.inv_leaf[k] = c->inv_leaf(k);
         pd.nw.x[k] = c->mnew[k].x.p, pd.nw.y[k] = c->mnew[k].y.p, pd.nw.z[k] = c->mnew[k].z.p, pd.nw.w[k] = c->mnew[k].w.p;
         pd.nw.cube[k] = c->mcube[k].p, pd.nw.pkey[k] = c->mpkey[k].p;
     }
@@ -1853,26 +1892,30 @@ MapPoseDone make_pose_done(scal_map* c, const MapStep& e) {
 int launch_pose_part(scal_map* c, const MapStep& e, bool prepare_only = false) {
     hipStream_t s = c->stream;
     const int st_ = e.set;
-    MapCounters* C = c->d_C(st_).p;
+    InputSet& I = c->sets[st_];
+    MapCounters* C = I.C.p;
     LMState* st = c->lm.d_st.p;
     MapState* S = c->d_S.p;
     if (e.feat) {
         if (e.prefetched) {
             // inputs gathered and downsampled: the surf cloud on the side stream, the corner cloud behind stage A - the side stream
             // recorded its event behind a wait for the corner filter's (scal_map_prefetch_finish)
-            SCAL_HIP(op_stream_wait_event(s, c->ev_pre[st_], 0));
+            SCAL_HIP(op_stream_wait_event(s, I.ev_pre, 0));
         } else {
             FeatDeviceView v = features_view(e.feat);
             SCAL_TRY(features_wait_done(e.feat, s));
             const int nbc = std::max(1, div_up(e.n_corner_bound, 256));
             SCAL_LAUNCH("k_map_gather", k_map_gather, dim3(nbc + std::max(1, div_up(e.n_surf_bound, 256))), dim3(256), 0, s, v.less_xyzi, &v.P->n_less_sharp,
-                               CSoA4{v.lfx, v.lfy, v.lfz, v.lfi}, &v.P->n_less_flat, c->corner_in(st_).v(), c->surf_in(st_).v(), C, c->scan_cap, nbc,
+                               CSoA4{v.lfx, v.lfy, v.lfz, v.lfi}, &v.P->n_less_flat, I.in[0].v(), I.in[1].v(), C, c->scan_cap, nbc,
                                static_cast<unsigned*>(nullptr));
         }
     }
-    if (!e.prefetched) SCAL_TRY(enqueue_stack_filters(c, c->vf, c->vf, s, e.n_corner_bound, e.n_surf_bound, st_, false));
+    if (!e.prefetched) {
+        SCAL_TRY(enqueue_stack_filter(c, 0, c->vf, s, e.n_corner_bound, st_));
+        SCAL_TRY(enqueue_stack_filter(c, 1, c->vf, s, e.n_surf_bound, st_));
+    }
     MapBeginArgs mb;
-    mb.active = 0, mb.in = e.pose, mb.allow_window_change = e.fast ? 0 : 1, mb.inv_line = 1.0f / c->cfg.line_res, mb.inv_plane = 1.0f / c->cfg.plane_res;
+    mb.active = 0, mb.in = e.pose, mb.allow_window_change = e.fast ? 0 : 1, mb.inv_line = c->inv_leaf(0), mb.inv_plane = c->inv_leaf(1);
     mb.slot_cap = c->lm.slot_cap, mb.prebuilt = e.prebuilt ? 1 : 0, mb.S = S;
     // a queued step whose grid the previous merge write left has no launch between its start and the first neighbour search: the
     // start rides on that launch
@@ -1896,11 +1939,11 @@ int launch_pose_part(scal_map* c, const MapStep& e, bool prepare_only = false) {
     FactorSoA F = c->lm.factors();
     const int assoc_blocks = std::max(1, std::min(3072, div_up(c->lm.slot_cap, 8)));
     MapPoseDone pd = make_pose_done(c, e);
-    const AssocFit fit{c->corner_stack(st_).cv(), c->surf_stack(st_).cv(), c->nnbuf(), C, F};
+    const AssocFit fit{I.stack[0].cv(), I.stack[1].cv(), c->nnbuf(), C, F};
     for (int outer = 0; outer < 2; ++outer) {
         {
             mb.active = (begin_in_knn && outer == 0) ? 1 : 0;
-            SCAL_LAUNCH(mb.active ? "k_assoc_knn.0" : "k_assoc_knn", k_assoc_knn, dim3(assoc_blocks), dim3(256), 0, s, c->corner_stack(st_).cv(), c->surf_stack(st_).cv(), S,
+            SCAL_LAUNCH(mb.active ? "k_assoc_knn.0" : "k_assoc_knn", k_assoc_knn, dim3(assoc_blocks), dim3(256), 0, s, I.stack[0].cv(), I.stack[1].cv(), S,
                              c->grid[0].cell[e.par].p, c->grid[0].pts(e.par, fixed_pool), c->grid[1].cell[e.par].p, c->grid[1].pts(e.par, fixed_pool), st, C, c->nnbuf(), mb);
         }
         // PCA / plane fit of every slot (by the thread that evaluates it), the solve and (second iteration) transformUpdate + the host
@@ -1964,7 +2007,7 @@ bool lm_gave_up(const MapResult& R) { return R.st.termination == 5 || R.S1.abort
 int lm_reset(scal_map* c, bool restore_pose) {
     hipStream_t s = c->stream;
     SCAL_TRY(c->lm.clear_exchange(s));
-    SCAL_HIP(op_memset_async(&c->d_S.p->abort, 0, sizeof(int), s));
+    SCAL_TRY(clear_abort(c));
     if (restore_pose) {
         static_assert(offsetof(MapState, t_wmap_wodom) == offsetof(MapState, q_wmap_wodom) + 4 * sizeof(double), "pose fields are contiguous");
         SCAL_TRY(c->blocks.set_pose(s, c->d_S.p->q_wmap_wodom, c->good_q, c->good_t));
@@ -1978,7 +2021,7 @@ int general_insert(scal_map* c, MapStep& e);
 // Ceres-adapter mode, a changed slice size) first restores the zero invariant of that grid set.  All queued steps have finished.
 int drop_prebuilt_grid(scal_map* c) {
     if (!c->grid_prebuilt) return SCAL_OK;
-    SCAL_LAUNCH("k_grid_clear", k_grid_clear, dim3(GRID_BLOCKS), dim3(256), 0, c->stream, grid_args(c, c->cur), c->d_S.p);
+    launch_grid_clear(c, c->cur);
     SCAL_HIP(hipGetLastError());
     c->grid_prebuilt = false;
     return SCAL_OK;
@@ -2001,7 +2044,7 @@ int run_general(scal_map* c, MapStep& e) {
     for (int attempt = 0; rc == MAP_RC_LM; ++attempt) {
         SCAL_TRY(lm_reset(c, true));
         // a full cell grid was left behind by the stopped pose part: restore the zero invariant before the grid is built again
-        SCAL_LAUNCH("k_grid_clear", k_grid_clear, dim3(GRID_BLOCKS), dim3(256), 0, c->stream, grid_args(c, e.par), c->d_S.p);
+        launch_grid_clear(c, e.par);
         if (attempt == 1) {
             SCAL_HIP(op_stream_synchronize(c->stream));
             e.failed = true;
@@ -2013,6 +2056,22 @@ int run_general(scal_map* c, MapStep& e) {
     return rc;
 }
 
+// The synchronous end of a step whose pose stands: the insertion by the full sort (n_map_before[] = host copy of the map sizes before
+// it; null: the merge insert has done it), the tail, the wait for it, and the map buffers change parity.
+// registered: see launch_tail.
+int finish_step_sync(scal_map* c, MapStep& e, const int* n_map_before, bool registered) {
+    if (n_map_before) {
+        e.insert_path = 0;
+        SCAL_TRY(insert_full_sort(c, e, n_map_before));
+    }
+    SCAL_TRY(launch_tail(c, e, registered));
+    SCAL_HIP(op_event_synchronize(c->ev_done[e.slot]));
+    const MapResult& R = c->res.p[e.slot];
+    if (R.C2.error) return report_device_error(c, R.C2.error);
+    c->cur = e.par ^ 1;
+    return SCAL_OK;
+}
+
 // second half of the general path: the pose stands (slot S1 / C1 published), insertion + registration + commit, synchronous
 int general_insert(scal_map* c, MapStep& e) {
     hipStream_t s = c->stream;
@@ -2020,30 +2079,22 @@ int general_insert(scal_map* c, MapStep& e) {
     if (R.C1.error) return report_device_error(c, R.C1.error);
     const int n_map[2] = {R.S1.n_map[0], R.S1.n_map[1]};
     bool try_merge = c->merge_insert && R.S1.window_same && n_map[0] + MERGE_MAX <= c->map_cap && n_map[1] + MERGE_MAX <= c->map_cap;
-    MapCounters* C = c->d_C(e.set).p;
     e.insert_path = 1;
     if (try_merge) {
         SCAL_TRY(launch_insert_merge(c, e));
-        SCAL_LAUNCH("k_map_end", k_map_end, dim3(1), dim3(256), 0, s, c->d_S.p, C, c->res.p + e.slot, e.seq);
+        launch_map_end(c, e);
         SCAL_HIP(op_stream_synchronize(s));
-        if (R.S2.abort) {  // a case the merge does not cover: redo with the full sort
-            SCAL_HIP(op_memset_async(&c->d_S.p->abort, 0, sizeof(int), s));
+        if (stopped_in_insertion(R)) {  // a case the merge does not cover: redo with the full sort
+            SCAL_TRY(clear_abort(c));
             try_merge = false;
         } else if (R.C2.error) {
             return report_device_error(c, R.C2.error);
         }
     } else {
         // restore the zero invariant of the cell counters (the merge insert does it in its key kernel)
-        SCAL_LAUNCH("k_grid_clear", k_grid_clear, dim3(GRID_BLOCKS), dim3(256), 0, s, grid_args(c, e.par), c->d_S.p);
+        launch_grid_clear(c, e.par);
     }
-    if (!try_merge) {
-        e.insert_path = 0;
-        SCAL_TRY(insert_full_sort(c, e, n_map));
-    }
-    SCAL_TRY(launch_tail(c, e));
-    SCAL_HIP(op_event_synchronize(c->ev_done[e.slot]));
-    if (R.C2.error) return report_device_error(c, R.C2.error);
-    c->cur = e.par ^ 1;
+    SCAL_TRY(finish_step_sync(c, e, try_merge ? nullptr : n_map, false));
     c->initialised = true;
     return SCAL_OK;
 }
@@ -2058,7 +2109,7 @@ int launch_fast(scal_map* c, MapStep& e) {
     c->n_fast++;
     SCAL_TRY(launch_pose_part(c, e));
     SCAL_TRY(launch_insert_merge(c, e, true));
-    SCAL_LAUNCH("k_map_end", k_map_end, dim3(1), dim3(256), 0, c->stream, c->d_S.p, c->d_C(e.set).p, c->res.p + e.slot, e.seq);
+    launch_map_end(c, e);
     SCAL_HIP(hipGetLastError());
     if (e.feat) SCAL_TRY(features_note_reader(e.feat, c->stream));  // the registration transform reads the full-resolution cloud last
     c->cur = e.par ^ 1;
@@ -2069,8 +2120,7 @@ int launch_fast(scal_map* c, MapStep& e) {
 void confirm(scal_map* c, MapStep& e) {
     const MapResult& R = c->res.p[e.slot];
     for (int k = 0; k < 2; ++k) c->map[k].n = R.S2.n_map[k];
-    for (int i = 0; i < 4; ++i) c->good_q[i] = R.S1.q_wmap_wodom[i];
-    for (int i = 0; i < 3; ++i) c->good_t[i] = R.S1.t_wmap_wodom[i];
+    copy_pose(c->good_q, c->good_t, R.S1.q_wmap_wodom, R.S1.t_wmap_wodom);
     c->last_insert_path = e.insert_path;
     e.confirmed = true;
 }
@@ -2088,74 +2138,74 @@ void pop_done(scal_map* c) {
     while (!c->steps.empty() && c->steps.front().confirmed && c->steps.front().pose_collected) c->steps.pop_front();
 }
 
+void trace_stop(const MapResult& R) {  // SCALOAM_PIPE_TIMING: the first few stops of the chain, to stderr
+    static const bool trace = std::getenv("SCALOAM_PIPE_TIMING") != nullptr;
+    static int shown = 0;
+    if (!trace || shown >= 12) return;
+    std::fprintf(stderr, "[scal_map] chain stopped: S1.abort %d S2.abort %d termination %d merge_fail %d neff %d/%d n_map %d/%d stack %d/%d window_same %d\n",
+                 R.S1.abort, R.S2.abort, R.st.termination, R.C2.merge_fail, R.C2.merge_neff[0], R.C2.merge_neff[1], R.S2.n_map[0], R.S2.n_map[1],
+                 R.C2.n_corner_stack, R.C2.n_surf_stack, R.S2.window_same);
+    ++shown;
+}
+
 // The speculative chain stopped on the device.  Everything queued has drained as no-ops behind the stop; the step that raised the
 // flag is redone on the general path (from its start, or only its insertion), the steps behind it are queued again.
 int recover(scal_map* c) {
     hipStream_t s = c->stream;
     SCAL_HIP(op_stream_synchronize(s));
-    size_t origin = c->steps.size();
-    bool at_pose = false;
-    for (size_t i = 0; i < c->steps.size(); ++i) {
-        MapStep& e = c->steps[i];
-        if (e.confirmed) continue;
-        const MapResult& R = c->res.p[e.slot];
-        if (R.S1.abort || R.st.termination == 5) { origin = i, at_pose = true; break; }
-        if (R.S2.abort) { origin = i, at_pose = false; break; }
-        if (R.C2.error) return report_device_error(c, R.C2.error);
-        confirm(c, e);  // in front of the stop: completed
+    // find the stop: the first unconfirmed step whose slot reports one
+    size_t origin = 0;
+    for (; origin < c->steps.size(); ++origin) {
+        MapStep& f = c->steps[origin];
+        if (f.confirmed) continue;
+        const MapResult& Rf = c->res.p[f.slot];
+        if (stopped_before_pose(Rf) || stopped_in_insertion(Rf)) break;
+        if (Rf.C2.error) return report_device_error(c, Rf.C2.error);
+        confirm(c, f);  // in front of the stop: completed
     }
     if (origin == c->steps.size()) return SCAL_OK;  // nothing stopped
     MapStep& e = c->steps[origin];
-    {
-        static const bool trace = std::getenv("SCALOAM_PIPE_TIMING") != nullptr;
-        static int shown = 0;
-        if (trace && shown < 12) {
-            const MapResult& R = c->res.p[e.slot];
-            std::fprintf(stderr, "[scal_map] chain stopped: S1.abort %d S2.abort %d termination %d merge_fail %d neff %d/%d n_map %d/%d stack %d/%d window_same %d\n",
-                         R.S1.abort, R.S2.abort, R.st.termination, R.C2.merge_fail, R.C2.merge_neff[0], R.C2.merge_neff[1], R.S2.n_map[0], R.S2.n_map[1],
-                         R.C2.n_corner_stack, R.C2.n_surf_stack, R.S2.window_same);
-            ++shown;
-        }
-    }
+    const MapResult& R = c->res.p[e.slot];
+    trace_stop(R);
+    // reset to its parity
     c->cur = e.par;
     c->grid_prebuilt = false;  // whatever is redone below ends with both grid sets empty
+    // redo: from the pose, or the insertion only
     bool dropped = false;
-    if (at_pose) {
+    if (stopped_before_pose(R)) {
         c->n_recover_pose++;
-        const MapResult& R0 = c->res.p[e.slot];
-        const bool lm = lm_gave_up(R0);
+        const bool lm = lm_gave_up(R);
         if (lm) SCAL_TRY(lm_reset(c, true));  // clears the abort word too
-        else SCAL_HIP(op_memset_async(&c->d_S.p->abort, 0, sizeof(int), s));
+        else SCAL_TRY(clear_abort(c));
         // the grid of this step exists - built by its own k_grid_build (unless the window check stopped the chain before it) or left
         // by the previous step's merge write - and the kernel that clears its counters never ran.  MapState::mp is still the window
         // it was built under: a stopped k_map_begin does not store the new one.
-        if (lm || R0.S1.abort == MAP_ABORT_GRID || e.prebuilt)
-            SCAL_LAUNCH("k_grid_clear", k_grid_clear, dim3(GRID_BLOCKS), dim3(256), 0, s, grid_args(c, e.par), c->d_S.p);
+        if (lm || R.S1.abort == MAP_ABORT_GRID || e.prebuilt) launch_grid_clear(c, e.par);
         SCAL_TRY(check_generation(e, !e.prefetched));
         const int rc = run_general(c, e);
         if (rc != SCAL_OK && !e.failed) return rc;
         dropped = e.failed;  // abandoned again: the scan is dropped, the caller gets SCAL_E_HIP from collect
     } else {
         c->n_recover_insert++;  // the pose of this step stands; only its insertion is redone, with the full sort
-        if (c->res.p[e.slot].S2.abort == MAP_ABORT_LM) SCAL_TRY(lm_reset(c, false));  // a workgroup gave up in the last round, after workgroup 0 had finished
-        else SCAL_HIP(op_memset_async(&c->d_S.p->abort, 0, sizeof(int), s));
-        if (c->res.p[e.slot].S2.abort == MAP_ABORT_LM)
-            SCAL_LAUNCH("k_grid_clear", k_grid_clear, dim3(GRID_BLOCKS), dim3(256), 0, s, grid_args(c, e.par), c->d_S.p);
-        const MapResult& R = c->res.p[e.slot];
+        const bool lm = R.S2.abort == MAP_ABORT_LM;  // a workgroup gave up in the last round, after workgroup 0 had finished
+        if (lm) {
+            SCAL_TRY(lm_reset(c, false));
+            launch_grid_clear(c, e.par);
+        } else {
+            SCAL_TRY(clear_abort(c));
+        }
         // the pose was out before the stop, so the caller may have collected it and run the features context again: the stopped
         // merge write has registered the full-resolution cloud already, and the redo reads only the stacks of its own input set
         const bool registered = R.S2.pose_seq == e.seq;
         if (!registered) SCAL_TRY(check_generation(e, false));
         const int n_map[2] = {R.S2.n_map[0], R.S2.n_map[1]};  // not committed: still the sizes before the insertion
-        e.fast = false, e.insert_path = 0;
-        SCAL_TRY(insert_full_sort(c, e, n_map));
-        SCAL_TRY(launch_tail(c, e, registered));
-        SCAL_HIP(op_event_synchronize(c->ev_done[e.slot]));
-        if (R.C2.error) return report_device_error(c, R.C2.error);
-        c->cur = e.par ^ 1;
+        e.fast = false;
+        SCAL_TRY(finish_step_sync(c, e, n_map, registered));
     }
+    // confirm or drop
     if (dropped) e.confirmed = true;  // nothing to confirm: map sizes and the last good correction stay as they were
     else confirm(c, e);
+    // replay the rest
     for (size_t i = origin + 1; i < c->steps.size(); ++i) {
         SCAL_TRY(check_generation(c->steps[i], !c->steps[i].prefetched));
         SCAL_TRY(launch_fast(c, c->steps[i]));
@@ -2167,14 +2217,13 @@ int recover(scal_map* c) {
 int confirm_steps(scal_map* c, bool wait) {
     for (size_t i = 0; i < c->steps.size(); ++i) {
         if (c->steps[i].confirmed) continue;
-        const int slot = c->steps[i].slot;
         if (wait) {
             SCAL_TRY(wait_done(c, c->steps[i]));
         } else if (!done_ready(c, c->steps[i])) {
             break;
         }
-        const MapResult& R = c->res.p[slot];
-        if (R.S1.abort || R.S2.abort || R.st.termination == 5) {
+        const MapResult& R = c->res.p[c->steps[i].slot];
+        if (stopped_before_pose(R) || stopped_in_insertion(R)) {
             SCAL_TRY(recover(c));  // confirms at least this step
             if (!c->steps[i].confirmed) {
                 set_error("scal_map: internal error (recovery did not complete the stopped step)");
@@ -2182,44 +2231,44 @@ int confirm_steps(scal_map* c, bool wait) {
             }
             continue;
         }
-        if (R.C2.error) {
-            confirm(c, c->steps[i]);
-            return report_device_error(c, R.C2.error);
-        }
         confirm(c, c->steps[i]);
+        if (R.C2.error) return report_device_error(c, R.C2.error);
     }
     return SCAL_OK;
 }
-int map_finish(scal_map* c) {
-    SCAL_TRY(confirm_steps(c, true));
-    pop_done(c);
-    return SCAL_OK;
-}
-int map_poll(scal_map* c) {
-    SCAL_TRY(confirm_steps(c, false));
+// confirm_steps, and the steps that are confirmed and collected leave the queue (scal_map_finish: wait = true)
+int map_settle(scal_map* c, bool wait) {
+    SCAL_TRY(confirm_steps(c, wait));
     pop_done(c);
     return SCAL_OK;
 }
 // room for one more step: MAX_STEPS bounds the steps whose pose has not been collected; collected ones whose insertion is still
 // running are waited for here
 int map_make_room(scal_map* c) {
-    if (c->poll_on_enqueue) SCAL_TRY(map_poll(c));
+    if (c->poll_on_enqueue) SCAL_TRY(map_settle(c, false));
     while (static_cast<int>(c->steps.size()) >= scal_map::MAX_STEPS) {
         if (!c->steps.front().pose_collected) {
             set_error("scal_map: %d steps are queued and not collected", scal_map::MAX_STEPS);
             return SCAL_E_STATE;
         }
         SCAL_TRY(wait_done(c, c->steps.front()));
-        SCAL_TRY(map_poll(c));
+        SCAL_TRY(map_settle(c, false));
     }
     return SCAL_OK;
 }
 
-int new_step(scal_map* c, MapStep* out) {
+MapStep new_step(scal_map* c) {
     MapStep e;
     e.slot = c->next_slot;
     c->next_slot = (c->next_slot + 1) % scal_map::NSLOTS;
-    *out = e;
+    return e;
+}
+
+// a step on the general path, synchronous: when this returns it is in the queue with its insertion confirmed, its pose to be collected
+int run_general_and_confirm(scal_map* c, MapStep& e) {
+    SCAL_TRY(run_general(c, e));
+    c->steps.push_back(e);
+    confirm(c, c->steps.back());
     return SCAL_OK;
 }
 
@@ -2234,11 +2283,22 @@ int map_enqueue(scal_map* c, MapStep& e) {
         c->steps.push_back(e);
         return SCAL_OK;
     }
-    SCAL_TRY(map_finish(c));
-    SCAL_TRY(run_general(c, e));
-    c->steps.push_back(e);
-    confirm(c, c->steps.back());
-    return SCAL_OK;
+    SCAL_TRY(map_settle(c, true));
+    return run_general_and_confirm(c, e);
+}
+
+// a fresh scal_map_stats with what the counters at the pose (MapResult::C1) hold
+void stats_at_pose(const MapCounters& H, scal_map_stats* stats) {
+    std::memset(stats, 0, sizeof *stats);
+    stats->n_corner_stack = H.n_corner_stack, stats->n_surf_stack = H.n_surf_stack;
+    stats->n_corner_map = H.n_valid[0], stats->n_surf_map = H.n_valid[1];
+    stats->solved = H.solve_on;
+}
+
+// the host mirrors of the map <- odometry correction follow the step whose pose the caller now has
+void publish_correction(scal_map* c, const MapState& S1) {
+    copy_pose(c->q_wmap_wodom, c->t_wmap_wodom, S1.q_wmap_wodom, S1.t_wmap_wodom);
+    c->have_mp = true;
 }
 
 // waits for the pose of the oldest uncollected step; map sizes in `stats` are those before this step's insertion (insert_path = -1)
@@ -2256,7 +2316,7 @@ int map_collect_pose(scal_map* c, double* q_out, double* t_out, scal_map_stats* 
     const int slot = pe->slot;
     for (int round = 0;; ++round) {
         SCAL_TRY(wait_pose(c, *pe));
-        if (pe->failed || (!c->res.p[slot].S1.abort && c->res.p[slot].st.termination != 5)) break;
+        if (pe->failed || !stopped_before_pose(c->res.p[slot])) break;
         if (round > scal_map::MAX_STEPS + 1) {
             set_error("scal_map_collect: internal error (recovery does not converge)");
             return SCAL_E_STATE;
@@ -2272,23 +2332,16 @@ int map_collect_pose(scal_map* c, double* q_out, double* t_out, scal_map_stats* 
         return SCAL_E_HIP;
     }
     if (H.error) return report_device_error(c, H.error);
-    const double* xf = R.st.x;
-    for (int i = 0; i < 4; ++i) q_out[i] = xf[i];
-    for (int i = 0; i < 3; ++i) t_out[i] = xf[4 + i];
-    for (int i = 0; i < 4; ++i) c->q_wmap_wodom[i] = R.S1.q_wmap_wodom[i];
-    for (int i = 0; i < 3; ++i) c->t_wmap_wodom[i] = R.S1.t_wmap_wodom[i];
-    c->have_mp = true;
+    copy_pose(q_out, t_out, R.st.x, R.st.x + 4);
+    publish_correction(c, R.S1);
     if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->n_corner_stack = H.n_corner_stack, stats->n_surf_stack = H.n_surf_stack;
-        stats->n_corner_map = H.n_valid[0], stats->n_surf_map = H.n_valid[1];
+        stats_at_pose(H, stats);
         for (int o = 0; o < 2; ++o) {
             const LMState& L = R.st;
             stats->n_edge[o] = H.solve_on ? L.log_n_edge[o] : 0, stats->n_plane[o] = H.solve_on ? L.log_n_plane[o] : 0;
             stats->lm_iters[o] = H.solve_on ? L.log_iters[o] : 0, stats->lm_success[o] = H.solve_on ? L.log_success[o] : 0;
             stats->cost_init[o] = H.solve_on ? L.log_cost_init[o] : 0.0, stats->cost_final[o] = H.solve_on ? L.log_cost_final[o] : 0.0;
         }
-        stats->solved = H.solve_on;
         stats->n_map_corner_total = R.S1.n_map[0], stats->n_map_surf_total = R.S1.n_map[1];
         stats->insert_path = -1;
     }
@@ -2296,42 +2349,52 @@ int map_collect_pose(scal_map* c, double* q_out, double* t_out, scal_map_stats* 
     return SCAL_OK;
 }
 
-}  // namespace
-
-extern "C" int scal_map_step(scal_map_t* c, const float* corner_last, int n_corner, const float* surf_last, int n_surf, const float* full_res,
-                             int n_full, const double* q_wodom, const double* t_wodom, double* q_w_curr, double* t_w_curr, float* registered,
-                             scal_map_stats* stats) {
+// ---- the host-array entry points (scal_map_step, scal_map_adapter_begin / _finish)
+// `fn`: the public function, for the error text
+int check_host_arrays(const char* fn, const scal_map* c, const float* corner_last, int n_corner, const float* surf_last, int n_surf, int n_full,
+                      const double* q_wodom, const double* t_wodom, const double* q_w_curr, const double* t_w_curr) {
     if (!c || !q_wodom || !t_wodom || !q_w_curr || !t_w_curr || n_corner < 0 || n_surf < 0 || n_full < 0 || (n_corner > 0 && !corner_last) ||
         (n_surf > 0 && !surf_last)) {
-        set_error("scal_map_step: bad argument");
+        set_error("%s: bad argument", fn);
         return SCAL_E_ARG;
     }
     if (n_corner > c->scan_cap || n_surf > c->scan_cap || n_full > c->scan_cap) {
-        set_error("scal_map_step: input cloud larger than max_scan_points (%d)", c->scan_cap);
+        set_error("%s: input cloud larger than max_scan_points (%d)", fn, c->scan_cap);
         return SCAL_E_TOO_MANY;
     }
+    return SCAL_OK;
+}
+
+void drop_prefetches(scal_map* c) { c->pf.clear(), c->pf_half.clear(); }  // pf_mu held
+
+// Start of a synchronous entry point: nothing may be in flight and no step open (`open_text`: the caller's error text for that;
+// adapter_counts: a begun Ceres-adapter step is an open step too).  Queued prefetches belong to a features context - not used by
+// these entry points - and are dropped; the new step takes a fresh set.
+int begin_sync_step(scal_map* c, bool adapter_counts, const char* open_text, MapStep* e) {
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    hipStream_t s = c->stream;
-    const bool have_full = full_res != nullptr && n_full > 0;
-    SCAL_TRY(map_finish(c));  // synchronous entry point: nothing may be in flight
-    if (!c->steps.empty()) {
-        set_error("scal_map_step: a queued step has not been collected");
+    SCAL_TRY(map_settle(c, true));
+    if (!c->steps.empty() || (adapter_counts && c->adapter_active)) {
+        set_error("%s", open_text);
         return SCAL_E_STATE;
     }
-    MapStep e;
-    SCAL_TRY(new_step(c, &e));
-    {
-        std::lock_guard<std::mutex> lk(c->pf_mu);
-        c->n_pf = 0, c->n_half = 0;  // queued prefetches belong to a features context: not used by this entry point
-        e.set = c->alloc_set();
-    }
-    // per-scan counters and inputs, staged through pinned memory
+    *e = new_step(c);
+    std::lock_guard<std::mutex> lk(c->pf_mu);
+    drop_prefetches(c);
+    e->set = c->alloc_set();
+    return SCAL_OK;
+}
+
+// per-scan counters and inputs, staged through pinned memory; n_full = 0: no full-resolution cloud
+int upload_step_inputs(scal_map* c, MapStep& e, const float* corner_last, int n_corner, const float* surf_last, int n_surf, const float* full_res,
+                       int n_full) {
+    hipStream_t s = c->stream;
+    InputSet& I = c->sets[e.set];
     MapCounters z;
     std::memset(&z, 0, sizeof z);
     z.n_corner_in = n_corner, z.n_surf_in = n_surf;
     *c->h_C.p = z;
-    SCAL_HIP(op_memcpy_async(c->d_C(e.set).p, c->h_C.p, sizeof(MapCounters), hipMemcpyHostToDevice, s));
-    c->h_misc.p[0] = have_full ? n_full : 0;
+    SCAL_HIP(op_memcpy_async(I.C.p, c->h_C.p, sizeof(MapCounters), hipMemcpyHostToDevice, s));
+    c->h_misc.p[0] = n_full;
     SCAL_HIP(op_memcpy_async(c->d_nfull.p, c->h_misc.p, sizeof(int), hipMemcpyHostToDevice, s));
     auto up = [&](const float* src, int n, SoAStore& dst) -> int {
         if (n > 0) {
@@ -2341,28 +2404,59 @@ extern "C" int scal_map_step(scal_map_t* c, const float* corner_last, int n_corn
         }
         return SCAL_OK;
     };
-    SCAL_TRY(up(corner_last, n_corner, c->corner_in(e.set)));
-    SCAL_TRY(up(surf_last, n_surf, c->surf_in(e.set)));
-    if (have_full) SCAL_TRY(up(full_res, n_full, c->full_in));
-    for (int i = 0; i < 4; ++i) e.pose.q_wodom[i] = q_wodom[i];
-    for (int i = 0; i < 3; ++i) e.pose.t_wodom[i] = t_wodom[i];
-    e.have_full = have_full, e.n_corner_bound = n_corner, e.n_surf_bound = n_surf;
-    SCAL_TRY(run_general(c, e));
-    c->steps.push_back(e);
-    confirm(c, c->steps.back());
+    SCAL_TRY(up(corner_last, n_corner, I.in[0]));
+    SCAL_TRY(up(surf_last, n_surf, I.in[1]));
+    if (n_full > 0) SCAL_TRY(up(full_res, n_full, c->full_in));
+    e.have_full = n_full > 0, e.n_corner_bound = n_corner, e.n_surf_bound = n_surf;
+    return SCAL_OK;
+}
+
+// the registered full-resolution cloud (n_full points, as uploaded) to the caller's array
+int download_registered(scal_map* c, float* registered, int n_full) {
+    hipStream_t s = c->stream;
+    launch_interleave(s, c->d_nfull.p, n_full, c->full_out.cv(), c->aos.p);
+    (void)c->hs_reg.reserve((size_t)c->scan_cap * 16 + 4096);
+    SCAL_HIP(c->hs_reg.d2h(registered, c->aos.p, sizeof(float) * 4 * n_full, s));
+    SCAL_HIP(op_stream_synchronize(s));
+    c->hs_reg.finish();
+    return SCAL_OK;
+}
+
+// statistics that are known once the insertion is confirmed (map_collect_pose leaves the sizes before it, and insert_path = -1)
+void stats_after_insertion(const scal_map* c, scal_map_stats* stats) {
+    if (!stats) return;
+    stats->n_map_corner_total = c->map[0].n, stats->n_map_surf_total = c->map[1].n;
+    stats->insert_path = c->last_insert_path;
+}
+
+int need_adapter_step(const scal_map* c, const char* fn) {
+    if (c->adapter_active) return SCAL_OK;
+    set_error("%s: no scal_map_adapter_begin", fn);
+    return SCAL_E_STATE;
+}
+
+int check_features_device(const scal_map* c, const FeatDeviceView& v) {
+    if (v.device == c->cfg.device) return SCAL_OK;
+    set_error("features context lives on device %d, map context on %d", v.device, c->cfg.device);
+    return SCAL_E_ARG;
+}
+
+}  // namespace
+
+extern "C" int scal_map_step(scal_map_t* c, const float* corner_last, int n_corner, const float* surf_last, int n_surf, const float* full_res,
+                             int n_full, const double* q_wodom, const double* t_wodom, double* q_w_curr, double* t_w_curr, float* registered,
+                             scal_map_stats* stats) {
+    SCAL_TRY(check_host_arrays("scal_map_step", c, corner_last, n_corner, surf_last, n_surf, n_full, q_wodom, t_wodom, q_w_curr, t_w_curr));
+    const bool have_full = full_res != nullptr && n_full > 0;
+    MapStep e;
+    SCAL_TRY(begin_sync_step(c, false, "scal_map_step: a queued step has not been collected", &e));
+    SCAL_TRY(upload_step_inputs(c, e, corner_last, n_corner, surf_last, n_surf, full_res, have_full ? n_full : 0));
+    copy_pose(e.pose.q_wodom, e.pose.t_wodom, q_wodom, t_wodom);
+    SCAL_TRY(run_general_and_confirm(c, e));
     SCAL_TRY(map_collect_pose(c, q_w_curr, t_w_curr, stats));
-    SCAL_TRY(map_finish(c));
-    if (stats) {
-        stats->n_map_corner_total = c->map[0].n, stats->n_map_surf_total = c->map[1].n;
-        stats->insert_path = c->last_insert_path;
-    }
-    if (have_full && registered) {
-        launch_interleave(s, c->d_nfull.p, n_full, c->full_out.cv(), c->aos.p);
-        (void)c->hs_reg.reserve((size_t)c->scan_cap * 16 + 4096);
-        SCAL_HIP(c->hs_reg.d2h(registered, c->aos.p, sizeof(float) * 4 * n_full, s));
-        SCAL_HIP(op_stream_synchronize(s));
-        c->hs_reg.finish();
-    }
+    SCAL_TRY(map_settle(c, true));
+    stats_after_insertion(c, stats);
+    if (have_full && registered) SCAL_TRY(download_registered(c, registered, n_full));
     return SCAL_OK;
 }
 
@@ -2374,34 +2468,30 @@ extern "C" int scal_map_prefetch_begin(scal_map_t* c, scal_features_t* feat) {
         return SCAL_E_ARG;
     }
     FeatDeviceView v = features_view(feat);
-    if (v.device != c->cfg.device) {
-        set_error("features context lives on device %d, map context on %d", v.device, c->cfg.device);
-        return SCAL_E_ARG;
-    }
+    SCAL_TRY(check_features_device(c, v));
     SCAL_HIP(hipSetDevice(c->cfg.device));
     const int ls_cap = std::min(c->scan_cap, v.n_scans * 120);
     const int cap = std::min(c->scan_cap, v.cap);
     std::lock_guard<std::mutex> lk(c->pf_mu);
-    if (c->n_pf + c->n_half >= scal_map::MAX_PF) {
+    if (c->pf.n + c->pf_half.n >= scal_map::MAX_PF) {
         set_error("scal_map_prefetch_features: %d prefetches are already queued ahead of their steps", scal_map::MAX_PF);
         return SCAL_E_STATE;
     }
     const int nset = c->alloc_set();
-    SCAL_TRY(c->ev_pre[nset].ensure(EV_DEVICE_ONLY));
-    SCAL_TRY(c->ev_pre_a[nset].ensure(EV_DEVICE_ONLY));
+    InputSet& I = c->sets[nset];
+    SCAL_TRY(I.ev_pre.ensure(EV_DEVICE_ONLY));
+    SCAL_TRY(I.ev_pre_a.ensure(EV_DEVICE_ONLY));
     // The gather (it also stores per-block bounding boxes of the surf cloud for the filter) and the small corner filter ride on the
     // features context's own stream, right behind stage A; the surf filter runs on the side stream, which it shares with
     // ScanContext's keyframe filter.  (More than four busy streams slow every stream down on this GPU; see stage_lane().)
     hipStream_t sa = v.stream;
     const int nbc = std::max(1, div_up(ls_cap, 256));
     SCAL_LAUNCH("k_map_gather", k_map_gather, dim3(nbc + std::max(1, div_up(cap, 256))), dim3(256), 0, sa, v.less_xyzi, &v.P->n_less_sharp,
-                     CSoA4{v.lfx, v.lfy, v.lfz, v.lfi}, &v.P->n_less_flat, c->corner_in(nset).v(), c->surf_in(nset).v(), c->d_C(nset).p, c->scan_cap, nbc,
-                     c->surf_parts[nset].p);
+                     CSoA4{v.lfx, v.lfy, v.lfz, v.lfi}, &v.P->n_less_flat, I.in[0].v(), I.in[1].v(), I.C.p, c->scan_cap, nbc, I.surf_parts.p);
     SCAL_HIP(hipGetLastError());
-    SCAL_TRY(enqueue_corner_filter(c, c->vf_corner, sa, ls_cap, nset));
-    SCAL_HIP(op_event_record(c->ev_pre_a[nset], sa));
-    c->pf_half[c->n_half].feat = feat, c->pf_half[c->n_half].set = nset, c->pf_half[c->n_half].generation = v.generation;
-    c->n_half++;
+    SCAL_TRY(enqueue_stack_filter(c, 0, c->vf_corner, sa, ls_cap, nset));
+    SCAL_HIP(op_event_record(I.ev_pre_a, sa));
+    c->pf_half.push(scal_map::Prefetch{feat, nset, v.generation});
     return SCAL_OK;
 }
 
@@ -2414,22 +2504,21 @@ extern "C" int scal_map_prefetch_finish(scal_map_t* c, scal_features_t* feat) {
     FeatDeviceView v = features_view(feat);
     const int cap = std::min(c->scan_cap, v.cap);
     std::lock_guard<std::mutex> lk(c->pf_mu);
-    if (c->n_half == 0 || c->pf_half[0].feat != feat) {
+    if (c->pf_half.n == 0 || c->pf_half.front().feat != feat) {
         set_error("scal_map_prefetch_finish: no scal_map_prefetch_begin of this features context is waiting (halves are finished in the order they were begun)");
         return SCAL_E_STATE;
     }
-    const scal_map::Prefetch h = c->pf_half[0];
-    for (int i = 1; i < c->n_half; ++i) c->pf_half[i - 1] = c->pf_half[i];
-    c->n_half--;
+    const scal_map::Prefetch h = c->pf_half.front();
+    c->pf_half.pop();
+    InputSet& I = c->sets[h.set];
     // ONE event from the features stream, recorded behind gather AND corner filter: the surf filter starts ~35 us later than it could
     // (it has that slack: the side lane is busy 190 of every ~217 us and the step needs its output a whole stage B later), the
     // features stream saves an event record between two kernels of the chain the pipeline is bound by, and the step waits for one
     // event that covers both halves
-    SCAL_HIP(op_stream_wait_event(c->side, c->ev_pre_a[h.set], 0));
-    SCAL_TRY(enqueue_surf_filter(c, c->vf_side, c->side, cap, h.set, true));
-    SCAL_HIP(op_event_record(c->ev_pre[h.set], c->side));
-    c->pf[c->n_pf] = h;
-    c->n_pf++;
+    SCAL_HIP(op_stream_wait_event(c->side, I.ev_pre_a, 0));
+    SCAL_TRY(enqueue_stack_filter(c, 1, c->vf_side, c->side, cap, h.set, true));
+    SCAL_HIP(op_event_record(I.ev_pre, c->side));
+    c->pf.push(h);
     return SCAL_OK;
 }
 
@@ -2440,37 +2529,31 @@ extern "C" int scal_map_prefetch_features(scal_map_t* c, scal_features_t* feat) 
 
 static int map_enqueue_features(scal_map* c, scal_features_t* feat, const double* q_wodom, const double* t_wodom) {
     FeatDeviceView v = features_view(feat);
-    if (v.device != c->cfg.device) {
-        set_error("features context lives on device %d, map context on %d", v.device, c->cfg.device);
-        return SCAL_E_ARG;
-    }
+    SCAL_TRY(check_features_device(c, v));
     SCAL_HIP(hipSetDevice(c->cfg.device));
     SCAL_TRY(map_make_room(c));
-    MapStep e;
-    SCAL_TRY(new_step(c, &e));
+    MapStep e = new_step(c);
     e.feat = feat;
     e.feat_generation = v.generation;
     e.n_corner_bound = std::min(c->scan_cap, v.n_scans * 120);
     e.n_surf_bound = std::min(c->scan_cap, v.cap);
     e.have_full = true;
-    for (int i = 0; i < 4; ++i) e.pose.q_wodom[i] = q_wodom[i];
-    for (int i = 0; i < 3; ++i) e.pose.t_wodom[i] = t_wodom[i];
+    copy_pose(e.pose.q_wodom, e.pose.t_wodom, q_wodom, t_wodom);
     {
         std::lock_guard<std::mutex> lk(c->pf_mu);
-        if (c->n_pf > 0 && c->pf[0].feat == feat) {  // the oldest queued prefetch belongs to this step: take its set
-            if (c->pf[0].generation != v.generation) {
+        if (c->pf.n > 0 && c->pf.front().feat == feat) {  // the oldest queued prefetch belongs to this step: take its set
+            if (c->pf.front().generation != v.generation) {
                 // the prefetched inputs are of an EARLIER scan than the one now in `feat` (its full-resolution cloud, read by the
                 // registration at the end of the step, has been overwritten): refuse instead of mixing two scans
-                c->n_pf = 0, c->n_half = 0;
+                drop_prefetches(c);
                 set_error("scal_map_enqueue_features: the features context was run again between scal_map_prefetch_features and this call");
                 return SCAL_E_STATE;
             }
             e.prefetched = true;
-            e.set = c->pf[0].set;
-            for (int i = 1; i < c->n_pf; ++i) c->pf[i - 1] = c->pf[i];
-            c->n_pf--;
+            e.set = c->pf.front().set;
+            c->pf.pop();
         } else {  // no (matching, complete) prefetch: drop what was queued and take a fresh set
-            c->n_pf = 0, c->n_half = 0;
+            drop_prefetches(c);
             e.set = c->alloc_set();
         }
     }
@@ -2485,11 +2568,8 @@ extern "C" int scal_map_step_features(scal_map_t* c, scal_features_t* feat, cons
     }
     SCAL_TRY(map_enqueue_features(c, feat, q_wodom, t_wodom));
     SCAL_TRY(map_collect_pose(c, q_w_curr, t_w_curr, stats));
-    SCAL_TRY(map_finish(c));
-    if (stats) {
-        stats->n_map_corner_total = c->map[0].n, stats->n_map_surf_total = c->map[1].n;
-        stats->insert_path = c->last_insert_path;
-    }
+    SCAL_TRY(map_settle(c, true));
+    stats_after_insertion(c, stats);
     return SCAL_OK;
 }
 
@@ -2513,7 +2593,7 @@ extern "C" int scal_map_collect(scal_map_t* c, double* q_w_curr, double* t_w_cur
 extern "C" int scal_map_finish(scal_map_t* c) {
     if (!c) return SCAL_E_ARG;
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    return map_finish(c);
+    return map_settle(c, true);
 }
 
 extern "C" int scal_map_export(scal_map_t* c, int which, float* out_xyzi, int cap) {
@@ -2522,7 +2602,7 @@ extern "C" int scal_map_export(scal_map_t* c, int which, float* out_xyzi, int ca
         return SCAL_E_ARG;
     }
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    if (map_finish(c) != SCAL_OK) return -1;
+    if (map_settle(c, true) != SCAL_OK) return -1;
     if (!c->have_mp || c->map[which].n == 0) return 0;
     hipStream_t s = c->stream;
     MapStore& M = c->map[which];
@@ -2555,7 +2635,7 @@ extern "C" int scal_map_export_all(scal_map_t* c, int which, float* out_xyzi, in
         return SCAL_E_ARG;
     }
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    if (map_finish(c) != SCAL_OK) return -1;
+    if (map_settle(c, true) != SCAL_OK) return -1;
     MapStore& M = c->map[which];
     if (!out_xyzi || cap == 0) return M.n;
     const int m = std::min(M.n, cap);
@@ -2579,8 +2659,7 @@ extern "C" int scal_map_set_merge_insert(scal_map_t* c, int enable) {
 
 extern "C" int scal_map_get_wmap_wodom(scal_map_t* c, double* q, double* t) {
     if (!c || !q || !t) return SCAL_E_ARG;
-    for (int i = 0; i < 4; ++i) q[i] = c->q_wmap_wodom[i];
-    for (int i = 0; i < 3; ++i) t[i] = c->t_wmap_wodom[i];
+    copy_pose(q, t, c->q_wmap_wodom, c->t_wmap_wodom);
     return SCAL_OK;
 }
 
@@ -2598,58 +2677,14 @@ extern "C" int scal_map_set_poll(scal_map_t* c, int enable) {
 
 // ------------------------------------------------------------------------------------------------ Ceres-adapter mode
 // The host keeps ceres::Problem / ceres::Solve (laserMapping.cpp:566-573, :713-721); the device does everything around it.
-static int upload_step_inputs(scal_map* c, MapStep& e, const float* corner_last, int n_corner, const float* surf_last, int n_surf, const float* full_res,
-                              int n_full) {
-    hipStream_t s = c->stream;
-    MapCounters z;
-    std::memset(&z, 0, sizeof z);
-    z.n_corner_in = n_corner, z.n_surf_in = n_surf;
-    *c->h_C.p = z;
-    SCAL_HIP(op_memcpy_async(c->d_C(e.set).p, c->h_C.p, sizeof(MapCounters), hipMemcpyHostToDevice, s));
-    c->h_misc.p[0] = n_full;
-    SCAL_HIP(op_memcpy_async(c->d_nfull.p, c->h_misc.p, sizeof(int), hipMemcpyHostToDevice, s));
-    auto up = [&](const float* src, int n, SoAStore& dst) -> int {
-        if (n > 0) {
-            SCAL_HIP(op_memcpy_async(c->aos.p, src, sizeof(float) * 4 * n, hipMemcpyHostToDevice, s));
-            launch_deinterleave(s, c->aos.p, n, dst.v());
-            SCAL_HIP(op_stream_synchronize(s));  // the staging buffer is reused by the next upload
-        }
-        return SCAL_OK;
-    };
-    SCAL_TRY(up(corner_last, n_corner, c->corner_in(e.set)));
-    SCAL_TRY(up(surf_last, n_surf, c->surf_in(e.set)));
-    if (n_full > 0) SCAL_TRY(up(full_res, n_full, c->full_in));
-    e.have_full = n_full > 0, e.n_corner_bound = n_corner, e.n_surf_bound = n_surf;
-    return SCAL_OK;
-}
-
 extern "C" int scal_map_adapter_begin(scal_map_t* c, const float* corner_last, int n_corner, const float* surf_last, int n_surf, const float* full_res,
                                       int n_full, const double* q_wodom, const double* t_wodom, double* q_w_curr, double* t_w_curr) {
-    if (!c || !q_wodom || !t_wodom || !q_w_curr || !t_w_curr || n_corner < 0 || n_surf < 0 || n_full < 0 || (n_corner > 0 && !corner_last) ||
-        (n_surf > 0 && !surf_last)) {
-        set_error("scal_map_adapter_begin: bad argument");
-        return SCAL_E_ARG;
-    }
-    if (n_corner > c->scan_cap || n_surf > c->scan_cap || n_full > c->scan_cap) {
-        set_error("scal_map_adapter_begin: input cloud larger than max_scan_points (%d)", c->scan_cap);
-        return SCAL_E_TOO_MANY;
-    }
-    SCAL_HIP(hipSetDevice(c->cfg.device));
-    SCAL_TRY(map_finish(c));
-    if (!c->steps.empty() || c->adapter_active) {
-        set_error("scal_map_adapter_begin: a step is still open");
-        return SCAL_E_STATE;
-    }
+    SCAL_TRY(check_host_arrays("scal_map_adapter_begin", c, corner_last, n_corner, surf_last, n_surf, n_full, q_wodom, t_wodom, q_w_curr, t_w_curr));
+    const bool have_full = full_res != nullptr && n_full > 0;
     MapStep e;
-    SCAL_TRY(new_step(c, &e));
-    {
-        std::lock_guard<std::mutex> lk(c->pf_mu);
-        c->n_pf = 0, c->n_half = 0;
-        e.set = c->alloc_set();
-    }
-    SCAL_TRY(upload_step_inputs(c, e, corner_last, n_corner, surf_last, n_surf, (full_res && n_full > 0) ? full_res : nullptr, full_res ? n_full : 0));
-    for (int i = 0; i < 4; ++i) e.pose.q_wodom[i] = q_wodom[i];
-    for (int i = 0; i < 3; ++i) e.pose.t_wodom[i] = t_wodom[i];
+    SCAL_TRY(begin_sync_step(c, true, "scal_map_adapter_begin: a step is still open", &e));
+    SCAL_TRY(upload_step_inputs(c, e, corner_last, n_corner, surf_last, n_surf, full_res, have_full ? n_full : 0));
+    copy_pose(e.pose.q_wodom, e.pose.t_wodom, q_wodom, t_wodom);
     e.fast = false, e.par = c->cur;
     SCAL_TRY(drop_prebuilt_grid(c));
     c->n_general++;
@@ -2659,8 +2694,7 @@ extern "C" int scal_map_adapter_begin(scal_map_t* c, const float* corner_last, i
     SCAL_HIP(op_memcpy_async(c->res.p + e.slot, c->lm.d_st.p, sizeof(LMState), hipMemcpyDeviceToHost, s));  // MapResult::st is its first member
     SCAL_HIP(op_stream_synchronize(s));
     const double* x = c->res.p[e.slot].st.x;
-    for (int i = 0; i < 4; ++i) q_w_curr[i] = x[i];
-    for (int i = 0; i < 3; ++i) t_w_curr[i] = x[4 + i];
+    copy_pose(q_w_curr, t_w_curr, x, x + 4);
     c->adapter_step = e;
     c->adapter_active = true;
     return SCAL_OK;
@@ -2671,20 +2705,18 @@ extern "C" int scal_map_associate(scal_map_t* c, const double* q_w_curr, const d
         set_error("scal_map_associate: null argument");
         return SCAL_E_ARG;
     }
-    if (!c->adapter_active) {
-        set_error("scal_map_associate: no scal_map_adapter_begin");
-        return SCAL_E_STATE;
-    }
+    SCAL_TRY(need_adapter_step(c, "scal_map_associate"));
     SCAL_HIP(hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
     const MapStep& e = c->adapter_step;
-    MapCounters* C = c->d_C(e.set).p;
+    const InputSet& I = c->sets[e.set];
+    MapCounters* C = I.C.p;
     SCAL_TRY(c->blocks.set_pose(s, c->lm.d_st.p->x, q_w_curr, t_w_curr));
     FactorSoA F = c->lm.factors();
     const int assoc_blocks = std::max(1, std::min(3072, div_up(c->lm.slot_cap, 8)));
-    SCAL_LAUNCH("k_assoc_knn", k_assoc_knn, dim3(assoc_blocks), dim3(256), 0, s, c->corner_stack(e.set).cv(), c->surf_stack(e.set).cv(), c->d_S.p,
+    SCAL_LAUNCH("k_assoc_knn", k_assoc_knn, dim3(assoc_blocks), dim3(256), 0, s, I.stack[0].cv(), I.stack[1].cv(), c->d_S.p,
                      c->grid[0].cell[e.par].p, c->grid[0].pts(e.par), c->grid[1].cell[e.par].p, c->grid[1].pts(e.par), c->lm.d_st.p, C, c->nnbuf(), MapBeginArgs{});
-    const AssocFit fit{c->corner_stack(e.set).cv(), c->surf_stack(e.set).cv(), c->nnbuf(), C, F};
+    const AssocFit fit{I.stack[0].cv(), I.stack[1].cv(), c->nnbuf(), C, F};
     SCAL_LAUNCH("k_assoc_fit", k_assoc_fit, dim3(std::max(1, div_up(c->lm.slot_cap, 64))), dim3(64), 0, s, fit, c->d_S.p);
     SCAL_TRY(c->blocks.compact(s, F, &C->n_slots));
     SCAL_HIP(op_memcpy_async(c->h_C.p, C, sizeof(MapCounters), hipMemcpyDeviceToHost, s));
@@ -2699,10 +2731,7 @@ extern "C" int scal_map_get_blocks(scal_map_t* c, scal_block* out, int cap) {
         set_error("scal_map_get_blocks: bad argument");
         return SCAL_E_ARG;
     }
-    if (!c->adapter_active) {
-        set_error("scal_map_get_blocks: no scal_map_adapter_begin");
-        return SCAL_E_STATE;
-    }
+    SCAL_TRY(need_adapter_step(c, "scal_map_get_blocks"));
     SCAL_HIP(hipSetDevice(c->cfg.device));
     return c->blocks.get_blocks(c->stream, c->lm.factors(), out, cap);
 }
@@ -2712,10 +2741,7 @@ extern "C" int scal_map_eval_blocks(scal_map_t* c, const double* x7, int want_ja
         set_error("scal_map_eval_blocks: bad argument");
         return SCAL_E_ARG;
     }
-    if (!c->adapter_active) {
-        set_error("scal_map_eval_blocks: no scal_map_adapter_begin");
-        return SCAL_E_STATE;
-    }
+    SCAL_TRY(need_adapter_step(c, "scal_map_eval_blocks"));
     SCAL_HIP(hipSetDevice(c->cfg.device));
     return c->blocks.eval_blocks(c->stream, c->lm.factors(), x7, want_jac, residuals, jacobians);
 }
@@ -2725,10 +2751,7 @@ extern "C" int scal_map_adapter_finish(scal_map_t* c, const double* q_w_curr, co
         set_error("scal_map_adapter_finish: null argument");
         return SCAL_E_ARG;
     }
-    if (!c->adapter_active) {
-        set_error("scal_map_adapter_finish: no scal_map_adapter_begin");
-        return SCAL_E_STATE;
-    }
+    SCAL_TRY(need_adapter_step(c, "scal_map_adapter_finish"));
     SCAL_HIP(hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
     MapStep& e = c->adapter_step;
@@ -2741,27 +2764,12 @@ extern "C" int scal_map_adapter_finish(scal_map_t* c, const double* q_w_curr, co
     SCAL_HIP(op_event_synchronize(c->ev_pose[e.slot]));
     SCAL_TRY(general_insert(c, e));
     const MapResult& R = c->res.p[e.slot];
-    for (int i = 0; i < 4; ++i) c->q_wmap_wodom[i] = R.S1.q_wmap_wodom[i];
-    for (int i = 0; i < 3; ++i) c->t_wmap_wodom[i] = R.S1.t_wmap_wodom[i];
-    c->have_mp = true;
+    publish_correction(c, R.S1);
     for (int k = 0; k < 2; ++k) c->map[k].n = R.S2.n_map[k];
     c->last_insert_path = e.insert_path;
-    if (stats) {
-        std::memset(stats, 0, sizeof *stats);
-        stats->n_corner_stack = R.C1.n_corner_stack, stats->n_surf_stack = R.C1.n_surf_stack;
-        stats->n_corner_map = R.C1.n_valid[0], stats->n_surf_map = R.C1.n_valid[1];
-        stats->solved = R.C1.solve_on;
-        stats->n_map_corner_total = c->map[0].n, stats->n_map_surf_total = c->map[1].n;
-        stats->insert_path = e.insert_path;
-    }
-    if (e.have_full && registered) {
-        const int n_full = c->h_misc.p[0];
-        launch_interleave(s, c->d_nfull.p, n_full, c->full_out.cv(), c->aos.p);
-        (void)c->hs_reg.reserve((size_t)c->scan_cap * 16 + 4096);
-        SCAL_HIP(c->hs_reg.d2h(registered, c->aos.p, sizeof(float) * 4 * n_full, s));
-        SCAL_HIP(op_stream_synchronize(s));
-        c->hs_reg.finish();
-    }
+    if (stats) stats_at_pose(R.C1, stats);
+    stats_after_insertion(c, stats);  // last_insert_path is this step's
+    if (e.have_full && registered) SCAL_TRY(download_registered(c, registered, c->h_misc.p[0]));
     return SCAL_OK;
 }
 
@@ -2773,7 +2781,7 @@ extern "C" int scal_map_debug_set_grid_cap(scal_map_t* c, int cap_corner, int ca
         return SCAL_E_ARG;
     }
     if (!c->grid_fixed) return SCAL_OK;
-    SCAL_TRY(map_finish(c));
+    SCAL_TRY(map_settle(c, true));
     SCAL_HIP(hipSetDevice(c->cfg.device));
     SCAL_TRY(drop_prebuilt_grid(c));  // binned under the old slice size: the next step builds its own
     c->grid_cap_now[0] = std::min(cap_corner, c->grid[0].fixed_cap);

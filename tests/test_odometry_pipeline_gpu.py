@@ -410,7 +410,26 @@ def test_async_entry_points_reject_misuse(S, hdl64_stream):
     assert e.value.code == S.E_STATE and "run again" in str(e.value)
     q3, t3, ms3 = mp.process_features(reg, qw, tw)
     assert ms3.insert_path in (0, 1)
-    for x in (reg, od, mp, sc):
+    # prefetches that no step takes - one for another features context than the step's, one in front of the host-array entry
+    # point - are dropped and the step takes a fresh input set: mapper `a` must do exactly what `b` does, which never prefetched
+    r0, r1 = (S.ScanRegistration(S.HDL64, 5.0, max_points=200000) for _ in range(2))
+    f0 = r0.laserCloudHandler(hdl64_stream(0))
+    r1.laserCloudHandler(hdl64_stream(1))
+    clouds = (f0["cloud"][f0["less_sharp"]], f0["less_flat"], f0["cloud"])
+    a, b = (S.LaserMapping(max_scan_points=200000, max_map_points=1000000) for _ in range(2))
+    a.prefetch_features(r0)
+    out_a = [a.process_features(r1, qw, tw)]
+    a.prefetch_features(r0)
+    out_a.append(a.process(*clouds, qw, tw)[:3])
+    out_b = [b.process_features(r1, qw, tw), b.process(*clouds, qw, tw)[:3]]
+    for (qa, ta, sa), (qb, tb, sb) in zip(out_a, out_b):
+        assert np.array_equal(qa, qb) and np.array_equal(ta, tb) and sa.insert_path == sb.insert_path
+    assert a.path_counters() == b.path_counters()
+    for which in (0, 1):
+        assert np.array_equal(a.export_all(which), b.export_all(which)), which
+        va, vb = a.export(which), b.export(which)   # the window's points come out in no fixed order
+        assert va.shape[0] > 0 and np.array_equal(va[np.lexsort(va.T[::-1])], vb[np.lexsort(vb.T[::-1])]), which
+    for x in (reg, od, mp, sc, r0, r1, a, b):
         x.close()
 
 
