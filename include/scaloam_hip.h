@@ -436,6 +436,62 @@ int scal_icp_align_device(scal_icp_t* ctx, const float* d_src_xyzi, int n_src, c
  * same correspondences, lowest target index on equal distances. */
 int scal_icp_set_search(scal_icp_t* ctx, int mode);
 
+/* ------------------------------------------------------------------ multiview refine (BASELINE.json config #5, "global ICP refine")
+ * An extension: the reference has no counterpart.  All K keyframes of a session are aligned at once, in Jacobi rounds.  One round:
+ *  1. every frame f is moved by its pose with the map merge's arithmetic and near-range rule (the bits of a one-frame
+ *     scal_mapmerge_add + download); the union of the moved frames, in frame order, is the round's fixed target;
+ *  2. every non-fixed frame is aligned by point-to-point ICP - iteration, increment, convergence criteria and states exactly those
+ *     of scal_icp_align - against the points of ALL OTHER frames: a point's own frame is never a candidate (a frame matched
+ *     against a target that contains itself does not move);
+ *  3. fitness = sum d^2 / n over the correspondences within max_corr_dist of a last sweep of the source moved by the final T.
+ *     This deviates on purpose from scal_icp_result::fitness, which is PCL's uncapped getFitnessScore(): an uncapped score needs an
+ *     exact neighbour for every far point that no other keyframe saw - at the scale of a session a dense sweep of millions of
+ *     queries.  Where every point has a neighbour within max_corr_dist the two are the same number;
+ *  4. frame f is accepted iff converged and fitness <= fitness_gate (the reference's loop test, :532, 0.3 there): pose <- T * pose
+ *     in f64 (T's f32 values promoted; ((T[r][0] P[0][c] + T[r][1] P[1][c]) + T[r][2] P[2][c]) (+ T[r][3] for c = 3), no
+ *     re-orthonormalisation).  Rejected and fixed frames keep their pose and still serve as targets;
+ *  5. the next round moves the LOCAL clouds by the new poses (no f32 error accumulates) and the rounds stop early once a round
+ *     accepts no increment other than the identity.
+ * max_corr_dist: the reference's ICP uses 150 m (:520) because it verifies ONE loop candidate against a submap; across a whole
+ * session that cap pairs every point of a frame with something, however far.  A CPU prototype on the golden KAIST03 keyframes
+ * 0 / 7 / 20 (0.4 m leaf, golden poses, each against the other two) moved the outer frames' clean poses by 0.30-0.90 m with the
+ * 150 m cap and by 0.08-0.17 m with a 2 m cap; the middle frame displaced by (0.3, -0.2, 0.05) m and 0.02 rad of yaw came back
+ * from 0.471 m / 1.146 deg to 0.062 m / 0.068 deg of its golden pose with the 2 m cap.  The Python wrapper defaults to 2 m.
+ * The neighbour search is exact for any cap: a sparse 1 m cell index (sorted cell keys behind a hash table) whose cell width does
+ * not grow with the map's extent, searched ring by ring, with a dense sweep for the queries it cannot settle when the cap asks
+ * for neighbours beyond the last ring. */
+typedef struct {
+    double max_corr_dist;           /* as scal_icp_config */
+    double transformation_epsilon;
+    double fitness_epsilon;
+    double fitness_gate;            /* accept iff converged && fitness <= fitness_gate */
+    int max_iterations;
+    int max_frames;                 /* capacities: keyframes per call ... */
+    int max_points;                 /* ... and points of all of them together */
+    int device;
+} scal_refine_config;
+typedef struct {
+    int converged, iterations, state, n_correspondences;  /* of the last round, as scal_icp_result (state 0: fixed frame) */
+    int accepted;           /* the last round's T went into the pose */
+    double fitness;         /* capped at max_corr_dist (see above); DBL_MAX without a correspondence */
+    double T[16];           /* the last round's transformation, row-major, f32 values */
+} scal_refine_frame_result;
+typedef struct scal_refine scal_refine_t;
+int scal_refine_create(const scal_refine_config* cfg, scal_refine_t** ctx);   /* SCAL_E_NO_DEVICE without a gfx950 device */
+void scal_refine_destroy(scal_refine_t* ctx);
+/* n_frames keyframes in their LOCAL frames, 16-byte xyzi records back to back in device memory: frame f = records [offsets[f],
+ * offsets[f+1]) (host array, offsets[0] = 0, non-decreasing), as scal_mapmerge_add_batch_device takes them; thin them first
+ * (scal_voxel_downsample_device, 0.4 m in the reference's ICP, :491-492).  poses12: rows of optimized_poses.txt, refined in place.
+ * fixed: one byte per frame, non-zero = the pose is held (NULL: none).  res[n_frames], *rounds_run: the rounds executed.
+ * SCAL_E_ARG: a NULL pointer, n_frames < 0, rounds < 1, bad offsets, near_thres not finite; SCAL_E_TOO_MANY: more frames or points
+ * than the context holds.  Arguments are checked before the device is touched and the context stays usable after any error.  An
+ * empty frame and a frame with fewer than 3 correspondences end in state 5, not accepted, pose kept. */
+int scal_refine_run_device(scal_refine_t* ctx, const float* d_xyzi, const int* offsets, int n_frames, double* poses12,
+                           const unsigned char* fixed, double near_thres, int rounds, scal_refine_frame_result* res, int* rounds_run);
+/* the same with the records in host memory (staged into the context) */
+int scal_refine_run(scal_refine_t* ctx, const float* xyzi, const int* offsets, int n_frames, double* poses12,
+                    const unsigned char* fixed, double near_thres, int rounds, scal_refine_frame_result* res, int* rounds_run);
+
 /* ------------------------------------------------------------------ the four stages as ONE pipelined object
  * The reference runs scanRegistration, laserOdometry, laserMapping and laserPosegraphOptimization as four processes that work on
  * different scans at the same time (node main()s: scanRegistration.cpp:475-517, laserOdometry.cpp:186-600, laserMapping.cpp:909-952,

@@ -59,6 +59,8 @@ int map_create(const scal_map_config* cfg, StreamLayout layout, scal_map_t** out
 int sc_create(const scal_sc_config* cfg, StreamLayout layout, scal_sc_t** out);
 // scal_icp_create on a given lane (scal_pipeline's loop verification keeps off the four busy lanes)
 int icp_create_on_lane(const scal_icp_config* cfg, int lane, scal_icp_t** out);
+// scal_refine_create on a given lane
+int refine_create_on_lane(const scal_refine_config* cfg, int lane, scal_refine_t** out);
 // scal_posegraph_create on a given lane (scal_pipeline_optimize_keyframes solves on the pose-graph map's lane)
 int posegraph_create_on_lane(const scal_posegraph_config* cfg, int lane, scal_posegraph_t** out);
 // scal_sc_insert_features with a hook queued on the ScanContext stream behind the descriptor and before the next keyframe filter may

@@ -1,0 +1,608 @@
+// Multiview refine on gfx950 (BASELINE.json config #5, "global ICP refine"; include/scaloam_hip.h has the semantics): all K keyframes
+// of a session aligned at once by point-to-point ICP, each against the points of all the others, in Jacobi rounds.  An extension -
+// the reference has no counterpart; the single alignment it is held to is scal_icp_align (icp.hip), bit for bit.
+//
+// Per round:
+//   k_rf_count / k_rf_write   every frame moved by its pose with the map merge's own passes (mapmerge_dev.hpp) -> G, the round's
+//                             target, frames in order, every point with its frame beside it; the sources start as a copy of G
+//   k_rf_keys, RadixSort,     sparse neighbour index over G: 48-bit key of the 1 m cell coordinates, sorted (stable, so a cell's
+//   k_rf_index                points stay in index order), the cells' [start, end) ranges behind an open-addressing hash table in
+//                             HBM.  The cell width does not depend on the map's extent, as icp.hip's dense 2^18-cell grid does.
+// Per iteration, ONE launch chain for all frames still iterating and one host synchronisation:
+//   k_rf_apply    last iteration's increments, one 3x4 matrix per frame
+//   k_rf_grid_nn  a wave per source point: the cube of cells around it ring by ring, candidates spread over the lanes, key
+//                 (f32 d^2 bits << 32) | index, stop rule best < ((k - 0.05) cell)^2 - k_icp_grid_nn's search; a candidate of the
+//                 query's own frame is dropped before the key is formed
+//   k_rf_dense    only when max_corr_dist reaches beyond the last ring: the unsettled queries as a list against all of G, a fixed
+//                 number of workgroups striding over (query tile, target chunk) pairs - none when the list is empty
+//   k_rf_reduce   the 17 correspondence sums per workgroup of 256 source points COUNTED FROM THE FRAME'S FIRST POINT, wave_sum, then
+//   k_rf_final    ((r0+r1)+r2)+r3, then the frame's workgroup partials in workgroup order -> pinned [K][17]: the additions of
+//                 k_icp_reduce / k_icp_final on that frame alone, in their order
+//   host          icp_host_step (icp_host.hpp, shared with icp.hip) per frame; K 3x4 increments and the active mask go back in one copy
+// Frames that have finished cost an early return per workgroup.
+#include "common.hpp"
+#include "device_utils.hpp"
+#include "icp_host.hpp"
+#include "mapmerge_dev.hpp"
+#include "radix_sort.hpp"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+namespace scal {
+
+constexpr int RF_NSUM = 17;        // n, sum p[3], sum q[3], sum q p^T[9], sum d^2
+constexpr int RF_RINGS = 3;        // as ICP_RINGS
+constexpr float RF_CELL = 1.0f;    // cell width in metres; cell coordinate = floor(v), exact in f32
+constexpr int RF_QT = 1024, RF_TC = 2048, RF_QPT = 4;  // dense sweep: queries / targets per work item, queries per thread
+constexpr int RF_DENSE_WG = 2048;  // workgroups of the dense sweep
+// cell coordinates: 17 bits in x and y (+-65 km), 14 in z (+-8 km), clamped beyond.  Clamping is monotone, so a cell that the ring
+// search has not examined is still at least k cells away from the query along some axis and the stop rule holds out there too.
+constexpr int RF_XB = 17, RF_ZB = 14, RF_KEY_BITS = 2 * RF_XB + RF_ZB;
+constexpr unsigned long long RF_NO_CELL = (1ull << RF_KEY_BITS) - 1;  // non-finite points: sorted behind every cell, in no cell
+constexpr unsigned long long RF_EMPTY = ~0ull;
+
+struct RfBlock {
+    int first, end, frame;  // 256 source points of one frame: [first, min(first + 256, end)) of G
+};
+struct RfCtrl {  // per frame, host -> device once per iteration
+    int active;    // the frame takes part in this iteration's sweep
+    float m[12];   // increment to apply first (active frames, from the second iteration on)
+};
+
+__global__ void __launch_bounds__(256) k_rf_count(const float4* __restrict__ in, const MMBlock* __restrict__ blocks, double thres,
+                                                  int* __restrict__ blkcnt) {
+    mm_count_body(in, blocks, thres, blkcnt);
+}
+__global__ void __launch_bounds__(256) k_rf_write(const float4* __restrict__ in, const MMBlock* __restrict__ blocks, const double* __restrict__ poses,
+                                                  double thres, const int* __restrict__ blkoff, long long cap, float4* __restrict__ out,
+                                                  int* __restrict__ frame_of) {
+    mm_write_body<true>(in, blocks, poses, thres, blkoff, 0, cap, out, frame_of);
+}
+
+__device__ __forceinline__ int rf_coord(float v, int bits) {  // NaN -> the lowest cell
+    const float lim = static_cast<float>(1 << (bits - 1));
+    return static_cast<int>(fminf(fmaxf(floorf(v), -lim), lim - 2.f));
+}
+// key of cell (x, y, z), RF_NO_CELL outside the coordinate range (nothing is stored there)
+__device__ __forceinline__ unsigned long long rf_key(int x, int y, int z) {
+    const int bx = x + (1 << (RF_XB - 1)), by = y + (1 << (RF_XB - 1)), bz = z + (1 << (RF_ZB - 1));
+    if (static_cast<unsigned>(bx) >= (1u << RF_XB) - 1 || static_cast<unsigned>(by) >= (1u << RF_XB) - 1 || static_cast<unsigned>(bz) >= (1u << RF_ZB) - 1)
+        return RF_NO_CELL;
+    return (static_cast<unsigned long long>(bz) << (2 * RF_XB)) | (static_cast<unsigned long long>(by) << RF_XB) | static_cast<unsigned long long>(bx);
+}
+__device__ __forceinline__ unsigned rf_slot(unsigned long long key, unsigned mask) {
+    unsigned long long h = key * 0x9E3779B97F4A7C15ull;
+    h ^= h >> 29;
+    return static_cast<unsigned>(h) & mask;
+}
+
+__global__ void __launch_bounds__(256) k_rf_keys(const float4* __restrict__ g, int n, unsigned long long* __restrict__ keys, int* __restrict__ vals) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = g[i];
+    unsigned long long key = RF_NO_CELL;  // non-finite points can never be a nearest neighbour (d < 3.4e38 fails)
+    if (fabsf(p.x) < 3.4e38f && fabsf(p.y) < 3.4e38f && fabsf(p.z) < 3.4e38f) key = rf_key(rf_coord(p.x, RF_XB), rf_coord(p.y, RF_XB), rf_coord(p.z, RF_ZB));
+    keys[i] = key;
+    vals[i] = i;
+}
+
+// sorted position i: the point itself with its index in G beside it; the first and the last position of a cell enter the cell's
+// range into the hash table (find-or-insert by compare-and-swap; which of the two arrives first does not matter)
+__global__ void __launch_bounds__(256) k_rf_index(const unsigned long long* __restrict__ keys, const int* __restrict__ vals, int n,
+                                                  const float4* __restrict__ g, float4* __restrict__ sorted, unsigned long long* __restrict__ hkeys,
+                                                  int2* __restrict__ hrange, unsigned mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = keys[i];
+    const int idx = vals[i];
+    float4 p = g[idx];
+    p.w = __int_as_float(idx);
+    sorted[i] = p;
+    if (key == RF_NO_CELL) return;
+    const bool head = i == 0 || keys[i - 1] != key, tail = i == n - 1 || keys[i + 1] != key;
+    if (!head && !tail) return;
+    unsigned slot = rf_slot(key, mask);
+    for (;;) {  // the table has at least twice as many slots as there are points
+        const unsigned long long prev = atomicCAS(&hkeys[slot], RF_EMPTY, key);
+        if (prev == RF_EMPTY || prev == key) break;
+        slot = (slot + 1) & mask;
+    }
+    if (head) hrange[slot].x = i;
+    if (tail) hrange[slot].y = i + 1;
+}
+
+__global__ void __launch_bounds__(256) k_rf_apply(float4* __restrict__ cur, const RfBlock* __restrict__ blocks, const RfCtrl* __restrict__ ctrl) {
+    const RfBlock b = blocks[blockIdx.x];
+    if (!ctrl[b.frame].active) return;
+    const int i = b.first + threadIdx.x;
+    if (i >= b.end) return;
+    const float* m = ctrl[b.frame].m;
+    const float4 p = cur[i];
+    float4 o;  // k_icp_apply's order
+    o.x = ((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3];
+    o.y = ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7];
+    o.z = ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11];
+    o.w = p.w;
+    cur[i] = o;
+}
+// the fitness sweep's sources: the moved frame itself (g) by the whole transformation
+__global__ void __launch_bounds__(256) k_rf_apply_from(const float4* __restrict__ g, float4* __restrict__ cur, const RfBlock* __restrict__ blocks,
+                                                       const RfCtrl* __restrict__ ctrl) {
+    const RfBlock b = blocks[blockIdx.x];
+    if (!ctrl[b.frame].active) return;
+    const int i = b.first + threadIdx.x;
+    if (i >= b.end) return;
+    const float* m = ctrl[b.frame].m;
+    const float4 p = g[i];
+    float4 o;
+    o.x = ((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3];
+    o.y = ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7];
+    o.z = ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11];
+    o.w = p.w;
+    cur[i] = o;
+}
+
+// one wave per query (k_icp_grid_nn with the cell looked up through the hash table and the query's own frame left out)
+__global__ void __launch_bounds__(256) k_rf_grid_nn(const float4* __restrict__ cur, int n, const int* __restrict__ frame_of, const int* __restrict__ goff,
+                                                    const RfCtrl* __restrict__ ctrl, const unsigned long long* __restrict__ hkeys,
+                                                    const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
+                                                    unsigned long long* __restrict__ best, int* __restrict__ un_list, int* __restrict__ d_nun,
+                                                    int keep_unresolved) {
+    const int qi = blockIdx.x * 4 + wave_id();
+    if (qi >= n) return;
+    const int frame = frame_of[qi];
+    if (!ctrl[frame].active) return;
+    const int own0 = goff[frame], own_n = goff[frame + 1] - own0;  // the frame's points are one index range of G
+    const int lane = lane_id();
+    const float4 q = cur[qi];
+    const int cx = rf_coord(q.x, RF_XB), cy = rf_coord(q.y, RF_XB), cz = rf_coord(q.z, RF_ZB);
+    unsigned long long bk = ~0ull;
+    bool done = false;
+    for (int k = 1; k <= RF_RINGS && !done; ++k) {
+        const int w = 2 * k + 1, ncube = w * w * w;
+        for (int j0 = 0; j0 < ncube; j0 += 64) {  // 64 cells at a time, one per lane
+            const int j = j0 + lane;
+            int s0 = 0, cnt = 0;
+            if (j < ncube) {
+                const int jz = j / (w * w), rem = j - jz * w * w, jy = rem / w, jx = rem - jy * w;
+                const int ax = jx - k, ay = jy - k, az = jz - k;
+                const bool fresh = k == 1 || max(max(abs(ax), abs(ay)), abs(az)) == k;  // inner cells were examined in an earlier ring
+                const unsigned long long key = fresh ? rf_key(cx + ax, cy + ay, cz + az) : RF_NO_CELL;
+                if (key != RF_NO_CELL) {
+                    unsigned slot = rf_slot(key, mask);
+                    for (;;) {
+                        const unsigned long long hk = hkeys[slot];
+                        if (hk == key) {
+                            const int2 r = hrange[slot];
+                            s0 = r.x, cnt = r.y - r.x;
+                            break;
+                        }
+                        if (hk == RF_EMPTY) break;
+                        slot = (slot + 1) & mask;
+                    }
+                }
+            }
+            // the points of these cells as one list spread over the lanes (k_icp_grid_nn)
+            const int incl = wave_inclusive_scan(cnt);
+            const int total = __shfl(incl, 63, 64);
+            const int excl = incl - cnt;
+            for (int base = 0; base < total; base += 64) {
+                const int t = base + lane;
+                int owner = 0;
+#pragma unroll
+                for (int step = 32; step > 0; step >>= 1) {
+                    const int v = __shfl(incl, owner + step - 1, 64);
+                    if (v <= t) owner += step;
+                }
+                owner = min(owner, 63);
+                const int idx = __shfl(s0, owner, 64) + (t - __shfl(excl, owner, 64));
+                if (t < total) {
+                    const float4 p = sorted[idx];
+                    const int ti = __float_as_int(p.w);
+                    if (static_cast<unsigned>(ti - own0) >= static_cast<unsigned>(own_n)) {  // not of the query's own frame
+                        const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
+                        float d = dx * dx;  // the dense sweep's arithmetic
+                        d += dy * dy;
+                        d += dz * dz;
+                        if (d < 3.4e38f) {
+                            const unsigned long long key = (static_cast<unsigned long long>(__float_as_uint(d)) << 32) | static_cast<unsigned>(ti);
+                            bk = key < bk ? key : bk;
+                        }
+                    }
+                }
+            }
+        }
+        bk = wave_min_u64(bk);
+        const float bound = (static_cast<float>(k) - 0.05f) * RF_CELL;
+        done = bk != ~0ull && __uint_as_float(static_cast<unsigned>(bk >> 32)) < bound * bound;
+    }
+    if (lane == 0) {
+        if (done)
+            best[qi] = bk;
+        else if (keep_unresolved)  // else: nothing within the last ring's bound, and max_corr_dist does not reach beyond it
+            un_list[atomicAdd(d_nun, 1)] = qi;
+    }
+}
+
+// exact nearest neighbour of the *d_nq listed queries among all of G but their own frame (k_icp_nn's sweep and keys); the
+// workgroups stride over the (query tile, target chunk) pairs, so an empty list costs RF_DENSE_WG early returns
+__global__ void __launch_bounds__(256) k_rf_dense(const float4* __restrict__ cur, const float4* __restrict__ tgt, int n_tgt, const int* __restrict__ frame_of,
+                                                  const int* __restrict__ goff, unsigned long long* __restrict__ best, const int* __restrict__ qlist,
+                                                  const int* __restrict__ d_nq) {
+    __shared__ float4 st[RF_TC];
+    const int nq = *d_nq;
+    if (nq == 0) return;
+    const long long n_qt = (nq + RF_QT - 1) / RF_QT, n_tc = (n_tgt + RF_TC - 1) / RF_TC;
+    for (long long w = blockIdx.x; w < n_qt * n_tc; w += gridDim.x) {
+        const int qt = static_cast<int>(w / n_tc), t0 = static_cast<int>(w % n_tc) * RF_TC;
+        const int tn = min(RF_TC, n_tgt - t0);
+        __syncthreads();  // the previous pair's chunk has been read
+        for (int i = threadIdx.x; i < tn; i += 256) st[i] = tgt[t0 + i];
+        __syncthreads();
+        float qx[RF_QPT], qy[RF_QPT], qz[RF_QPT], bd[RF_QPT];
+        int bi[RF_QPT], qid[RF_QPT], own0[RF_QPT];
+        unsigned own_n[RF_QPT];
+#pragma unroll
+        for (int u = 0; u < RF_QPT; ++u) {
+            const int qi = qt * RF_QT + u * 256 + threadIdx.x;
+            qid[u] = qi < nq ? qlist[qi] : -1;
+            const float4 q = qid[u] >= 0 ? cur[qid[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const int f = qid[u] >= 0 ? frame_of[qid[u]] : 0;
+            own0[u] = goff[f] - t0, own_n[u] = qid[u] >= 0 ? static_cast<unsigned>(goff[f + 1] - goff[f]) : 0u;
+            qx[u] = q.x, qy[u] = q.y, qz[u] = q.z, bd[u] = 3.4e38f, bi[u] = -1;
+        }
+#pragma unroll 2
+        for (int t = 0; t < tn; ++t) {
+            const float4 p = st[t];
+#pragma unroll
+            for (int u = 0; u < RF_QPT; ++u) {
+                const float dx = qx[u] - p.x, dy = qy[u] - p.y, dz = qz[u] - p.z;
+                float d = dx * dx;  // FLANN L2_Simple<float>
+                d += dy * dy;
+                d += dz * dz;
+                // ascending t: the lowest index of equal distances is kept; own-frame points are no candidates
+                if (d < bd[u] && static_cast<unsigned>(t - own0[u]) >= own_n[u]) bd[u] = d, bi[u] = t;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RF_QPT; ++u) {
+            if (qid[u] >= 0 && bi[u] >= 0)
+                atomicMin(&best[qid[u]], (static_cast<unsigned long long>(__float_as_uint(bd[u])) << 32) | static_cast<unsigned>(t0 + bi[u]));
+        }
+    }
+}
+
+// partial sums of one workgroup of 256 source points of one frame (k_icp_reduce's additions); resets the keys for the next sweep
+__global__ void __launch_bounds__(256) k_rf_reduce(const float4* __restrict__ cur, const float4* __restrict__ tgt, const RfBlock* __restrict__ blocks,
+                                                   const RfCtrl* __restrict__ ctrl, unsigned long long* __restrict__ best, float max2,
+                                                   double* __restrict__ partials) {
+    __shared__ double red[4][RF_NSUM];
+    const RfBlock b = blocks[blockIdx.x];
+    if (!ctrl[b.frame].active) return;
+    const int i = b.first + threadIdx.x;
+    double v[RF_NSUM];
+#pragma unroll
+    for (int k = 0; k < RF_NSUM; ++k) v[k] = 0.0;
+    if (i < b.end) {
+        const unsigned long long key = best[i];
+        best[i] = ~0ull;
+        const float d = __uint_as_float(static_cast<unsigned>(key >> 32));
+        if (key != ~0ull && !(d > max2)) {
+            const float4 p = cur[i];
+            const float4 q = tgt[static_cast<unsigned>(key & 0xffffffffu)];
+            v[0] = 1.0;
+            v[1] = p.x, v[2] = p.y, v[3] = p.z;
+            v[4] = q.x, v[5] = q.y, v[6] = q.z;
+            const double qq[3] = {q.x, q.y, q.z}, pp[3] = {p.x, p.y, p.z};
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[7 + 3 * r + c] = qq[r] * pp[c];
+            v[16] = d;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < RF_NSUM; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane_id() == 0) red[wave_id()][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < RF_NSUM) partials[static_cast<size_t>(blockIdx.x) * RF_NSUM + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// one workgroup per frame: its workgroup partials in workgroup order -> host_out[frame][17] (pinned, device-visible memory)
+__global__ void __launch_bounds__(64) k_rf_final(const double* __restrict__ partials, const int* __restrict__ fb0, const RfCtrl* __restrict__ ctrl,
+                                                 double* __restrict__ host_out, int* __restrict__ d_nun) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *d_nun = 0;  // the unresolved-query list is consumed by now
+    const int f = blockIdx.x;
+    if (!ctrl[f].active) return;
+    if (threadIdx.x < RF_NSUM) {
+        double s = 0.0;
+        for (int b = fb0[f]; b < fb0[f + 1]; ++b) s += partials[static_cast<size_t>(b) * RF_NSUM + threadIdx.x];
+        host_out[f * RF_NSUM + threadIdx.x] = s;
+    }
+}
+
+}  // namespace scal
+
+using namespace scal;
+
+struct scal_refine {
+    scal_refine_config cfg;
+    LaneStream stream;  // released by `delete c`, after scal_refine_destroy has synchronised it
+    int nb_mm_cap = 0, nb_cap = 0;  // workgroups of the move (<= max_points / 1024 + max_frames) and of a sweep (<= max_points / 256 + max_frames)
+    unsigned hmask = 0;
+    DevBuf<float4> loc, g, cur, sorted;  // loc: host records staged in (scal_refine_run), allocated on first use
+    DevBuf<int> frame_of, un_list, d_misc;  // d_misc: [0] unresolved count, [1] n (the sort's device count)
+    DevBuf<unsigned long long> best, keys, hkeys;
+    DevBuf<int> vals;
+    DevBuf<int2> hrange;
+    RadixSort sorter;
+    DevBuf<MMBlock> mm_blocks;
+    DevBuf<int> blk;       // kept points per move workgroup, then their exclusive prefix
+    DevBuf<double> poses, partials;
+    DevBuf<RfBlock> blocks;
+    DevBuf<int> goff, fb0;
+    DevBuf<RfCtrl> ctrl;
+    PinBuf<MMBlock> h_mm_blocks;
+    PinBuf<int> h_blk, h_goff, h_fb0;
+    PinBuf<double> h_poses, h_sums;
+    PinBuf<RfBlock> h_blocks;
+    PinBuf<RfCtrl> h_ctrl;
+};
+
+extern "C" int scal_refine_create(const scal_refine_config* cfg, scal_refine_t** out) { return refine_create_on_lane(cfg, 0, out); }
+
+int scal::refine_create_on_lane(const scal_refine_config* cfg, int lane, scal_refine_t** out) {
+    if (!cfg || !out || cfg->max_frames <= 0 || cfg->max_points <= 0 || cfg->max_iterations <= 0 || !(cfg->max_corr_dist > 0) ||
+        !(cfg->fitness_gate == cfg->fitness_gate) || cfg->max_points > (1 << 30)) {
+        set_error("scal_refine_create: bad argument");
+        return SCAL_E_ARG;
+    }
+    *out = nullptr;
+    SCAL_TRY(select_device(cfg->device));
+    auto* c = new scal_refine();
+    c->cfg = *cfg;
+    const size_t np = static_cast<size_t>(cfg->max_points), nf = static_cast<size_t>(cfg->max_frames);
+    c->nb_mm_cap = static_cast<int>(np / MM_TILE + nf);
+    c->nb_cap = static_cast<int>(np / 256 + nf);
+    size_t slots = 1024;
+    while (slots < 2 * np) slots <<= 1;
+    c->hmask = static_cast<unsigned>(slots - 1);
+    int rc = SCAL_OK;
+    auto A = [&](int r) { if (rc == SCAL_OK) rc = r; };
+    A(c->g.alloc(np)); A(c->cur.alloc(np)); A(c->sorted.alloc(np)); A(c->frame_of.alloc(np)); A(c->un_list.alloc(np)); A(c->d_misc.alloc(2));
+    A(c->best.alloc(np)); A(c->keys.alloc(np)); A(c->vals.alloc(np)); A(c->hkeys.alloc(slots)); A(c->hrange.alloc(slots));
+    A(c->sorter.init(cfg->max_points));
+    A(c->mm_blocks.alloc(c->nb_mm_cap)); A(c->h_mm_blocks.alloc(c->nb_mm_cap)); A(c->blk.alloc(c->nb_mm_cap)); A(c->h_blk.alloc(c->nb_mm_cap));
+    A(c->poses.alloc(12 * nf)); A(c->h_poses.alloc(12 * nf)); A(c->partials.alloc(static_cast<size_t>(RF_NSUM) * c->nb_cap));
+    A(c->blocks.alloc(c->nb_cap)); A(c->h_blocks.alloc(c->nb_cap));
+    A(c->goff.alloc(nf + 1)); A(c->h_goff.alloc(nf + 1)); A(c->fb0.alloc(nf + 1)); A(c->h_fb0.alloc(nf + 1));
+    A(c->ctrl.alloc(nf)); A(c->h_ctrl.alloc(nf)); A(c->h_sums.alloc(RF_NSUM * nf));
+    if (rc == SCAL_OK) rc = c->stream.acquire(cfg->device, lane);
+    if (rc == SCAL_OK && (hipMemsetAsync(c->d_misc.p, 0, 2 * sizeof(int), c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = SCAL_E_HIP;
+    if (rc != SCAL_OK) {
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return SCAL_OK;
+}
+
+extern "C" void scal_refine_destroy(scal_refine_t* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->cfg.device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    delete c;
+}
+
+static int refine_check_args(scal_refine* c, const float* xyzi, const int* offsets, int n_frames, double* poses12, double near_thres, int rounds,
+                             scal_refine_frame_result* res, int* rounds_run) {
+    if (!c || !offsets || !poses12 || !res || !rounds_run || n_frames < 0 || rounds < 1 || !(near_thres == near_thres) || std::isinf(near_thres)) {
+        set_error("scal_refine_run: bad argument");
+        return SCAL_E_ARG;
+    }
+    if (n_frames > c->cfg.max_frames) {
+        set_error("scal_refine_run: %d frames exceed max_frames %d", n_frames, c->cfg.max_frames);
+        return SCAL_E_TOO_MANY;
+    }
+    if (offsets[0] != 0) {
+        set_error("scal_refine_run: offsets[0] must be 0");
+        return SCAL_E_ARG;
+    }
+    for (int f = 0; f < n_frames; ++f)
+        if (offsets[f + 1] < offsets[f]) {
+            set_error("scal_refine_run: offsets must not decrease");
+            return SCAL_E_ARG;
+        }
+    if (offsets[n_frames] > c->cfg.max_points) {
+        set_error("scal_refine_run: %d points exceed max_points %d", offsets[n_frames], c->cfg.max_points);
+        return SCAL_E_TOO_MANY;
+    }
+    if (offsets[n_frames] > 0 && !xyzi) {
+        set_error("scal_refine_run: bad argument");
+        return SCAL_E_ARG;
+    }
+    return SCAL_OK;
+}
+
+namespace {
+struct RfFrame {
+    IcpIterState is;
+    bool runs = false;    // not fixed and not empty: takes part in this round
+    bool active = false;  // still iterating
+};
+}  // namespace
+
+// one sweep of the frames marked active in h_ctrl (already uploaded): sums -> c->h_sums (waits)
+static int refine_sweep(scal_refine* c, int n, int n_frames, int nb, float max2, bool dense) {
+    hipStream_t s = c->stream;
+    SCAL_LAUNCH_PROF("k_rf_grid_nn", k_rf_grid_nn, dim3(div_up(n, 4)), dim3(256), 0, s, c->cur.p, n, c->frame_of.p, c->goff.p, c->ctrl.p, c->hkeys.p,
+                     c->hrange.p, c->hmask, c->sorted.p, c->best.p, c->un_list.p, c->d_misc.p, dense ? 1 : 0);
+    if (dense)
+        SCAL_LAUNCH_PROF("k_rf_dense", k_rf_dense, dim3(RF_DENSE_WG), dim3(256), 0, s, c->cur.p, c->g.p, n, c->frame_of.p, c->goff.p, c->best.p,
+                         c->un_list.p, c->d_misc.p);
+    SCAL_LAUNCH_PROF("k_rf_reduce", k_rf_reduce, dim3(nb), dim3(256), 0, s, c->cur.p, c->g.p, c->blocks.p, c->ctrl.p, c->best.p, max2, c->partials.p);
+    hipLaunchKernelGGL(k_rf_final, dim3(n_frames), dim3(64), 0, s, c->partials.p, c->fb0.p, c->ctrl.p, c->h_sums.p, c->d_misc.p);
+    SCAL_HIP(hipGetLastError());
+    SCAL_HIP(hipStreamSynchronize(s));
+    return SCAL_OK;
+}
+
+static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets, int K, double* poses12, const unsigned char* fixed, double near_thres,
+                         int rounds, scal_refine_frame_result* res, int* rounds_run) {
+    hipStream_t s = c->stream;
+    *rounds_run = 0;
+    const double dmax = std::numeric_limits<double>::max();
+    for (int f = 0; f < K; ++f) {
+        std::memset(&res[f], 0, sizeof res[f]);
+        for (int k = 0; k < 4; ++k) res[f].T[5 * k] = 1.0;
+        res[f].fitness = dmax;
+    }
+    if (K == 0) return SCAL_OK;
+    // the move's workgroups: the same for every round
+    int nb_mm = 0;
+    for (int f = 0; f < K; ++f)
+        for (int i = offsets[f]; i < offsets[f + 1]; i += MM_TILE) c->h_mm_blocks.p[nb_mm++] = MMBlock{i, offsets[f + 1], f};
+    if (nb_mm) SCAL_HIP(hipMemcpyAsync(c->mm_blocks.p, c->h_mm_blocks.p, sizeof(MMBlock) * nb_mm, hipMemcpyHostToDevice, s));
+    const float max2 = static_cast<float>(c->cfg.max_corr_dist * c->cfg.max_corr_dist);
+    const float last_bound = (static_cast<float>(RF_RINGS) - 0.05f) * RF_CELL;
+    // a query the rings leave unsettled has nothing nearer than last_bound: it only needs the dense sweep when the cap reaches further
+    const bool dense = !(max2 < last_bound * last_bound);
+    const double te = c->cfg.transformation_epsilon, fe = c->cfg.fitness_epsilon;
+    std::vector<RfFrame> fr(K);
+    for (int round = 0; round < rounds; ++round) {
+        // 1. G = every frame moved by its pose
+        std::memcpy(c->h_poses.p, poses12, sizeof(double) * 12 * K);
+        SCAL_HIP(hipMemcpyAsync(c->poses.p, c->h_poses.p, sizeof(double) * 12 * K, hipMemcpyHostToDevice, s));
+        int n = 0;
+        if (nb_mm) {
+            hipLaunchKernelGGL(k_rf_count, dim3(nb_mm), dim3(256), 0, s, d_loc, c->mm_blocks.p, near_thres, c->blk.p);
+            SCAL_HIP(hipMemcpyAsync(c->h_blk.p, c->blk.p, sizeof(int) * nb_mm, hipMemcpyDeviceToHost, s));
+            SCAL_HIP(hipStreamSynchronize(s));
+            for (int b = 0; b < nb_mm; ++b) {  // exclusive prefix; a frame's offset in G is that of its first workgroup
+                const int cnt = c->h_blk.p[b];
+                c->h_blk.p[b] = n;
+                n += cnt;
+            }
+        }
+        int b_mm = 0, nb = 0;
+        for (int f = 0; f < K; ++f) {
+            const int n_wg = div_up(offsets[f + 1] - offsets[f], MM_TILE);
+            c->h_goff.p[f] = n_wg ? c->h_blk.p[b_mm] : (b_mm < nb_mm ? c->h_blk.p[b_mm] : n);
+            b_mm += n_wg;
+        }
+        c->h_goff.p[K] = n;
+        for (int f = 0; f < K; ++f) {  // the sweeps' workgroups: 256 points counted from the frame's own first point
+            c->h_fb0.p[f] = nb;
+            for (int i = c->h_goff.p[f]; i < c->h_goff.p[f + 1]; i += 256) c->h_blocks.p[nb++] = RfBlock{i, c->h_goff.p[f + 1], f};
+        }
+        c->h_fb0.p[K] = nb;
+        bool any = false;
+        for (int f = 0; f < K; ++f) {
+            fr[f] = RfFrame();
+            const int nf = c->h_goff.p[f + 1] - c->h_goff.p[f];
+            const bool is_fixed = fixed && fixed[f];
+            fr[f].runs = fr[f].active = !is_fixed && nf > 0 && n - nf > 0;
+            if (!is_fixed && !fr[f].runs) fr[f].is.st = 5;  // pcl::Registration::align refuses empty clouds: not converged
+            any = any || fr[f].runs;
+        }
+        if (any) {
+            SCAL_HIP(hipMemcpyAsync(c->blk.p, c->h_blk.p, sizeof(int) * nb_mm, hipMemcpyHostToDevice, s));
+            SCAL_HIP(hipMemcpyAsync(c->goff.p, c->h_goff.p, sizeof(int) * (K + 1), hipMemcpyHostToDevice, s));
+            SCAL_HIP(hipMemcpyAsync(c->fb0.p, c->h_fb0.p, sizeof(int) * (K + 1), hipMemcpyHostToDevice, s));
+            SCAL_HIP(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, sizeof(RfBlock) * nb, hipMemcpyHostToDevice, s));
+            SCAL_HIP(hipMemcpyAsync(c->d_misc.p + 1, &c->h_goff.p[K], sizeof(int), hipMemcpyHostToDevice, s));
+            SCAL_LAUNCH_PROF("k_rf_write", k_rf_write, dim3(nb_mm), dim3(256), 0, s, d_loc, c->mm_blocks.p, c->poses.p, near_thres, c->blk.p,
+                             static_cast<long long>(n), c->g.p, c->frame_of.p);
+            SCAL_HIP(hipMemcpyAsync(c->cur.p, c->g.p, sizeof(float4) * n, hipMemcpyDeviceToDevice, s));
+            // 2. the neighbour index over G
+            SCAL_HIP(hipMemsetAsync(c->hkeys.p, 0xff, sizeof(unsigned long long) * (static_cast<size_t>(c->hmask) + 1), s));
+            SCAL_HIP(hipMemsetAsync(c->best.p, 0xff, sizeof(unsigned long long) * n, s));
+            hipLaunchKernelGGL(k_rf_keys, dim3(div_up(n, 256)), dim3(256), 0, s, c->g.p, n, c->keys.p, c->vals.p);
+            SortedPairs sp;
+            SCAL_TRY(c->sorter.sort(s, c->keys.p, c->vals.p, c->d_misc.p + 1, n, RF_KEY_BITS, nullptr, &sp));
+            SCAL_LAUNCH_PROF("k_rf_index", k_rf_index, dim3(div_up(n, 256)), dim3(256), 0, s, sp.keys[sp.fixed_sel], sp.vals[sp.fixed_sel], n, c->g.p,
+                             c->sorted.p, c->hkeys.p, c->hrange.p, c->hmask);
+            SCAL_HIP(hipGetLastError());
+            // 3. the iterations: one launch chain and one synchronisation each, for all frames still iterating
+            bool first = true;
+            for (;;) {
+                bool go = false;
+                for (int f = 0; f < K; ++f) {
+                    c->h_ctrl.p[f].active = fr[f].active ? 1 : 0;
+                    go = go || fr[f].active;
+                }
+                if (!go) break;
+                SCAL_HIP(hipMemcpyAsync(c->ctrl.p, c->h_ctrl.p, sizeof(RfCtrl) * K, hipMemcpyHostToDevice, s));
+                if (!first) hipLaunchKernelGGL(k_rf_apply, dim3(nb), dim3(256), 0, s, c->cur.p, c->blocks.p, c->ctrl.p);
+                first = false;
+                SCAL_TRY(refine_sweep(c, n, K, nb, max2, dense));
+                for (int f = 0; f < K; ++f) {
+                    if (!fr[f].active) continue;
+                    float T[16];
+                    const int step = icp_host_step(fr[f].is, c->h_sums.p + RF_NSUM * f, c->cfg.max_iterations, te, fe, T);
+                    if (step == ICP_STEP_CONTINUE)
+                        std::memcpy(c->h_ctrl.p[f].m, T, sizeof(float) * 12);
+                    else  // finished: the fitness sweep moves the frame by the whole transformation, the last increment need not be applied
+                        fr[f].active = false;
+                }
+            }
+            // 4. fitness: the moved frame by the whole transformation, one more sweep with the same cap
+            for (int f = 0; f < K; ++f) {
+                c->h_ctrl.p[f].active = fr[f].runs ? 1 : 0;
+                std::memcpy(c->h_ctrl.p[f].m, fr[f].is.F, sizeof(float) * 12);
+            }
+            SCAL_HIP(hipMemcpyAsync(c->ctrl.p, c->h_ctrl.p, sizeof(RfCtrl) * K, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_rf_apply_from, dim3(nb), dim3(256), 0, s, c->g.p, c->cur.p, c->blocks.p, c->ctrl.p);
+            SCAL_TRY(refine_sweep(c, n, K, nb, max2, dense));
+        }
+        // 5. results and poses
+        bool moved = false;
+        for (int f = 0; f < K; ++f) {
+            scal_refine_frame_result& r = res[f];
+            const IcpIterState& is = fr[f].is;
+            r.converged = is.converged ? 1 : 0, r.iterations = is.it, r.state = is.st, r.n_correspondences = is.n_corr;
+            const double* sums = c->h_sums.p + RF_NSUM * f;
+            r.fitness = fr[f].runs && sums[0] > 0 ? sums[16] / sums[0] : dmax;
+            for (int k = 0; k < 16; ++k) r.T[k] = is.F[k];
+            r.accepted = fr[f].runs && is.converged && r.fitness <= c->cfg.fitness_gate ? 1 : 0;
+            if (!r.accepted) continue;
+            double* P = poses12 + 12 * f;
+            double Q[12];
+            for (int rr = 0; rr < 3; ++rr)
+                for (int cc = 0; cc < 4; ++cc) {
+                    const double F0 = is.F[4 * rr], F1 = is.F[4 * rr + 1], F2 = is.F[4 * rr + 2];
+                    double v = (F0 * P[cc] + F1 * P[4 + cc]) + F2 * P[8 + cc];
+                    if (cc == 3) v += static_cast<double>(is.F[4 * rr + 3]);
+                    Q[4 * rr + cc] = v;
+                }
+            std::memcpy(P, Q, sizeof Q);
+            const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+            moved = moved || std::memcmp(is.F, I, sizeof I) != 0;
+        }
+        *rounds_run = round + 1;
+        if (!moved) break;
+    }
+    return SCAL_OK;
+}
+
+extern "C" int scal_refine_run_device(scal_refine_t* c, const float* d_xyzi, const int* offsets, int n_frames, double* poses12, const unsigned char* fixed,
+                                      double near_thres, int rounds, scal_refine_frame_result* res, int* rounds_run) {
+    SCAL_TRY(refine_check_args(c, d_xyzi, offsets, n_frames, poses12, near_thres, rounds, res, rounds_run));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    return refine_rounds(c, reinterpret_cast<const float4*>(d_xyzi), offsets, n_frames, poses12, fixed, near_thres, rounds, res, rounds_run);
+}
+
+extern "C" int scal_refine_run(scal_refine_t* c, const float* xyzi, const int* offsets, int n_frames, double* poses12, const unsigned char* fixed,
+                               double near_thres, int rounds, scal_refine_frame_result* res, int* rounds_run) {
+    SCAL_TRY(refine_check_args(c, xyzi, offsets, n_frames, poses12, near_thres, rounds, res, rounds_run));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    const int n = offsets[n_frames];
+    if (!c->loc.p) SCAL_TRY(c->loc.alloc(static_cast<size_t>(c->cfg.max_points)));
+    if (n) SCAL_HIP(hipMemcpyAsync(c->loc.p, xyzi, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream));
+    return refine_rounds(c, c->loc.p, offsets, n_frames, poses12, fixed, near_thres, rounds, res, rounds_run);
+}

@@ -10,6 +10,8 @@ int main(void) {
     scal_features_t* f = NULL;
     scal_pipeline_config pc;
     scal_pipeline_t* p = NULL;
+    scal_refine_config rc_cfg;
+    scal_refine_t* rf = NULL;
     int rc, n = scal_device_count();
     memset(&fc, 0, sizeof fc);
     fc.lidar_type = SCAL_HDL64, fc.n_scans = 64, fc.minimum_range = 5.0, fc.max_points = 1000, fc.check_finite = 1;
@@ -26,6 +28,20 @@ int main(void) {
         printf("scal_pipeline_create accepted ring = 99\n");
         return 1;
     }
+    memset(&rc_cfg, 0, sizeof rc_cfg);
+    rc_cfg.max_corr_dist = 2.0, rc_cfg.transformation_epsilon = 1e-6, rc_cfg.fitness_epsilon = 1e-6, rc_cfg.fitness_gate = 0.3;
+    rc_cfg.max_iterations = 100, rc_cfg.max_frames = 0, rc_cfg.max_points = 1000;
+    if (scal_refine_create(&rc_cfg, &rf) != SCAL_E_ARG) {
+        printf("scal_refine_create accepted max_frames = 0\n");
+        return 1;
+    }
+    rc_cfg.max_frames = 4;
+    rc = scal_refine_create(&rc_cfg, &rf);
+    if (n < 1 && rc != SCAL_E_NO_DEVICE) {
+        printf("scal_refine_create: expected SCAL_E_NO_DEVICE without a GPU, got %d (%s)\n", rc, scal_last_error());
+        return 1;
+    }
+    if (rc == SCAL_OK) scal_refine_destroy(rf);
     printf("abi ok %s devices=%d\n", scal_version(), n);
     return 0;
 }

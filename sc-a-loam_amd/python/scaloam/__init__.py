@@ -75,6 +75,17 @@ class ICPResult(C.Structure):
                 ("fitness", C.c_double), ("T", C.c_double * 16)]
 
 
+class RefineConfig(C.Structure):
+    _fields_ = [("max_corr_dist", C.c_double), ("transformation_epsilon", C.c_double), ("fitness_epsilon", C.c_double),
+                ("fitness_gate", C.c_double), ("max_iterations", C.c_int), ("max_frames", C.c_int), ("max_points", C.c_int),
+                ("device", C.c_int)]
+
+
+class RefineFrameResult(C.Structure):
+    _fields_ = [("converged", C.c_int), ("iterations", C.c_int), ("state", C.c_int), ("n_correspondences", C.c_int),
+                ("accepted", C.c_int), ("fitness", C.c_double), ("T", C.c_double * 16)]
+
+
 class MapMergeConfig(C.Structure):
     _fields_ = [("max_points", C.c_longlong), ("max_frame_points", C.c_int), ("device", C.c_int)]
 
@@ -144,6 +155,7 @@ EXPORTED_SYMBOLS = [
     "scal_map_create", "scal_map_destroy", "scal_map_step", "scal_map_step_features", "scal_map_export", "scal_map_export_all", "scal_map_get_wmap_wodom", "scal_map_set_merge_insert", "scal_map_get_path_counters", "scal_map_set_poll", "scal_map_debug_set_lm_polls", "scal_map_debug_set_grid_cap", "scal_map_adapter_begin", "scal_map_associate", "scal_map_get_blocks", "scal_map_eval_blocks", "scal_map_adapter_finish", "scal_odom_adapter_begin", "scal_odom_associate", "scal_odom_get_blocks", "scal_odom_eval_blocks", "scal_odom_adapter_finish", "scal_map_prefetch_features", "scal_map_prefetch_begin", "scal_map_prefetch_finish", "scal_map_enqueue_features", "scal_map_collect", "scal_map_finish",
     "scal_set_stream_mode", "scal_mapmerge_create", "scal_mapmerge_destroy", "scal_mapmerge_reset", "scal_mapmerge_add",
     "scal_mapmerge_add_batch_device", "scal_mapmerge_size", "scal_mapmerge_download", "scal_mapmerge_device_points", "scal_mapmerge_downsample", "scal_icp_create", "scal_icp_destroy", "scal_icp_align", "scal_icp_align_device", "scal_icp_set_search",
+    "scal_refine_create", "scal_refine_destroy", "scal_refine_run_device", "scal_refine_run",
     "scal_odom_create", "scal_odom_destroy", "scal_odom_step", "scal_odom_step_features", "scal_odom_enqueue_features", "scal_odom_collect",
     "scal_factors_eval",
     "scal_pipeline_create", "scal_pipeline_destroy", "scal_pipeline_push_device", "scal_pipeline_push_host", "scal_pipeline_pop", "scal_pipeline_drain",
@@ -252,6 +264,12 @@ def lib():
     L.scal_icp_align.argtypes = [vp, _f32p, C.c_int, _f32p, C.c_int, C.POINTER(ICPResult)]
     L.scal_icp_set_search.argtypes = [vp, C.c_int]
     L.scal_icp_align_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.POINTER(ICPResult)]
+    if hasattr(L, "scal_refine_create"):  # absent from older builds compared through SCALOAM_LIB
+        L.scal_refine_create.argtypes = [C.POINTER(RefineConfig), C.POINTER(vp)]
+        L.scal_refine_destroy.argtypes = [vp]
+        L.scal_refine_destroy.restype = None
+        for fn in (L.scal_refine_run_device, L.scal_refine_run):
+            fn.argtypes = [vp, vp, _i32p, C.c_int, _f64p, C.c_char_p, C.c_double, C.c_int, C.POINTER(RefineFrameResult), _i32p]
     L.scal_mapmerge_create.argtypes = [C.POINTER(MapMergeConfig), C.POINTER(vp)]
     L.scal_mapmerge_destroy.argtypes = [vp]
     L.scal_mapmerge_destroy.restype = None
@@ -832,6 +850,60 @@ class LoopICP:
         _check(lib().scal_icp_align(self.h, _p(s, _f32p), s.shape[0], _p(t, _f32p), t.shape[0], C.byref(r)))
         return dict(converged=bool(r.converged), iterations=r.iterations, state=r.state, n_correspondences=r.n_correspondences,
                     fitness=r.fitness, T=np.array(r.T[:]).reshape(4, 4))
+
+
+class MultiviewRefine:
+    """scal_refine: all keyframes of a session aligned at once, each by point-to-point ICP against the points of all the others, in
+    Jacobi rounds (include/scaloam_hip.h).  The ICP settings are the reference's (laserPosegraphOptimization.cpp:518-531) except
+    max_corr_dist: 2 m instead of 150 m, which across a whole session pairs every point with something however far (the header has
+    the numbers)."""
+
+    def __init__(self, max_frames, max_points, max_corr_dist=2.0, max_iterations=100, transformation_epsilon=1e-6, fitness_epsilon=1e-6,
+                 fitness_gate=0.3, device=0):
+        self.h = C.c_void_p()
+        cfg = RefineConfig(max_corr_dist, transformation_epsilon, fitness_epsilon, fitness_gate, max_iterations, int(max_frames),
+                           int(max_points), device)
+        _check(lib().scal_refine_create(C.byref(cfg), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.scal_refine_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def _run(self, fn, ptr, offsets, poses12, fixed, rounds, near_thres):
+        off = np.ascontiguousarray(offsets, np.int32)
+        k = off.shape[0] - 1
+        P = np.array(poses12, np.float64).reshape(-1, 12).copy()
+        if k < 0 or P.shape[0] != k:
+            raise ValueError("one pose12 row per frame and offsets of n_frames + 1 entries are needed")
+        fx = None
+        if fixed is not None:
+            fx = np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8)
+            if fx.shape[0] != k:
+                raise ValueError("one fixed flag per frame is needed")
+        res = (RefineFrameResult * max(k, 1))()
+        run = C.c_int(0)
+        _check(fn(self.h, ptr, _p(off, _i32p), k, _p(P, _f64p), fx.ctypes.data_as(C.c_char_p) if fx is not None else None,
+                  float(near_thres), int(rounds), res, C.byref(run)))
+        out = [dict(converged=bool(r.converged), iterations=r.iterations, state=r.state, n_correspondences=r.n_correspondences,
+                    accepted=bool(r.accepted), fitness=r.fitness, T=np.array(r.T[:]).reshape(4, 4)) for r in res[:k]]
+        return P, out, run.value
+
+    def refine(self, frames, poses12, fixed=None, rounds=1, near_thres=2.0):
+        """frames: a list of [n, 4] xyzi arrays in their local frames; returns (poses12 [K, 12], per-frame dicts, rounds_run)"""
+        fs = [_f32(f).reshape(-1, 4) for f in frames]
+        off = np.zeros(len(fs) + 1, np.int64)
+        off[1:] = np.cumsum([f.shape[0] for f in fs])
+        if off[-1] > 2**31 - 1:
+            raise ValueError("more points than 32-bit offsets hold")
+        cat = np.ascontiguousarray(np.concatenate(fs, 0)) if fs else np.zeros((0, 4), np.float32)
+        return self._run(lib().scal_refine_run, cat.ctypes.data_as(C.c_void_p), off, poses12, fixed, rounds, near_thres)
+
+    def refine_device(self, d_xyzi_ptr, offsets, poses12, fixed=None, rounds=1, near_thres=2.0):
+        """the frames as 16-byte xyzi records back to back in device memory, frame f = records [offsets[f], offsets[f+1])"""
+        return self._run(lib().scal_refine_run_device, d_xyzi_ptr, offsets, poses12, fixed, rounds, near_thres)
 
 
 class MapMerge:

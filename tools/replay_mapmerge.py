@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Replay of utils/python/makeMergedMap.py on the GPU: reads a session directory as the reference saves it (Scans/*.pcd +
 optimized_poses.txt), merges the keyframes into the global frame (near-range removal 2 m) with scal_mapmerge_*, writes the map as
-a binary PCD.  `--check` also runs the CPU oracle and compares bit for bit."""
+a binary PCD.  `--check` also runs the CPU oracle and compares bit for bit.  `--refine ROUNDS` first refines the poses with
+scal_refine_* (every keyframe thinned at --refine-leaf and aligned against all the others, keyframe 0 held), writes them to
+refined_poses.txt beside the session's optimized_poses.txt and merges with them."""
 import argparse
 import glob
 import os
@@ -20,6 +22,9 @@ def main():
     ap.add_argument("--near", type=float, default=2.0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--refine", type=int, default=0, metavar="ROUNDS", help="multiview refine of the poses before the merge")
+    ap.add_argument("--refine-leaf", type=float, default=0.4)
+    ap.add_argument("--max-corr", type=float, default=2.0)
     a = ap.parse_args()
     import scaloam as S
     from scaloam import formats as F
@@ -27,14 +32,27 @@ def main():
     poses = F.read_poses(os.path.join(a.data_dir, "optimized_poses.txt"))
     lo, hi = a.range if a.range else (0, min(len(files), len(poses)))
     frames = [F.read_pcd(f) for f in files[lo:hi]]
+    poses = np.asarray(poses[lo:hi], np.float64).reshape(-1, 12)
+    if a.refine > 0:
+        vg = S.VoxelGrid(max_points=max(f.shape[0] for f in frames))
+        thin = [vg.filter(f, a.refine_leaf) for f in frames]
+        rf = S.MultiviewRefine(len(thin), sum(t.shape[0] for t in thin) + 1, max_corr_dist=a.max_corr)
+        fixed = np.zeros(len(thin), np.uint8)
+        fixed[0] = 1
+        poses, res, run = rf.refine(thin, poses, fixed=fixed, rounds=a.refine, near_thres=a.near)
+        print(f"refine: {run} round(s), {sum(r['accepted'] for r in res)} of {len(res)} keyframes accepted in the last one")
+        path = os.path.join(a.data_dir, "refined_poses.txt")
+        F.write_poses(path, poses)
+        print("written", path)
+        vg.close(), rf.close()
     mm = S.MapMerge(max_points=sum(f.shape[0] for f in frames) + 1, max_frame_points=max(f.shape[0] for f in frames))
-    for f, p in zip(frames, poses[lo:hi]):
+    for f, p in zip(frames, poses):
         mm.add(f, p, a.near)
     out = mm.download()
     print(f"{len(frames)} keyframes, {sum(f.shape[0] for f in frames)} points in, {out.shape[0]} points in the map")
     if a.check:
         import oracle_py as O
-        ref = O.mapmerge(frames, poses[lo:hi], a.near)
+        ref = O.mapmerge(frames, poses, a.near)
         print("bit-exact vs oracle:", bool(ref.shape == out.shape and np.array_equal(ref.view(np.uint32), out.view(np.uint32))))
     path = a.out or os.path.join(a.data_dir, f"map_{lo}_to_{hi}_with_intensity.pcd")
     F.write_pcd_binary(path, out)
