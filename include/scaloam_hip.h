@@ -236,6 +236,26 @@ int scal_sc_shard_query_device(scal_sc_t* ctx, const double* d_queries, int nq, 
  * the 3 * nq records stay in device memory (d_out) and nothing is synchronised: follow with scal_sc_sync */
 int scal_sc_shard_query_batch_device(scal_sc_t* ctx, const double* d_queries, int nq, const int* limits, scal_sc_cand* d_out);
 int scal_sc_merge_candidates(const scal_sc_cand* gathered, int n_records, double dist_thres, scal_sc_result* res);
+/* detectLoopClosureIDBetweenSession (Scancontext.cpp:272-333) for nq query descriptors (20x60 doubles, column-major, back to back)
+ * that are NOT in the database: ring key of the query, KNN(3) over ALL keys of the database - no exclusion of recent keys, no >= 31
+ * gate, no tree period -, distanceBtnScanContext(query, candidate) for the three, strict minimum, loop_id = nn_idx iff min_dist <
+ * dist_thres, yaw_rad = deg2rad(shift * 6) as f32.  A database of one or two entries behaves as nanoflann does: unfilled KNN slots
+ * keep index 0.  Queries run in chunks of 64, one launch set per chunk; a record depends neither on nq nor on the chunking.
+ * Deviation: the reference builds its batch tree once, at the first call (is_tree_batch_made), and keeps searching that; this call
+ * searches the database as it is at the call - the same whenever nothing was inserted in between.
+ * SCAL_E_STATE: empty database.  SCAL_E_ARG: sharded context, NULL pointers, nq < 0. */
+int scal_sc_detect_between(scal_sc_t* db, const double* query_descs_colmajor /* host [nq][1200] */, int nq, scal_sc_result* res /* [nq] */);
+/* the same with the descriptors in device memory (complete before the call, or scal_sc_stream ordered behind their producer) */
+int scal_sc_detect_between_device(scal_sc_t* db, const double* d_query_descs, int nq, scal_sc_result* res);
+/* scal_sc_distance_matrix with the query rows taken from entries [q0, q1) of ANOTHER context on the same device (`queries` may also
+ * be `db` itself): row-major [q][d] over database entries [d0, d1), modes 0-3 as above, bit-identical to the block a single context
+ * holding both sets of descriptors would give.  The work is queued on db's stream behind everything queued on queries' stream
+ * (an event); the call waits for it.  SCAL_E_ARG: a sharded context, different devices, a range outside either context. */
+int scal_sc_cross_matrix(scal_sc_t* db, scal_sc_t* queries, int q0, int q1, int d0, int d1, int mode, double* dist, int* shift);
+/* scal_sc_batch_loop_search with the query rows from another context: for every query entry q in [q0, q1) of `queries` the k (<= 16)
+ * smallest distances over ALL entries of db (no entry is "too recent" for a query from another session).  Outputs [q1 - q0][k]:
+ * database index (-1 = fewer than k entries), distance, column shift; ascending distance, ties to the lower index. */
+int scal_sc_cross_search(scal_sc_t* db, scal_sc_t* queries, int q0, int q1, int k, int mode, int* idx, double* dist, int* shift);
 
 /* ------------------------------------------------------------------ stage C: scan-to-map
  * Replaces process(), src/laserMapping.cpp:310-802 and :845-849. */
@@ -435,6 +455,16 @@ int scal_icp_align_device(scal_icp_t* ctx, const float* d_src_xyzi, int n_src, c
  * 0 = dense sweep only.  Both stand in for pcl::KdTreeFLANN::nearestKSearch(k=1) (pcl/registration/impl/icp.hpp) and give the
  * same correspondences, lowest target index on equal distances. */
 int scal_icp_set_search(scal_icp_t* ctx, int mode);
+/* icp.align(output, guess): pcl::Registration::align with an initial transformation (row-major 4x4, f32).  The working copy of the
+ * source is moved once by the guess (the f32 arithmetic of every later increment) and the accumulated transformation starts at the
+ * guess instead of the identity; iteration, convergence criteria and states are those of scal_icp_align.  T is the whole
+ * transformation, guess included, and fitness is that of the ORIGINAL source moved by T.  guess == NULL or the identity matrix is
+ * scal_icp_align launch for launch, with identical results.  SCAL_E_ARG: a guess that is not finite or whose last row is not
+ * 0 0 0 1 (the context stays usable). */
+int scal_icp_align_guess(scal_icp_t* ctx, const float* src_xyzi, int n_src, const float* tgt_xyzi, int n_tgt, const float guess[16],
+                         scal_icp_result* res);
+int scal_icp_align_guess_device(scal_icp_t* ctx, const float* d_src_xyzi, int n_src, const float* d_tgt_xyzi, int n_tgt, const float guess[16],
+                                scal_icp_result* res);
 
 /* ------------------------------------------------------------------ multiview refine (BASELINE.json config #5, "global ICP refine")
  * An extension: the reference has no counterpart.  All K keyframes of a session are aligned at once, in Jacobi rounds.  One round:
@@ -728,6 +758,74 @@ int scal_posegraph_get_nodes(scal_posegraph_t* g, double* pose7 /* [n][7] */, in
  * loops were down-weighted.  SCAL_E_ARG unless n = the number of edges; SCAL_E_STATE before the first optimize on these edges. */
 int scal_posegraph_get_edge_weights(scal_posegraph_t* g, double* w /* [n] */, int n);
 
+/* ------------------------------------------------------------------ relocalisation against a stored session
+ * An extension: the reference's README lists "SLAM with multi-session localization" as a TODO and ships its two hooks uncalled
+ * (saveScancontextAndKeys, Scancontext.cpp:236-246; detectLoopClosureIDBetweenSession, :272-333).  A context holds one saved session -
+ * per keyframe its Scans/NNNNNN.pcd cloud, its line of optimized_poses.txt and its descriptor - and answers "where is this scan in
+ * it": scal_sc_detect_between finds the place, ICP against a submap around it verifies it and gives the pose.
+ *
+ * add_keyframe does what the node does before it stores a keyframe (laserPosegraphOptimization.cpp:629-639): VoxelGrid(leaf) of the
+ * cloud (the device filter of scal_voxel_*), the filtered cloud into an xyzi arena in HBM, the descriptor from the filtered cloud
+ * (makeAndSaveScancontextAndKeys) or as given by the caller (saveScancontextAndKeys of a reloaded SCDs/NNNNNN.scd).
+ *
+ * query, one launch chain on the context's stream (every part of the context runs on that one stream); the clouds never leave HBM:
+ *  1. source = VoxelGrid(leaf) of the query cloud;
+ *  2. its descriptor and keys (not inserted);
+ *  3. scal_sc_detect_between; loop_id < 0: status 0, nothing more runs.  c = loop_id;
+ *  4. target = the stored clouds of keyframes j in [c - h, c + h] (h = submap_half) that exist, in keyframe order, each brought into
+ *     keyframe c's frame, then VoxelGrid(leaf).  Keyframe c's cloud is copied unchanged; every other j is moved by
+ *     M_j = P_c^-1 P_j, computed in f64 with all sums left to right and then rounded to an f32 3x4:
+ *         Ri = Rc^T,   ti[r] = -((Ri[r][0] tc[0] + Ri[r][1] tc[1]) + Ri[r][2] tc[2]),
+ *         M[r][k] = (Ri[r][0] Pj[0][k] + Ri[r][1] Pj[1][k]) + Ri[r][2] Pj[2][k]   (+ ti[r] for k = 3),
+ *     and applied with local2global's f32 arithmetic (:338-359), ((m0 x + m1 y) + m2 z) + m3 per coordinate.
+ *     DEVIATION from loopFindNearKeyframesCloud (:472-494), which moves all 2h + 1 clouds by the ROOT keyframe's single pose (:482):
+ *     inside one odometry frame that stack is what the reference verifies with, but against a stored session it would smear the
+ *     submap over 2h keyframe gaps; here every cloud is moved by its own pose;
+ *  5. guess G = Rz(-sc.yaw_rad): cos and sin of the f32 yaw taken in double and rounded to f32, G = [c s 0 0; -s c 0 0; 0 0 1 0;
+ *     0 0 0 1].  The shift comes from distanceBtnScanContext(query, candidate), which turns the CANDIDATE onto the query, hence the
+ *     sign.  no_yaw_guess = 1: the identity, as the reference's verification starts (it computes the yaw and drops it, :722).
+ *     On the golden KAIST03 keyframes (CPU oracle) ICP from the identity fails for every heading
+ *     difference of about 90 degrees or more and the guess repairs all of them;
+ *  6. scal_icp_align_guess_device(source, target, G);
+ *  7. status = 1 iff converged and fitness <= fitness_thres, else 2; pose12 = P_c T in f64 (T's f32 values promoted;
+ *     (P[r][0] T[0][k] + P[r][1] T[1][k]) + P[r][2] T[2][k], + P[r][3] for k = 3): the query's pose in the session's frame.
+ * Capacities: the arena holds max_points filtered records over all keyframes; the work buffers hold max_query_points records - one
+ * query cloud BEFORE its filter, and one submap before its filter (the sum of the stored clouds of its keyframes). */
+typedef struct {
+    int max_keyframes, max_points;   /* stored session: keyframes, xyzi records over all stored (filtered) clouds */
+    int max_query_points;            /* one query cloud before the filter (and one submap before its filter) */
+    double sc_max_radius, sc_dist_thres;   /* 0 = 80, 0.2 */
+    int float_math;
+    float leaf;                      /* 0 = 0.4 (downSizeFilterScancontext / downSizeFilterICP) */
+    int submap_half;                 /* 0 = 25 (historyKeyframeSearchNum); -1 = the candidate keyframe alone */
+    double fitness_thres;            /* 0 = 0.3 */
+    double max_corr_dist, transformation_epsilon, fitness_epsilon;   /* 0 = 150, 1e-6, 1e-6 */
+    int max_iterations;              /* 0 = 100 */
+    int no_yaw_guess;                /* 1 = start ICP from identity, as the reference's verification does */
+    int device;
+} scal_reloc_config;
+typedef struct {
+    scal_sc_result sc;       /* the between-session search */
+    int status;              /* 0 no place found (sc.loop_id < 0), 1 accepted, 2 rejected by ICP (not converged or fitness > thres) */
+    int n_src, n_tgt;        /* cloud sizes after the filters (status 0: n_tgt = 0) */
+    scal_icp_result icp;     /* T: query frame -> candidate keyframe's frame, guess included; all zero for status 0 */
+    double pose12[12];       /* status 1 or 2: P_candidate * T, the query's pose in the session's frame, row-major 3x4 */
+} scal_reloc_result;
+typedef struct scal_reloc scal_reloc_t;
+int scal_reloc_create(const scal_reloc_config* cfg, scal_reloc_t** ctx);   /* SCAL_E_NO_DEVICE without a gfx950 device */
+void scal_reloc_destroy(scal_reloc_t* ctx);
+int scal_reloc_size(scal_reloc_t* ctx);   /* keyframes stored */
+/* one keyframe of a saved session in its local frame, pose12 = its line of optimized_poses.txt; desc_colmajor NULL: the descriptor is
+ * built from the filtered cloud.  Returns the keyframe index (>= 0).  SCAL_E_CAPACITY when the arena or the database is full - nothing
+ * is stored -, SCAL_E_TOO_MANY for more than max_query_points points, SCAL_E_ARG for a pose that is not finite. */
+int scal_reloc_add_keyframe(scal_reloc_t* ctx, const float* xyzi, int n, const double pose12[12], const double* desc_colmajor_or_NULL);
+/* SCAL_E_STATE: no keyframe stored.  SCAL_E_TOO_MANY: more than max_query_points points.  SCAL_E_CAPACITY: the submap does not fit the
+ * work buffers (or a voxel grid needs more than 45 key bits).  The context stays usable after any of them. */
+int scal_reloc_query(scal_reloc_t* ctx, const float* xyzi, int n, scal_reloc_result* out);
+/* nq queries, cloud q = records [offsets[q], offsets[q + 1]): steps 1-2 for all of them, one batched search per 64 queries, then steps
+ * 4-7 per found candidate.  Every record equals the single call's bit for bit. */
+int scal_reloc_query_batch(scal_reloc_t* ctx, const float* xyzi, const int* offsets /* [nq + 1] */, int nq, scal_reloc_result* out /* [nq] */);
+scal_sc_t* scal_reloc_sc(scal_reloc_t* ctx);    /* the session's database (owned by the context), e.g. for scal_sc_cross_search between two sessions */
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,10 @@ struct ScFilterOut {
 };
 int sc_insert_features_then(scal_sc_t* ctx, scal_features_t* feat, int (*after)(void* user, hipStream_t s, const ScFilterOut& ds), void* user);
 
+// makeScancontext of a cloud in device memory (SoA planes, *d_n <= n_max points) into d_desc (1200 doubles, column-major, device
+// memory), not inserted; queued on the ScanContext stream, nothing is waited for (scal_reloc's query descriptor)
+int sc_make_cloud_device(scal_sc_t* ctx, const float* d_x, const float* d_y, const float* d_z, const int* d_n, int n_max, double* d_desc);
+
 // Owning handles in the style of DevBuf (move-only): one reference to a shared stream, released when the handle goes away ...
 struct LaneStream {
     hipStream_t s = nullptr;

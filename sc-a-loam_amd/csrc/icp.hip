@@ -422,8 +422,11 @@ static int icp_sweep(scal_icp* c, const float4* pts, int n_src, int n_tgt, float
     return SCAL_OK;
 }
 
-// clouds in host memory (on_device = false: staged into the context) or already in HBM (the target is then used in place)
-static int icp_align(scal_icp* c, const float* src_xyzi, int n_src, const float* tgt_xyzi, int n_tgt, bool on_device, scal_icp_result* res) {
+// clouds in host memory (on_device = false: staged into the context) or already in HBM (the target is then used in place).
+// guess != nullptr: pcl::Registration::align(output, guess) - the working copy of the source is moved by the guess once and the
+// accumulated transformation starts from it; nullptr is align(output), today's path launch for launch.
+static int icp_align(scal_icp* c, const float* src_xyzi, int n_src, const float* tgt_xyzi, int n_tgt, bool on_device, const float* guess,
+                     scal_icp_result* res) {
     if (!c || !res || n_src < 0 || n_tgt < 0 || (n_src && !src_xyzi) || (n_tgt && !tgt_xyzi)) {
         set_error("scal_icp_align: bad argument");
         return SCAL_E_ARG;
@@ -451,6 +454,11 @@ static int icp_align(scal_icp* c, const float* src_xyzi, int n_src, const float*
     else
         SCAL_HIP(hipMemcpyAsync(c->tgt.p, tgt_xyzi, sizeof(float) * 4 * n_tgt, hipMemcpyHostToDevice, s));
     c->tgt_cur = tgt;
+    if (guess) {
+        Mat34f G;
+        std::memcpy(G.m, guess, sizeof G.m);
+        hipLaunchKernelGGL(k_icp_apply, dim3(div_up(n_src, 256)), dim3(256), 0, s, c->cur.p, c->cur.p, n_src, G);
+    }
     hipLaunchKernelGGL(k_icp_fill, dim3(div_up(n_src, 256)), dim3(256), 0, s, c->best.p, n_src);
     c->grid_built = false;
     if (c->search == 1 && n_tgt >= 4 * ICP_TC) {  // small targets: the dense sweep is a handful of workgroups anyway
@@ -468,6 +476,7 @@ static int icp_align(scal_icp* c, const float* src_xyzi, int n_src, const float*
     const float max2 = static_cast<float>(c->cfg.max_corr_dist * c->cfg.max_corr_dist);
     const double te = c->cfg.transformation_epsilon, fe = c->cfg.fitness_epsilon;
     IcpIterState is;  // the iteration itself is icp_host.hpp's, shared with the multiview refine
+    if (guess) std::memcpy(is.F, guess, sizeof is.F);
     for (;;) {
         SCAL_TRY(icp_sweep(c, c->cur.p, n_src, n_tgt, max2));
         float T[16];
@@ -496,9 +505,42 @@ static int icp_align(scal_icp* c, const float* src_xyzi, int n_src, const float*
 }
 
 extern "C" int scal_icp_align(scal_icp_t* c, const float* src_xyzi, int n_src, const float* tgt_xyzi, int n_tgt, scal_icp_result* res) {
-    return icp_align(c, src_xyzi, n_src, tgt_xyzi, n_tgt, false, res);
+    return icp_align(c, src_xyzi, n_src, tgt_xyzi, n_tgt, false, nullptr, res);
 }
 
 extern "C" int scal_icp_align_device(scal_icp_t* c, const float* d_src_xyzi, int n_src, const float* d_tgt_xyzi, int n_tgt, scal_icp_result* res) {
-    return icp_align(c, d_src_xyzi, n_src, d_tgt_xyzi, n_tgt, true, res);
+    return icp_align(c, d_src_xyzi, n_src, d_tgt_xyzi, n_tgt, true, nullptr, res);
+}
+
+// the guess as icp_align takes it: nullptr for none or the identity (both are align(output)), the 16 f32 values otherwise
+static int icp_check_guess(const float guess[16], const float** use) {
+    *use = nullptr;
+    if (!guess) return SCAL_OK;
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(guess[k])) {
+            set_error("scal_icp_align_guess: the guess is not finite");
+            return SCAL_E_ARG;
+        }
+    if (!(guess[12] == 0.f && guess[13] == 0.f && guess[14] == 0.f && guess[15] == 1.f)) {
+        set_error("scal_icp_align_guess: the last row of the guess must be 0 0 0 1");
+        return SCAL_E_ARG;
+    }
+    bool identity = true;
+    for (int k = 0; k < 12; ++k) identity = identity && guess[k] == (k % 5 == 0 ? 1.f : 0.f);
+    if (!identity) *use = guess;
+    return SCAL_OK;
+}
+
+extern "C" int scal_icp_align_guess(scal_icp_t* c, const float* src_xyzi, int n_src, const float* tgt_xyzi, int n_tgt, const float guess[16],
+                                    scal_icp_result* res) {
+    const float* g;
+    SCAL_TRY(icp_check_guess(guess, &g));
+    return icp_align(c, src_xyzi, n_src, tgt_xyzi, n_tgt, false, g, res);
+}
+
+extern "C" int scal_icp_align_guess_device(scal_icp_t* c, const float* d_src_xyzi, int n_src, const float* d_tgt_xyzi, int n_tgt,
+                                           const float guess[16], scal_icp_result* res) {
+    const float* g;
+    SCAL_TRY(icp_check_guess(guess, &g));
+    return icp_align(c, d_src_xyzi, n_src, d_tgt_xyzi, n_tgt, true, g, res);
 }

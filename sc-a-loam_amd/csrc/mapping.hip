@@ -1093,7 +1093,12 @@ SCAL_KERNEL(512, k_merge_lookup)
 // A merge that cannot be done (merge_fail, map pool full) stops the speculative chain here: nothing has been committed yet, the
 // host redoes this insertion with the full sort and replays the steps queued behind it.
 __device__ __forceinline__ void merge_write_body(const MergeArgs& a, MapState* S, MapCounters* C) {
-    if (S->abort) return;
+    // A stop raised in front of this launch: nothing to do, as ever.  The one exception is this launch's own stop: with merge_fail
+    // set, workgroup 0 raises MAP_ABORT_MERGE below, and a workgroup that starts after that store must still clear its cells first -
+    // the full-sort redo does not touch the grid, and the set would keep stale counts for the step that builds on it next.  (A step
+    // that drains behind an earlier stop never has merge_fail set: the kernels that raise it are no-ops then.)
+    const int ab = S->abort;  // read once
+    if (ab != MAP_ABORT_NONE && !(ab == MAP_ABORT_MERGE && C->merge_fail)) return;
     if (static_cast<int>(blockIdx.x) < MERGE_WB0 + MERGE_WB1) {
         // zero invariant of the cell grid: the blocks that walk the old points clear the cells their points were binned into -
         // first of all, also when the merge is about to be called off (the full-sort redo does not touch the grid)

@@ -17,6 +17,7 @@
 #include "device_utils.hpp"
 #include "voxel_dev.hpp"
 #include "features_dev.hpp"
+#include <algorithm>
 #include <cmath>
 #include <cfloat>
 
@@ -400,21 +401,22 @@ SCAL_KERNEL(256, k_sc_pairs)
 
 // dense block of the pair grid, one wave per (query, database) pair.
 // mode 0: the reference's 7-shift search; mode 1: exhaustive over all 60 shifts (first strict minimum).
-__device__ __forceinline__ void k_sc_matrix_body(const SCDb& db, int q0, int nq, int d0, int nd, int mode, double* __restrict__ dist,
-                                                   int* __restrict__ shift) {
+// Query rows are entries of qdb, columns entries of db: the same database for a block inside one session, two for a cross-session block.
+__device__ __forceinline__ void sc_matrix_block(const SCDb& qdb, const SCDb& db, int q0, int nq, int d0, int nd, int mode, double* __restrict__ dist,
+                                                int* __restrict__ shift) {
     __shared__ double scratch[4][7 * NS];
     const int w = wave_id(), lane = lane_id();
     const long long p = static_cast<long long>(blockIdx.x) * 4 + w;
     if (p >= static_cast<long long>(nq) * nd) return;
     const int a = q0 + static_cast<int>(p / nd), b = d0 + static_cast<int>(p % nd);
-    const double* d1 = db.desc + (size_t)a * DESC;
+    const double* d1 = qdb.desc + (size_t)a * DESC;
     const double* d2 = db.desc + (size_t)b * DESC;
-    const double* n1 = db.cnorm + (size_t)a * NS;
+    const double* n1 = qdb.cnorm + (size_t)a * NS;
     const double* n2 = db.cnorm + (size_t)b * NS;
     double bd;
     int bs;
     if (mode == 0) {
-        wave_pair_distance(d1, n1, db.skey + (size_t)a * NS, d2, n2, db.skey + (size_t)b * NS, scratch[w], &bd, &bs);
+        wave_pair_distance(d1, n1, qdb.skey + (size_t)a * NS, d2, n2, db.skey + (size_t)b * NS, scratch[w], &bd, &bs);
     } else {
         // lane = shift: sequential sum over columns exactly as distDirectSC does
         double dd = 1e300;
@@ -445,7 +447,16 @@ __device__ __forceinline__ void k_sc_matrix_body(const SCDb& db, int q0, int nq,
     }
     if (lane == 0) dist[p] = bd, shift[p] = bs;
 }
+__device__ __forceinline__ void k_sc_matrix_body(const SCDb& db, int q0, int nq, int d0, int nd, int mode, double* __restrict__ dist,
+                                                   int* __restrict__ shift) {
+    sc_matrix_block(db, db, q0, nq, d0, nd, mode, dist, shift);
+}
 SCAL_KERNEL(256, k_sc_matrix)
+__device__ __forceinline__ void k_sc_matrix_cross_body(const SCDb& qdb, const SCDb& db, int q0, int nq, int d0, int nd, int mode,
+                                                         double* __restrict__ dist, int* __restrict__ shift) {
+    sc_matrix_block(qdb, db, q0, nq, d0, nd, mode, dist, shift);
+}
+SCAL_KERNEL(256, k_sc_matrix_cross)
 
 
 // ---- dense matrix on the matrix cores (mode 2) --------------------------------------------------------------------------------
@@ -716,6 +727,11 @@ struct scal_sc {
     DevBuf<int> bq_limits;
     PinBuf<int> bq_hlimits;
     int bq_cap = 0, bq_nb = 0;
+    // between-session search: one chunk of 64 queries staged from the host, its 3 x 64 records
+    DevBuf<double> bt_q;
+    DevBuf<SCRec> bt_rec;
+    PinBuf<SCRec> bt_hrec;
+    Event ev_cross;  // cross-session blocks: this context's stream behind the query context's
     // detections enqueued and not collected: 1 = search launched, 2 = database too small (nothing launched); up to DET_DEPTH in flight,
     // each with its own record slot and event, so collecting one does not wait for anything queued on the stream behind it
     static constexpr int DET_DEPTH = 4;
@@ -1070,6 +1086,21 @@ extern "C" int scal_sc_insert_descriptors_device(scal_sc_t* c, const double* d_d
     return SCAL_OK;
 }
 
+// keys, norms and per-workgroup top-3 of a batch of nq queries over nb workgroups of database keys (grown when needed)
+static int ensure_batch(scal_sc* c, int nq, int nb) {
+    if (c->bq_cap >= nq && c->bq_nb >= nb) return SCAL_OK;
+    SCAL_HIP(op_stream_synchronize(c->stream));
+    const int cq = std::max(nq, 8), cb = std::max(nb, c->bq_nb);
+    SCAL_TRY(c->bq_rkey.alloc((size_t)cq * NR));
+    SCAL_TRY(c->bq_skey.alloc((size_t)cq * NS));
+    SCAL_TRY(c->bq_norm.alloc((size_t)cq * NS));
+    SCAL_TRY(c->bq_best.alloc((size_t)cq * cb * 3));
+    SCAL_TRY(c->bq_limits.alloc(cq));
+    SCAL_TRY(c->bq_hlimits.alloc(64));
+    c->bq_cap = cq, c->bq_nb = cb;
+    return SCAL_OK;
+}
+
 // scal_sc_shard_query_device for a batch: query q uses limits[q] (the tree size at its rebuild, Scancontext.cpp:353-365);
 // three launches for the whole batch, results stay on the device (d_out[3 * nq]), no host synchronisation
 extern "C" int scal_sc_shard_query_batch_device(scal_sc_t* c, const double* d_queries, int nq, const int* limits, scal_sc_cand* d_out) {
@@ -1081,17 +1112,7 @@ extern "C" int scal_sc_shard_query_batch_device(scal_sc_t* c, const double* d_qu
     SCAL_HIP(hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
     const int nb = std::max(1, div_up(c->n_local, 256));
-    if (c->bq_cap < nq || c->bq_nb < nb) {
-        SCAL_HIP(op_stream_synchronize(s));
-        const int cq = std::max(nq, 8), cb = std::max(nb, c->bq_nb);
-        SCAL_TRY(c->bq_rkey.alloc((size_t)cq * NR));
-        SCAL_TRY(c->bq_skey.alloc((size_t)cq * NS));
-        SCAL_TRY(c->bq_norm.alloc((size_t)cq * NS));
-        SCAL_TRY(c->bq_best.alloc((size_t)cq * cb * 3));
-        SCAL_TRY(c->bq_limits.alloc(cq));
-        SCAL_TRY(c->bq_hlimits.alloc(64));
-        c->bq_cap = cq, c->bq_nb = cb;
-    }
+    SCAL_TRY(ensure_batch(c, nq, nb));
     for (int q = 0; q < nq; ++q) c->bq_hlimits.p[q] = limits[q] - 30;  // NUM_EXCLUDE_RECENT
     SCAL_HIP(op_memcpy_async(c->bq_limits.p, c->bq_hlimits.p, sizeof(int) * nq, hipMemcpyHostToDevice, s));
     if (nq > 0) {
@@ -1299,15 +1320,12 @@ namespace scal {
 // than the query by more than `exclude` keyframes (NUM_EXCLUDE_RECENT, Scancontext.h:92): d0 + j < q0 + row - exclude.
 // One workgroup per row; k rounds of a block-wide argmin over (distance, index) keys that must exceed the previous pick:
 // deterministic, ties go to the lower index.  Entries with NaN distance (no overlapping sector at any shift) never win.
-__device__ __forceinline__ void k_sc_row_topk_body(const double* __restrict__ dist, const int* __restrict__ shift, int nq, int nd, int q0, int d0,
-                                                     int exclude, int k, int* __restrict__ out_idx, double* __restrict__ out_dist,
-                                                     int* __restrict__ out_shift) {
+// row `row` of the block, eligible columns [0, limit)
+__device__ __forceinline__ void sc_row_topk(const double* __restrict__ dist, const int* __restrict__ shift, int row, int nd, int limit, int d0, int k,
+                                            int* __restrict__ out_idx, double* __restrict__ out_dist, int* __restrict__ out_shift) {
     __shared__ unsigned long long s_d[4];
     __shared__ int s_j[4];
-    const int row = blockIdx.x;
-    if (row >= nq) return;
     const double* drow = dist + static_cast<size_t>(row) * nd;
-    const int limit = min(nd, q0 + row - exclude - d0);  // eligible columns: [0, limit)
     unsigned long long last_d = 0;
     int last_j = -1;
     bool first = true;
@@ -1346,7 +1364,22 @@ __device__ __forceinline__ void k_sc_row_topk_body(const double* __restrict__ di
         last_d = bd, last_j = bj, first = false;
     }
 }
+__device__ __forceinline__ void k_sc_row_topk_body(const double* __restrict__ dist, const int* __restrict__ shift, int nq, int nd, int q0, int d0,
+                                                     int exclude, int k, int* __restrict__ out_idx, double* __restrict__ out_dist,
+                                                     int* __restrict__ out_shift) {
+    const int row = blockIdx.x;
+    if (row >= nq) return;
+    sc_row_topk(dist, shift, row, nd, min(nd, q0 + row - exclude - d0), d0, k, out_idx, out_dist, out_shift);
+}
 SCAL_KERNEL(256, k_sc_row_topk)
+// the same over every column: the rows are queries from another session, no database entry is "too recent"
+__device__ __forceinline__ void k_sc_row_topk_all_body(const double* __restrict__ dist, const int* __restrict__ shift, int nq, int nd, int d0, int k,
+                                                         int* __restrict__ out_idx, double* __restrict__ out_dist, int* __restrict__ out_shift) {
+    const int row = blockIdx.x;
+    if (row >= nq) return;
+    sc_row_topk(dist, shift, row, nd, nd, d0, k, out_idx, out_dist, out_shift);
+}
+SCAL_KERNEL(256, k_sc_row_topk_all)
 }  // namespace scal
 
 static int ensure_pairs(scal_sc* c, size_t n) {
@@ -1389,8 +1422,10 @@ extern "C" int scal_sc_distance_pairs(scal_sc_t* c, const int* idx_a, const int*
     return SCAL_OK;
 }
 
+// qdb: the database the query rows [q0, q0 + nq) come from - c's own, or another context's on the same device (cross-session block)
 template <typename T>
-static int enqueue_gram(scal_sc* c, int q0, int nq, int d0, int nd, DevBuf<T>& frag, DevBuf<T>& bhat, double* d_dist, int* d_shift, hipStream_t s) {
+static int enqueue_gram(scal_sc* c, const SCDb& qdb, int q0, int nq, int d0, int nd, DevBuf<T>& frag, DevBuf<T>& bhat, double* d_dist, int* d_shift,
+                        hipStream_t s) {
     constexpr int GE = GramT<T>::GE;
     const int qblocks = div_up(nq, GQ), n_tiles = qblocks * 4, chunks = div_up(nd, GE);
     if (qblocks > 65535) {
@@ -1405,7 +1440,7 @@ static int enqueue_gram(scal_sc* c, int q0, int nq, int d0, int nd, DevBuf<T>& f
     const size_t lds = sizeof(T) * GE * NR * GROW;  // 79,360 B: above the 64 KiB default, two workgroups per CU
     SCAL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sc_gram<T>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     const bool f64 = sizeof(T) == 8;
-    SCAL_LAUNCH_PROF(f64 ? "k_sc_gram_prep" : "k_sc_gram_prep_f32", k_sc_gram_prep<T>, dim3(n_tiles), dim3(256), 0, s, c->db(), q0, nq, frag.p,
+    SCAL_LAUNCH_PROF(f64 ? "k_sc_gram_prep" : "k_sc_gram_prep_f32", k_sc_gram_prep<T>, dim3(n_tiles), dim3(256), 0, s, qdb, q0, nq, frag.p,
                      c->g_qmask.p);
     SCAL_LAUNCH_PROF(f64 ? "k_sc_gram_prep_db" : "k_sc_gram_prep_db_f32", k_sc_gram_prep_db<T>, dim3(nd), dim3(256), 0, s, c->db(), d0, nd, bhat.p,
                      c->g_dmask.p);
@@ -1416,17 +1451,23 @@ static int enqueue_gram(scal_sc* c, int q0, int nq, int d0, int nd, DevBuf<T>& f
 }
 
 // mode 0 / 1: one wave per pair on the vector ALUs (summation order of the reference); mode 2: matrix cores (k_sc_gram)
-static int enqueue_matrix(scal_sc* c, int q0, int q1, int d0, int d1, int mode, double* d_dist, int* d_shift, hipStream_t s) {
+// qc: the context the query rows are entries of (nullptr: c itself)
+static int enqueue_matrix(scal_sc* c, int q0, int q1, int d0, int d1, int mode, double* d_dist, int* d_shift, hipStream_t s, const scal_sc* qc = nullptr) {
     const int nq = q1 - q0, nd = d1 - d0;
     const size_t np = static_cast<size_t>(nq) * nd;
     if (mode < 2) {
-        SCAL_LAUNCH("k_sc_matrix", k_sc_matrix, dim3(static_cast<unsigned>((np + 3) / 4)), dim3(256), 0, s, c->db(), q0, nq, d0, nd, mode,
+        if (qc)
+            SCAL_LAUNCH("k_sc_matrix_cross", k_sc_matrix_cross, dim3(static_cast<unsigned>((np + 3) / 4)), dim3(256), 0, s, qc->db(), c->db(), q0, nq, d0,
+                        nd, mode, d_dist, d_shift);
+        else
+            SCAL_LAUNCH("k_sc_matrix", k_sc_matrix, dim3(static_cast<unsigned>((np + 3) / 4)), dim3(256), 0, s, c->db(), q0, nq, d0, nd, mode,
                          d_dist, d_shift);
         SCAL_HIP(hipGetLastError());
         return SCAL_OK;
     }
-    return mode == 2 ? enqueue_gram<double>(c, q0, nq, d0, nd, c->g_frag, c->g_bhat, d_dist, d_shift, s)
-                     : enqueue_gram<float>(c, q0, nq, d0, nd, c->g_frag32, c->g_bhat32, d_dist, d_shift, s);
+    const SCDb qdb = qc ? qc->db() : c->db();
+    return mode == 2 ? enqueue_gram<double>(c, qdb, q0, nq, d0, nd, c->g_frag, c->g_bhat, d_dist, d_shift, s)
+                     : enqueue_gram<float>(c, qdb, q0, nq, d0, nd, c->g_frag32, c->g_bhat32, d_dist, d_shift, s);
 }
 
 static int check_matrix_args(scal_sc* c, const void* dist, const void* shift, int q0, int q1, int d0, int d1, int mode) {
@@ -1498,6 +1539,170 @@ extern "C" int scal_sc_batch_loop_search(scal_sc_t* c, int q0, int q1, int exclu
         if (nd > 0) SCAL_TRY(enqueue_matrix(c, t0, t1, 0, nd, mode, c->d_dist.p, c->d_shift.p, s));
         SCAL_LAUNCH("k_sc_row_topk", k_sc_row_topk, dim3(nq), dim3(256), 0, s, c->d_dist.p, c->d_shift.p, nq, nd, t0, 0, exclude_recent, k, o_idx.p,
                          o_dist.p, o_shift.p);
+        SCAL_HIP(hipGetLastError());
+        const size_t off = static_cast<size_t>(t0 - q0) * k;
+        SCAL_HIP(op_memcpy_async(idx + off, o_idx.p, sizeof(int) * nq * k, hipMemcpyDeviceToHost, s));
+        SCAL_HIP(op_memcpy_async(dist + off, o_dist.p, sizeof(double) * nq * k, hipMemcpyDeviceToHost, s));
+        SCAL_HIP(op_memcpy_async(shift + off, o_shift.p, sizeof(int) * nq * k, hipMemcpyDeviceToHost, s));
+        SCAL_HIP(op_stream_synchronize(s));
+    }
+    return SCAL_OK;
+}
+
+// ---- between sessions ---------------------------------------------------------------------------------------------------------
+// makeScancontext of a cloud already in HBM (SoA, device-side count) into d_desc, not inserted (scal_reloc's query)
+int scal::sc_make_cloud_device(scal_sc_t* c, const float* d_x, const float* d_y, const float* d_z, const int* d_n, int n_max, double* d_desc) {
+    if (!c || !d_x || !d_y || !d_z || !d_desc || n_max < 0) {
+        set_error("sc_make_cloud_device: bad argument");
+        return SCAL_E_ARG;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(make_into(c, d_x, d_y, d_z, 1, d_n, n_max, false));
+    SCAL_HIP(op_memcpy_async(d_desc, c->qdesc.p, sizeof(double) * DESC, hipMemcpyDeviceToDevice, c->stream));
+    return SCAL_OK;
+}
+
+// detectLoopClosureIDBetweenSession (Scancontext.cpp:272-333) per query: ring key, KNN(3) over ALL keys of the database, the three
+// candidates' distances, strict minimum, threshold.  Chunks of 64 queries, one k_sc_keys / k_sc_topk / k_sc_detect launch set each;
+// every query has its own rows in every buffer, so a record depends neither on nq nor on the chunking.
+static int detect_between(scal_sc* c, const double* queries, int nq, bool on_device, scal_sc_result* res) {
+    if (!c || nq < 0 || (nq > 0 && (!queries || !res))) {
+        set_error("scal_sc_detect_between: bad argument");
+        return SCAL_E_ARG;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->cfg.n_shards > 1) {
+        set_error("scal_sc_detect_between needs an unsharded context");
+        return SCAL_E_ARG;
+    }
+    if (c->n_global == 0) {
+        set_error("scal_sc_detect_between: the database is empty");
+        return SCAL_E_STATE;
+    }
+    if (nq == 0) return SCAL_OK;
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    constexpr int CHUNK = 64;
+    const int nb = std::max(1, div_up(c->n_local, 256));
+    SCAL_TRY(ensure_batch(c, CHUNK, nb));
+    if (!c->bt_rec.p) {
+        SCAL_TRY(c->bt_rec.alloc(3 * CHUNK));
+        SCAL_TRY(c->bt_hrec.alloc(3 * CHUNK));
+    }
+    if (!on_device && !c->bt_q.p) SCAL_TRY(c->bt_q.alloc(static_cast<size_t>(CHUNK) * DESC));
+    for (int q0 = 0; q0 < nq; q0 += CHUNK) {
+        const int n = std::min(CHUNK, nq - q0);
+        const double* d_q = queries + static_cast<size_t>(q0) * DESC;
+        if (!on_device) {
+            SCAL_HIP(op_memcpy_async(c->bt_q.p, d_q, sizeof(double) * DESC * n, hipMemcpyHostToDevice, s));
+            d_q = c->bt_q.p;
+        }
+        SCAL_LAUNCH("k_sc_keys", k_sc_keys, dim3(n), dim3(128), 0, s, d_q, c->bq_rkey.p, c->bq_skey.p, c->bq_norm.p);
+        // limit = the size: no key is excluded; unfilled KNN slots keep index 0 (fill_missing_with_zero)
+        SCAL_LAUNCH("k_sc_topk", k_sc_topk, dim3(nb, n), dim3(256), 0, s, c->rkey.p, c->bq_rkey.p, c->n_local, 1, 0, c->n_global, c->bq_best.p,
+                    static_cast<const int*>(nullptr));
+        SCAL_LAUNCH("k_sc_detect", k_sc_detect, dim3(1, n), dim3(256), 0, s, c->bq_best.p, nb, c->db(), 1, 0, d_q, c->bq_skey.p, c->bq_norm.p, 1,
+                    c->bt_rec.p);
+        SCAL_HIP(hipGetLastError());
+        SCAL_HIP(op_memcpy_async(c->bt_hrec.p, c->bt_rec.p, sizeof(SCRec) * 3 * n, hipMemcpyDeviceToHost, s));
+        SCAL_HIP(op_stream_synchronize(s));
+        for (int q = 0; q < n; ++q) {
+            std::memset(&res[q0 + q], 0, sizeof res[0]);
+            finish_result(c->bt_hrec.p + 3 * q, 3, c->cfg.dist_thres, &res[q0 + q]);
+        }
+    }
+    return SCAL_OK;
+}
+
+extern "C" int scal_sc_detect_between(scal_sc_t* c, const double* query_descs_colmajor, int nq, scal_sc_result* res) {
+    return detect_between(c, query_descs_colmajor, nq, false, res);
+}
+extern "C" int scal_sc_detect_between_device(scal_sc_t* c, const double* d_query_descs, int nq, scal_sc_result* res) {
+    return detect_between(c, d_query_descs, nq, true, res);
+}
+
+// Locks the database context and (when it is another one) the query context and checks both and the ranges (d1 < 0: the whole
+// database); cross_order then puts the database context's stream behind everything queued on the query context's.
+namespace {
+struct CrossLock {
+    std::unique_lock<std::mutex> a, b;
+};
+}  // namespace
+static int cross_begin(const char* who, scal_sc* c, scal_sc* qc, int q0, int q1, int d0, int d1, int mode, CrossLock* lk) {
+    if (!c || !qc || q0 < 0 || d0 < 0 || q1 < q0 || (d1 >= 0 && d1 < d0) || mode < 0 || mode > 3) {
+        set_error("%s: bad argument", who);
+        return SCAL_E_ARG;
+    }
+    if (c == qc) {
+        lk->a = std::unique_lock<std::mutex>(c->mu);
+    } else {
+        lk->a = std::unique_lock<std::mutex>(c->mu, std::defer_lock);
+        lk->b = std::unique_lock<std::mutex>(qc->mu, std::defer_lock);
+        std::lock(lk->a, lk->b);
+    }
+    if (c->cfg.n_shards > 1 || qc->cfg.n_shards > 1 || c->cfg.device != qc->cfg.device) {
+        set_error("%s needs two unsharded contexts on the same device", who);
+        return SCAL_E_ARG;
+    }
+    if (q1 > qc->n_global || d1 > c->n_global) {
+        set_error("%s: range outside the query context (%d entries) or the database (%d entries)", who, qc->n_global, c->n_global);
+        return SCAL_E_ARG;
+    }
+    return SCAL_OK;
+}
+static int cross_order(scal_sc* c, scal_sc* qc) {
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    if (c != qc && static_cast<hipStream_t>(c->stream) != static_cast<hipStream_t>(qc->stream)) {
+        SCAL_TRY(c->ev_cross.ensure(EV_DEVICE_ONLY));
+        SCAL_HIP(op_event_record(c->ev_cross, qc->stream));
+        SCAL_HIP(op_stream_wait_event(c->stream, c->ev_cross, 0));
+    }
+    return SCAL_OK;
+}
+
+extern "C" int scal_sc_cross_matrix(scal_sc_t* c, scal_sc_t* qc, int q0, int q1, int d0, int d1, int mode, double* dist, int* shift) {
+    if (!dist || !shift) {
+        set_error("scal_sc_cross_matrix: bad argument");
+        return SCAL_E_ARG;
+    }
+    CrossLock lk;
+    SCAL_TRY(cross_begin("scal_sc_cross_matrix", c, qc, q0, q1, d0, d1, mode, &lk));
+    const size_t np = static_cast<size_t>(q1 - q0) * (d1 - d0);
+    if (np == 0) return SCAL_OK;
+    SCAL_TRY(cross_order(c, qc));
+    SCAL_TRY(ensure_pairs(c, np));
+    hipStream_t s = c->stream;
+    SCAL_TRY(enqueue_matrix(c, q0, q1, d0, d1, mode, c->d_dist.p, c->d_shift.p, s, qc));
+    SCAL_HIP(op_memcpy_async(dist, c->d_dist.p, sizeof(double) * np, hipMemcpyDeviceToHost, s));
+    SCAL_HIP(op_memcpy_async(shift, c->d_shift.p, sizeof(int) * np, hipMemcpyDeviceToHost, s));
+    SCAL_HIP(op_stream_synchronize(s));
+    return SCAL_OK;
+}
+
+// scal_sc_batch_loop_search with the query rows from another context: row tiles of 512 queries against the whole database, the
+// top-k taken on the device over every column
+extern "C" int scal_sc_cross_search(scal_sc_t* c, scal_sc_t* qc, int q0, int q1, int k, int mode, int* idx, double* dist, int* shift) {
+    if (!idx || !dist || !shift || k < 1 || k > 16) {
+        set_error("scal_sc_cross_search: bad argument (1 <= k <= 16)");
+        return SCAL_E_ARG;
+    }
+    CrossLock lk;
+    SCAL_TRY(cross_begin("scal_sc_cross_search", c, qc, q0, q1, 0, -1, mode, &lk));
+    if (q1 == q0) return SCAL_OK;
+    SCAL_TRY(cross_order(c, qc));
+    hipStream_t s = c->stream;
+    const int TILE_Q = 512, nd = c->n_global;
+    SCAL_TRY(ensure_pairs(c, static_cast<size_t>(TILE_Q) * std::max(1, nd)));
+    DevBuf<int> o_idx, o_shift;
+    DevBuf<double> o_dist;
+    SCAL_TRY(o_idx.alloc(static_cast<size_t>(TILE_Q) * k));
+    SCAL_TRY(o_shift.alloc(static_cast<size_t>(TILE_Q) * k));
+    SCAL_TRY(o_dist.alloc(static_cast<size_t>(TILE_Q) * k));
+    for (int t0 = q0; t0 < q1; t0 += TILE_Q) {
+        const int t1 = std::min(q1, t0 + TILE_Q), nq = t1 - t0;
+        if (nd > 0) SCAL_TRY(enqueue_matrix(c, t0, t1, 0, nd, mode, c->d_dist.p, c->d_shift.p, s, qc));
+        SCAL_LAUNCH("k_sc_row_topk_all", k_sc_row_topk_all, dim3(nq), dim3(256), 0, s, c->d_dist.p, c->d_shift.p, nq, nd, 0, k, o_idx.p, o_dist.p, o_shift.p);
         SCAL_HIP(hipGetLastError());
         const size_t off = static_cast<size_t>(t0 - q0) * k;
         SCAL_HIP(op_memcpy_async(idx + off, o_idx.p, sizeof(int) * nq * k, hipMemcpyDeviceToHost, s));

@@ -12,6 +12,8 @@ int main(void) {
     scal_pipeline_t* p = NULL;
     scal_refine_config rc_cfg;
     scal_refine_t* rf = NULL;
+    scal_reloc_config rl_cfg;
+    scal_reloc_t* rl = NULL;
     int rc, n = scal_device_count();
     memset(&fc, 0, sizeof fc);
     fc.lidar_type = SCAL_HDL64, fc.n_scans = 64, fc.minimum_range = 5.0, fc.max_points = 1000, fc.check_finite = 1;
@@ -42,6 +44,25 @@ int main(void) {
         return 1;
     }
     if (rc == SCAL_OK) scal_refine_destroy(rf);
+    memset(&rl_cfg, 0, sizeof rl_cfg); /* zero = the reference's default in every field but the capacities */
+    rl_cfg.max_keyframes = 4, rl_cfg.max_points = 1000;
+    if (scal_reloc_create(&rl_cfg, &rl) != SCAL_E_ARG) {
+        printf("scal_reloc_create accepted max_query_points = 0\n");
+        return 1;
+    }
+    rl_cfg.max_query_points = 1000;
+    rc = scal_reloc_create(&rl_cfg, &rl);
+    if (n < 1 && rc != SCAL_E_NO_DEVICE) {
+        printf("scal_reloc_create: expected SCAL_E_NO_DEVICE without a GPU, got %d (%s)\n", rc, scal_last_error());
+        return 1;
+    }
+    if (rc == SCAL_OK) {
+        if (scal_reloc_size(rl) != 0 || !scal_reloc_sc(rl)) {
+            printf("scal_reloc_create: a fresh context must be empty and own a ScanContext database\n");
+            return 1;
+        }
+        scal_reloc_destroy(rl);
+    }
     printf("abi ok %s devices=%d\n", scal_version(), n);
     return 0;
 }

@@ -86,6 +86,17 @@ class RefineFrameResult(C.Structure):
                 ("accepted", C.c_int), ("fitness", C.c_double), ("T", C.c_double * 16)]
 
 
+class RelocConfig(C.Structure):
+    _fields_ = [("max_keyframes", C.c_int), ("max_points", C.c_int), ("max_query_points", C.c_int), ("sc_max_radius", C.c_double),
+                ("sc_dist_thres", C.c_double), ("float_math", C.c_int), ("leaf", C.c_float), ("submap_half", C.c_int),
+                ("fitness_thres", C.c_double), ("max_corr_dist", C.c_double), ("transformation_epsilon", C.c_double),
+                ("fitness_epsilon", C.c_double), ("max_iterations", C.c_int), ("no_yaw_guess", C.c_int), ("device", C.c_int)]
+
+
+class RelocResult(C.Structure):
+    _fields_ = [("sc", SCResult), ("status", C.c_int), ("n_src", C.c_int), ("n_tgt", C.c_int), ("icp", ICPResult), ("pose12", C.c_double * 12)]
+
+
 class MapMergeConfig(C.Structure):
     _fields_ = [("max_points", C.c_longlong), ("max_frame_points", C.c_int), ("device", C.c_int)]
 
@@ -165,6 +176,8 @@ EXPORTED_SYMBOLS = [
     "scal_pipeline_update_keyframe_poses", "scal_pipeline_pgo_map", "scal_pipeline_pgo_map_device",
     "scal_pipeline_optimize_keyframes", "scal_posegraph_create", "scal_posegraph_destroy", "scal_posegraph_set_nodes", "scal_posegraph_set_prior",
     "scal_posegraph_add_between", "scal_posegraph_clear_edges", "scal_posegraph_optimize", "scal_posegraph_get_nodes", "scal_posegraph_get_edge_weights",
+    "scal_sc_detect_between", "scal_sc_detect_between_device", "scal_sc_cross_matrix", "scal_sc_cross_search", "scal_icp_align_guess", "scal_icp_align_guess_device",
+    "scal_reloc_create", "scal_reloc_destroy", "scal_reloc_size", "scal_reloc_add_keyframe", "scal_reloc_query", "scal_reloc_query_batch", "scal_reloc_sc",
 ]
 
 _lib = None
@@ -326,6 +339,22 @@ def lib():
         L.scal_posegraph_optimize.argtypes = [vp, C.POINTER(PoseGraphParams), C.POINTER(PoseGraphStats)]
         L.scal_posegraph_get_nodes.argtypes = [vp, _f64p, C.c_int]
         L.scal_posegraph_get_edge_weights.argtypes = [vp, _f64p, C.c_int]
+    if hasattr(L, "scal_reloc_create"):  # absent from older builds compared through SCALOAM_LIB
+        L.scal_sc_detect_between.argtypes = [vp, _f64p, C.c_int, C.POINTER(SCResult)]
+        L.scal_sc_detect_between_device.argtypes = [vp, vp, C.c_int, C.POINTER(SCResult)]
+        L.scal_sc_cross_matrix.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, _i32p]
+        L.scal_sc_cross_search.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _f64p, _i32p]
+        L.scal_icp_align_guess.argtypes = [vp, _f32p, C.c_int, _f32p, C.c_int, _f32p, C.POINTER(ICPResult)]
+        L.scal_icp_align_guess_device.argtypes = [vp, vp, C.c_int, vp, C.c_int, _f32p, C.POINTER(ICPResult)]
+        L.scal_reloc_create.argtypes = [C.POINTER(RelocConfig), C.POINTER(vp)]
+        L.scal_reloc_destroy.argtypes = [vp]
+        L.scal_reloc_destroy.restype = None
+        L.scal_reloc_size.argtypes = [vp]
+        L.scal_reloc_add_keyframe.argtypes = [vp, _f32p, C.c_int, _f64p, _f64p]
+        L.scal_reloc_query.argtypes = [vp, _f32p, C.c_int, C.POINTER(RelocResult)]
+        L.scal_reloc_query_batch.argtypes = [vp, _f32p, _i32p, C.c_int, C.POINTER(RelocResult)]
+        L.scal_reloc_sc.argtypes = [vp]
+        L.scal_reloc_sc.restype = C.c_void_p
     L.scal_keyframe_gate_init.argtypes = [C.POINTER(KeyframeGateState), C.c_double, C.c_double]
     L.scal_keyframe_gate.argtypes = [C.POINTER(KeyframeGateState), _f64p, _f64p, _i32p]
     for fn in ("scal_pipeline_sc_of", "scal_pipeline_map_of"):
@@ -601,6 +630,35 @@ class SCManager:
         _check(lib().scal_sc_batch_loop_search(self.h, q0, q1, exclude_recent, k, mode, _p(idx, _i32p), _p(dist, _f64p), _p(shift, _i32p)))
         return idx, dist, shift
 
+    def detect_between(self, query_descs):
+        """detectLoopClosureIDBetweenSession for every [ring, sector] descriptor of `query_descs` (a list or an [nq, 20, 60] array) against
+        the whole database; a list of detectLoopClosureID-style dicts"""
+        q = [np.asarray(d) for d in query_descs]
+        flat = _f64(np.stack([d.T.reshape(-1) for d in q])) if q else np.zeros((0, 1200))
+        res = (SCResult * max(1, len(q)))()
+        _check(lib().scal_sc_detect_between(self.h, _p(flat, _f64p), len(q), res))
+        return [self._result(r) for r in res[:len(q)]]
+
+    def detect_between_device(self, d_query_descs_ptr, nq):
+        """the same with nq column-major descriptors back to back in device memory"""
+        res = (SCResult * max(1, nq))()
+        _check(lib().scal_sc_detect_between_device(self.h, d_query_descs_ptr, nq, res))
+        return [self._result(r) for r in res[:nq]]
+
+    def cross_matrix(self, queries, q0, q1, d0, d1, mode=0):
+        """distance_matrix with the query rows taken from entries [q0, q1) of another SCManager on the same device"""
+        d = np.zeros((max(0, q1 - q0), max(0, d1 - d0)))
+        s = np.zeros((max(0, q1 - q0), max(0, d1 - d0)), np.int32)
+        _check(lib().scal_sc_cross_matrix(self.h, queries.h, q0, q1, d0, d1, mode, _p(d, _f64p), _p(s, _i32p)))
+        return d, s
+
+    def cross_search(self, queries, q0, q1, k=3, mode=2):
+        """(idx, dist, shift) arrays [q1-q0][k]: the k best entries of this database for every entry [q0, q1) of `queries`"""
+        n = max(0, q1 - q0)
+        idx, dist, shift = np.zeros((n, max(k, 1)), np.int32), np.zeros((n, max(k, 1))), np.zeros((n, max(k, 1)), np.int32)
+        _check(lib().scal_sc_cross_search(self.h, queries.h, q0, q1, k, mode, _p(idx, _i32p), _p(dist, _f64p), _p(shift, _i32p)))
+        return idx, dist, shift
+
     def distance_matrix_device(self, q0, q1, d0, d1, mode, d_dist_ptr, d_shift_ptr):
         """Device outputs ((q1-q0)*(d1-d0) doubles / int32), enqueued on the context's stream; sync() before reading."""
         _check(lib().scal_sc_distance_matrix_device(self.h, q0, q1, d0, d1, mode, d_dist_ptr, d_shift_ptr))
@@ -844,10 +902,15 @@ class LoopICP:
         """1 (default): cell grid + dense sweep for unresolved queries; 0: dense sweep only.  Same result."""
         _check(lib().scal_icp_set_search(self.h, mode))
 
-    def align(self, src, tgt):
+    def align(self, src, tgt, guess=None):
+        """guess: a 4x4 initial transformation (pcl's align(output, guess)); None = the identity"""
         s, t = _f32(src), _f32(tgt)
         r = ICPResult()
-        _check(lib().scal_icp_align(self.h, _p(s, _f32p), s.shape[0], _p(t, _f32p), t.shape[0], C.byref(r)))
+        if guess is None:
+            _check(lib().scal_icp_align(self.h, _p(s, _f32p), s.shape[0], _p(t, _f32p), t.shape[0], C.byref(r)))
+        else:
+            g = _f32(np.asarray(guess).reshape(16))
+            _check(lib().scal_icp_align_guess(self.h, _p(s, _f32p), s.shape[0], _p(t, _f32p), t.shape[0], _p(g, _f32p), C.byref(r)))
         return dict(converged=bool(r.converged), iterations=r.iterations, state=r.state, n_correspondences=r.n_correspondences,
                     fitness=r.fitness, T=np.array(r.T[:]).reshape(4, 4))
 
@@ -904,6 +967,88 @@ class MultiviewRefine:
     def refine_device(self, d_xyzi_ptr, offsets, poses12, fixed=None, rounds=1, near_thres=2.0):
         """the frames as 16-byte xyzi records back to back in device memory, frame f = records [offsets[f], offsets[f+1])"""
         return self._run(lib().scal_refine_run_device, d_xyzi_ptr, offsets, poses12, fixed, rounds, near_thres)
+
+
+def yaw_guess(yaw_rad):
+    """Rz(-yaw) as scal_reloc builds it from a search's f32 yaw: cos and sin in double, rounded to f32"""
+    y = float(np.float32(yaw_rad))
+    c, s = np.float32(np.cos(y)), np.float32(np.sin(y))
+    return np.array([[c, s, 0, 0], [-s, c, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1]], np.float32)
+
+
+def relative_transform(pose12_c, pose12_j):
+    """M = P_c^-1 P_j as scal_reloc computes it for a submap keyframe: f64, every sum left to right, rounded to an f32 3x4"""
+    Pc, Pj = np.asarray(pose12_c, np.float64).reshape(3, 4), np.asarray(pose12_j, np.float64).reshape(3, 4)
+    Ri = Pc[:, :3].T
+    ti = -((Ri[:, 0] * Pc[0, 3] + Ri[:, 1] * Pc[1, 3]) + Ri[:, 2] * Pc[2, 3])
+    M = (Ri[:, 0:1] * Pj[0:1, :] + Ri[:, 1:2] * Pj[1:2, :]) + Ri[:, 2:3] * Pj[2:3, :]
+    M[:, 3] += ti
+    return M.astype(np.float32)
+
+
+class Relocalizer:
+    """scal_reloc: one saved session (per keyframe its Scans/ cloud, its optimized pose, its descriptor) in device memory; query() finds
+    the place of a new scan by the between-session ScanContext search and verifies it by ICP from the search's yaw against a submap of
+    the keyframes around the candidate (include/scaloam_hip.h has the steps).  0 = the reference's default for every setting."""
+
+    def __init__(self, max_keyframes, max_points, max_query_points=400000, sc_max_radius=0.0, sc_dist_thres=0.0, float_math=0, leaf=0.0,
+                 submap_half=0, fitness_thres=0.0, max_corr_dist=0.0, transformation_epsilon=0.0, fitness_epsilon=0.0, max_iterations=0,
+                 no_yaw_guess=False, device=0):
+        self.h = C.c_void_p()
+        cfg = RelocConfig(int(max_keyframes), int(max_points), int(max_query_points), sc_max_radius, sc_dist_thres, float_math, leaf,
+                          int(submap_half), fitness_thres, max_corr_dist, transformation_epsilon, fitness_epsilon, int(max_iterations),
+                          1 if no_yaw_guess else 0, device)
+        _check(lib().scal_reloc_create(C.byref(cfg), C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.scal_reloc_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def size(self):
+        return lib().scal_reloc_size(self.h)
+
+    def sc(self):
+        """the session's ScanContext database as a borrowed SCManager (valid while this object lives)"""
+        return _borrow(SCManager, lib().scal_reloc_sc(self.h))
+
+    def add_keyframe(self, xyzi, pose12, desc=None):
+        """one keyframe in its local frame with its row of optimized_poses.txt; desc: a reloaded [ring, sector] descriptor (formats.read_scd),
+        None = built from the filtered cloud.  Returns the keyframe index."""
+        x = _f32(xyzi).reshape(-1, 4)
+        P = _f64(np.asarray(pose12).reshape(-1)[:12])
+        d = _f64(np.asarray(desc).T.reshape(-1)) if desc is not None else None
+        j = lib().scal_reloc_add_keyframe(self.h, _p(x, _f32p), x.shape[0], _p(P, _f64p), _p(d, _f64p))
+        if j < 0:
+            _check(j)
+        return j
+
+    @staticmethod
+    def _result(r):
+        return dict(status=r.status, sc=SCManager._result(r.sc), n_src=r.n_src, n_tgt=r.n_tgt,
+                    icp=dict(converged=bool(r.icp.converged), iterations=r.icp.iterations, state=r.icp.state,
+                             n_correspondences=r.icp.n_correspondences, fitness=r.icp.fitness, T=np.array(r.icp.T[:]).reshape(4, 4)),
+                    pose12=np.array(r.pose12[:]))
+
+    def query(self, xyzi):
+        x = _f32(xyzi).reshape(-1, 4)
+        r = RelocResult()
+        _check(lib().scal_reloc_query(self.h, _p(x, _f32p), x.shape[0], C.byref(r)))
+        return self._result(r)
+
+    def query_batch(self, clouds):
+        cs = [_f32(c).reshape(-1, 4) for c in clouds]
+        off = np.zeros(len(cs) + 1, np.int64)
+        off[1:] = np.cumsum([c.shape[0] for c in cs])
+        if off[-1] > 2**31 - 1:
+            raise ValueError("more points than 32-bit offsets hold")
+        off = off.astype(np.int32)
+        cat = np.ascontiguousarray(np.concatenate(cs, 0)) if cs else np.zeros((0, 4), np.float32)
+        res = (RelocResult * max(1, len(cs)))()
+        _check(lib().scal_reloc_query_batch(self.h, _p(cat, _f32p), _p(off, _i32p), len(cs), res))
+        return [self._result(r) for r in res[:len(cs)]]
 
 
 class MapMerge:
