@@ -23,17 +23,12 @@ namespace scal {
 // chunks; each thread carries its table entry forward (positions only grow), so the table is searched once per workgroup.  Per point
 // one 16-byte load (PGO_ITEMS of them in flight per thread) and four coalesced 4-byte stores into the planes the filter reads.
 constexpr int PGO_ITEMS = 4, PGO_TILE = 256 * PGO_ITEMS, PGO_MAX_BLOCKS = 256;
-static __global__ void __launch_bounds__(256) k_pgo_gather(const float4* __restrict__ arena, const PgoXf* __restrict__ xf, int n_sel, int n, int chunk,
+static __global__ void __launch_bounds__(256) k_pgo_gather(const float4* __restrict__ arena, const GatherXf* __restrict__ xf, int n_sel, int n, int chunk,
                                                            float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz,
                                                            float* __restrict__ ow, unsigned* __restrict__ parts, int* __restrict__ d_n) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *d_n = n;  // the filter's device-side count
     const int c0 = blockIdx.x * chunk, c1 = static_cast<int>(min(static_cast<long long>(n), static_cast<long long>(c0) + chunk));
-    int s = 0;
-    for (int hi = n_sel - 1; s < hi;) {  // the last entry with dst <= c0 (entries of empty keyframes share their dst)
-        const int mid = (s + hi + 1) >> 1;
-        if (xf[mid].dst <= c0) s = mid;
-        else hi = mid - 1;
-    }
+    int s = gather_find(xf, n_sel, c0);
     int s_src = xf[s].src, s_dst = xf[s].dst, next = xf[s + 1].dst;
     int cur = -1;
     float T[12];
@@ -61,12 +56,10 @@ static __global__ void __launch_bounds__(256) k_pgo_gather(const float4* __restr
                 T[0] = a.x, T[1] = a.y, T[2] = a.z, T[3] = a.w, T[4] = b.x, T[5] = b.y, T[6] = b.z, T[7] = b.w;
                 T[8] = c.x, T[9] = c.y, T[10] = c.z, T[11] = c.w;
             }
-            const float x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p[j].x), __fmul_rn(T[1], p[j].y)), __fmul_rn(T[2], p[j].z)), T[3]);
-            const float y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], p[j].x), __fmul_rn(T[5], p[j].y)), __fmul_rn(T[6], p[j].z)), T[7]);
-            const float z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], p[j].x), __fmul_rn(T[9], p[j].y)), __fmul_rn(T[10], p[j].z)), T[11]);
+            const float4 q = xf_point(T, p[j]);
             const int i = t0 + j * 256 + static_cast<int>(threadIdx.x);
-            ox[i] = x, oy[i] = y, oz[i] = z, ow[i] = p[j].w;
-            const unsigned u[3] = {vox_ordered(x), vox_ordered(y), vox_ordered(z)};
+            ox[i] = q.x, oy[i] = q.y, oz[i] = q.z, ow[i] = q.w;
+            const unsigned u[3] = {vox_ordered(q.x), vox_ordered(q.y), vox_ordered(q.z)};
 #pragma unroll
             for (int a = 0; a < 3; ++a) lo[a] = min(lo[a], u[a]), hi[a] = max(hi[a], u[a]);
         }
@@ -95,22 +88,13 @@ __global__ void k_kf_append(const float* __restrict__ x, const float* __restrict
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) arena[base + i] = make_float4(x[i], y[i], z[i], w[i]);
 }
 
-// local2global (:338-359) of keyframes j0 .. j1 (contiguous in the arena, in keyframe order) with ONE transform, into out[0 .. n):
-// each coordinate ((T0 * x + T1 * y) + T2 * z) + T3 in f32, rounded operation by operation (Eigen's expression, no contraction).
-// Streaming: one 16-byte load and one 16-byte store per point.
+// local2global (:338-359, xf_point) of keyframes j0 .. j1 (contiguous in the arena, in keyframe order) with ONE transform, into
+// out[0 .. n).  Streaming: one 16-byte load and one 16-byte store per point.
 __global__ void k_kf_submap(const float4* __restrict__ arena, const int* __restrict__ off, int j0, int j1, Aff34 T, float4* __restrict__ out,
                             int* __restrict__ d_n_out) {
     const int base = off[j0], n = off[j1 + 1] - base;
     if (blockIdx.x == 0 && threadIdx.x == 0) *d_n_out = n;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float4 p = arena[base + i];
-        float4 q;
-        q.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.m[0], p.x), __fmul_rn(T.m[1], p.y)), __fmul_rn(T.m[2], p.z)), T.m[3]);
-        q.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.m[4], p.x), __fmul_rn(T.m[5], p.y)), __fmul_rn(T.m[6], p.z)), T.m[7]);
-        q.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.m[8], p.x), __fmul_rn(T.m[9], p.y)), __fmul_rn(T.m[10], p.z)), T.m[11]);
-        q.w = p.w;
-        out[i] = q;
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = xf_point(T.m, arena[base + i]);
 }
 
 // pcl::getTransformation (f32 Affine3f, R = Rz(yaw) Ry(pitch) Rx(roll)), as scaloam.pgo._affine_f32 states it: the sines and cosines
@@ -221,12 +205,9 @@ int KeyframeStore::init(int dev, int points, int keyframes, int map_points) {
     h_off.p[0] = 0, h_overflow.p[0] = 0;
     // verification: lane 5 (scal_pipeline's busy chains are on lanes 0, 1, 3 and 4)
     SCAL_TRY(vstream.acquire(dev, 5));
-    SCAL_TRY(vf.init(points));
-    vf.set_tag(".V");
+    SCAL_TRY(vcf.init(points));
+    vcf.set_tag(".V");
     for (DevBuf<float4>* b : {&raw_src, &raw_tgt, &ds_src, &ds_tgt}) SCAL_TRY(b->alloc(static_cast<size_t>(points)));
-    for (DevBuf<float>* b : {&sx, &sy, &sz, &sw, &ox, &oy, &oz, &ow}) SCAL_TRY(b->alloc(static_cast<size_t>(points)));
-    SCAL_TRY(d_n.alloc(2));
-    SCAL_TRY(h_cnt.alloc(2));
     scal_icp_config ic{};
     ic.max_corr_dist = 150, ic.max_iterations = 100, ic.transformation_epsilon = 1e-6, ic.fitness_epsilon = 1e-6;  // :519-523
     ic.max_source = points, ic.max_target = points, ic.device = dev;
@@ -238,15 +219,12 @@ int KeyframeStore::init(int dev, int points, int keyframes, int map_points) {
     // pose-graph map: lane 2 - the pipeline's busy chains are on lanes 0, 1, 3 and 4, and on lane 5 the map would queue behind loop
     // verifications
     SCAL_TRY(mstream.acquire(dev, 2));
-    SCAL_TRY(mvf.init(map_cap));
-    mvf.set_tag(".M");
+    SCAL_TRY(mcf.init(map_cap));
+    mcf.set_tag(".M");
     SCAL_TRY(d_xf.alloc(static_cast<size_t>(keyframes) + 1));
     SCAL_TRY(h_xf.alloc(static_cast<size_t>(keyframes) + 1));
     SCAL_TRY(d_parts.alloc(6 * PGO_MAX_BLOCKS));
-    for (DevBuf<float>* b : {&mx, &my, &mz, &mw, &fx, &fy, &fz, &fw}) SCAL_TRY(b->alloc(static_cast<size_t>(map_cap)));
     SCAL_TRY(d_map.alloc(static_cast<size_t>(map_cap)));
-    SCAL_TRY(d_mn.alloc(2));
-    SCAL_TRY(h_mn.alloc(2));
     return SCAL_OK;
 }
 
@@ -349,21 +327,13 @@ int KeyframeStore::verify(const KfLoopJob& job, double fitness_thres, scal_pipel
     for (int c = 0; c < 2; ++c) {
         if (nr[c] <= 0) continue;
         const int grid = std::min(div_up(nr[c], 256), 1024);
-        hipLaunchKernelGGL(k_kf_submap, dim3(grid), dim3(256), 0, s, arena.p, d_off.p, jr0[c], jr1[c], T, raw[c], d_n.p);
+        hipLaunchKernelGGL(k_kf_submap, dim3(grid), dim3(256), 0, s, arena.p, d_off.p, jr0[c], jr1[c], T, raw[c], vcf.d_n_in());
         SCAL_HIP(hipGetLastError());
         // downSizeFilterICP (:491-492): leaf 0.4, the voxel filter of scal_voxel_downsample_device (45 key bits)
-        launch_deinterleave(s, reinterpret_cast<const float*>(raw[c]), nr[c], SoA4{sx.p, sy.p, sz.p, sw.p});
-        SCAL_TRY(vf.run(s, CSoA4{sx.p, sy.p, sz.p, sw.p}, d_n.p, nr[c], 0.4f, 45, SoA4{ox.p, oy.p, oz.p, ow.p}, d_n.p + 1));
-        launch_interleave(s, d_n.p + 1, nr[c], CSoA4{ox.p, oy.p, oz.p, ow.p}, reinterpret_cast<float*>(ds[c]));
-        VoxMeta hm;
-        SCAL_HIP(hipMemcpyAsync(&hm, vf.meta.p, sizeof hm, hipMemcpyDeviceToHost, s));
-        SCAL_HIP(hipMemcpyAsync(h_cnt.p, d_n.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-        SCAL_HIP(hipStreamSynchronize(s));
-        if (hm.error) {
-            set_error("scal_pipeline: loop verification: voxel grid bounding box needs more than 45 key bits");
-            return SCAL_E_CAPACITY;
-        }
-        n_ds[c] = h_cnt.p[0];
+        vcf.load_counted(s, reinterpret_cast<const float*>(raw[c]), nr[c]);
+        SCAL_TRY(vcf.filter(s, nr[c], 0.4f));
+        vcf.store(s, nr[c], reinterpret_cast<float*>(ds[c]));
+        if ((n_ds[c] = vcf.wait(s, "scal_pipeline: loop verification")) < 0) return n_ds[c];
     }
     out->n_src = n_ds[0], out->n_tgt = n_ds[1];
     scal_icp_result r;
@@ -435,11 +405,11 @@ int KeyframeStore::pgo_map(int kf_end, int skip, float leaf, float* out_xyzi, lo
         }
         int dst = 0;
         for (int j = 0; j < j_end; j += skip, ++n_sel) {  // updatePoses' result as it stands now (:815-822 under mKF)
-            PgoXf& e = h_xf.p[n_sel];
+            GatherXf& e = h_xf.p[n_sel];
             const std::vector<PoseVersion>& v = upd[static_cast<size_t>(j)];
             const Aff34 T = affine_f32(v.empty() ? pose6[static_cast<size_t>(j)].data() : v.back().p.data());
             std::memcpy(e.m, T.m, sizeof e.m);
-            e.src = h_off.p[j], e.dst = dst;
+            e.src = h_off.p[j], e.dst = dst, e.copy = 0, e.pad = 0;
             dst += h_off.p[j + 1] - h_off.p[j];
         }
         h_xf.p[n_sel].src = 0, h_xf.p[n_sel].dst = dst;
@@ -453,25 +423,19 @@ int KeyframeStore::pgo_map(int kf_end, int skip, float leaf, float* out_xyzi, lo
     // No event against stage D's appends: the gather reads only the arena ranges of confirmed keyframes, whose appends the host has
     // already synchronised on (check()), and later appends write behind them.  The verification stream only reads the arena too.
     const int ni = static_cast<int>(n);
-    SCAL_HIP(hipMemcpyAsync(d_xf.p, h_xf.p, sizeof(PgoXf) * (static_cast<size_t>(n_sel) + 1), hipMemcpyHostToDevice, s));
+    SCAL_HIP(hipMemcpyAsync(d_xf.p, h_xf.p, sizeof(GatherXf) * (static_cast<size_t>(n_sel) + 1), hipMemcpyHostToDevice, s));
     int grid = std::min(PGO_MAX_BLOCKS, div_up(ni, PGO_TILE));
     const int chunk = div_up(div_up(ni, grid), PGO_TILE) * PGO_TILE;
     grid = div_up(ni, chunk);  // every workgroup has points
-    SCAL_LAUNCH_PROF("k_pgo_gather", k_pgo_gather, dim3(grid), dim3(256), 0, s, arena.p, d_xf.p, n_sel, ni, chunk, mx.p, my.p, mz.p, mw.p, d_parts.p,
-                     d_mn.p);
+    const SoA4 in = mcf.in();
+    SCAL_LAUNCH_PROF("k_pgo_gather", k_pgo_gather, dim3(grid), dim3(256), 0, s, arena.p, d_xf.p, n_sel, ni, chunk, in.x, in.y, in.z, in.w, d_parts.p,
+                     mcf.d_n_in());
     SCAL_HIP(hipGetLastError());
-    SCAL_TRY(mvf.run(s, CSoA4{mx.p, my.p, mz.p, mw.p}, d_mn.p, ni, leaf, 45, SoA4{fx.p, fy.p, fz.p, fw.p}, d_mn.p + 1, nullptr, d_parts.p, grid));
-    launch_interleave(s, d_mn.p + 1, ni, CSoA4{fx.p, fy.p, fz.p, fw.p}, reinterpret_cast<float*>(d_map.p));
-    VoxMeta hm;
-    SCAL_HIP(hipMemcpyAsync(&hm, mvf.meta.p, sizeof hm, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipMemcpyAsync(h_mn.p, d_mn.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipStreamSynchronize(s));
-    if (hm.error) {
-        map_n = -1;
-        set_error("scal_pipeline_pgo_map: voxel grid bounding box needs more than 45 key bits");
-        return SCAL_E_CAPACITY;
-    }
-    map_n = h_mn.p[0];
+    SCAL_TRY(mcf.filter(s, ni, leaf, d_parts.p, grid));
+    mcf.store(s, ni, reinterpret_cast<float*>(d_map.p));
+    const int m_all = mcf.wait(s, "scal_pipeline_pgo_map");
+    map_n = m_all < 0 ? -1 : m_all;
+    if (m_all < 0) return m_all;
     *n_out = map_n;
     const long long m = std::min(map_n, cap);
     if (m > 0) {  // on the map's stream: a copy on the null stream would wait for the pipeline's lanes

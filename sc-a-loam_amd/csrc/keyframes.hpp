@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "voxel_dev.hpp"
+#include "gather_dev.hpp"
 #include <array>
 #include <vector>
 
@@ -24,13 +25,6 @@ struct PoseVersion {
     std::array<double, 6> p;
 };
 
-// one selected keyframe of a pose-graph map (k_pgo_gather's table; entry n_sel holds only dst = the map's size)
-struct PgoXf {
-    float m[12];   // affine_f32 of its current pose
-    int src, dst;  // its first arena record, its first position in the map
-    int pad[2];
-};
-
 // The pose-graph node's keyframeLaserClouds / keyframePoses (:629-637): an AoS xyzi arena of `max_points` records with the per-keyframe
 // offsets on the device (off[j] .. off[j + 1] = the pipeline's keyframe j), the poses and the database index of every keyframe on the
 // host.  Stage D appends (one thread), the verification thread reads: the host metadata is guarded by `mu`.
@@ -49,25 +43,19 @@ struct KeyframeStore {
     std::vector<std::vector<PoseVersion>> upd; // keyframe j's updated poses, oldest first (none: its gated pose holds)
     // verification (own stream, lane 5): submaps, their 0.4 m filter, ICP
     LaneStream vstream;
-    VoxelFilter vf;
+    CloudFilter vcf;          // the source's run, then the target's
     DevBuf<float4> raw_src, raw_tgt, ds_src, ds_tgt;
-    DevBuf<float> sx, sy, sz, sw, ox, oy, oz, ow;
-    DevBuf<int> d_n;          // [0] submap size, [1] filtered size
-    PinBuf<int> h_cnt;
     scal_icp_t* icp = nullptr;
     // pose-graph map (pubMap, :810-834; pgo_map_max_points > 0): its own stream (lane 2, which scal_pipeline's layout leaves empty),
     // filter and buffers; one map at a time (map_mu)
     int map_cap = 0;
     std::mutex map_mu;
     LaneStream mstream;
-    VoxelFilter mvf;
-    DevBuf<PgoXf> d_xf;
-    PinBuf<PgoXf> h_xf;
+    CloudFilter mcf;              // k_pgo_gather writes its input planes and count
+    DevBuf<GatherXf> d_xf;        // one entry per selected keyframe (m: affine_f32 of its current pose, never `copy`) and the sentinel
+    PinBuf<GatherXf> h_xf;
     DevBuf<unsigned> d_parts;     // per-workgroup bounding boxes of the gather, reduced by the filter's key kernel
-    DevBuf<float> mx, my, mz, mw, fx, fy, fz, fw;
     DevBuf<float4> d_map;         // the last map, xyzi
-    DevBuf<int> d_mn;             // [0] points before the filter, [1] after
-    PinBuf<int> h_mn;
     long long map_n = -1;         // points of the last map, -1 before the first
 
     ~KeyframeStore();

@@ -82,11 +82,7 @@ struct scal_mapmerge {
     DevBuf<int> d_error;
     int nb_cap = 0, pose_cap = 0;
     long long n_host = 0;  // upper bound of the running total known to the host (sum of the frame sizes added)
-    // downsampling of the merged map (lazily allocated)
-    VoxelFilter vf;
-    DevBuf<float> sx, sy, sz, sw, ox, oy, oz, ow;
-    DevBuf<int> d_n;
-    bool vf_ready = false;
+    CloudFilter cf;  // downsampling of the merged map (allocated on first use)
 };
 
 extern "C" int scal_mapmerge_create(const scal_mapmerge_config* cfg, scal_mapmerge_t** out) {
@@ -254,33 +250,18 @@ extern "C" int scal_mapmerge_downsample(scal_mapmerge_t* c, float leaf, float* o
     *n_out = 0;
     if (n == 0) return SCAL_OK;
     hipStream_t s = c->stream;
-    if (!c->vf_ready) {
-        const int cap = static_cast<int>(std::min<long long>(c->cap, 2000000000ll));
-        SCAL_TRY(c->vf.init(cap));
-        SCAL_TRY(c->sx.alloc(cap)); SCAL_TRY(c->sy.alloc(cap)); SCAL_TRY(c->sz.alloc(cap)); SCAL_TRY(c->sw.alloc(cap));
-        SCAL_TRY(c->ox.alloc(cap)); SCAL_TRY(c->oy.alloc(cap)); SCAL_TRY(c->oz.alloc(cap)); SCAL_TRY(c->ow.alloc(cap));
-        SCAL_TRY(c->d_n.alloc(2));
-        c->vf_ready = true;
-    }
+    if (!c->cf.ready()) SCAL_TRY(c->cf.init(static_cast<int>(std::min<long long>(c->cap, 2000000000ll))));
     const int ni = static_cast<int>(n);
-    launch_deinterleave(s, reinterpret_cast<const float*>(c->out.p), ni, SoA4{c->sx.p, c->sy.p, c->sz.p, c->sw.p});
-    SCAL_HIP(hipMemcpyAsync(c->d_n.p, &ni, sizeof(int), hipMemcpyHostToDevice, s));
-    SCAL_HIP(hipStreamSynchronize(s));
-    SCAL_TRY(c->vf.run(s, CSoA4{c->sx.p, c->sy.p, c->sz.p, c->sw.p}, c->d_n.p, ni, leaf, 45, SoA4{c->ox.p, c->oy.p, c->oz.p, c->ow.p}, c->d_n.p + 1));
-    int m = 0;
-    VoxMeta hm;
-    SCAL_HIP(hipMemcpyAsync(&m, c->d_n.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipMemcpyAsync(&hm, c->vf.meta.p, sizeof hm, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipStreamSynchronize(s));
-    if (hm.error) {
-        set_error("scal_mapmerge_downsample: the map's bounding box needs more voxel-key bits than the sort is given (leaf %g)", leaf);
-        return hm.error;
-    }
+    SCAL_TRY(c->cf.load(s, reinterpret_cast<const float*>(c->out.p), ni));
+    SCAL_TRY(c->cf.filter(s, ni, leaf));
+    const int m = c->cf.wait(s, "scal_mapmerge_downsample");
+    if (m < 0) return m;
     *n_out = m;
     const long long w = std::min<long long>(m, cap_points);
     if (w > 0) {  // the four centroid components come back separately and are interleaved on the host (offline path)
         std::vector<float> comp(static_cast<size_t>(w));
-        const float* src[4] = {c->ox.p, c->oy.p, c->oz.p, c->ow.p};
+        const SoA4 o = c->cf.out();
+        const float* src[4] = {o.x, o.y, o.z, o.w};
         for (int k = 0; k < 4; ++k) {
             SCAL_HIP(hipMemcpyAsync(comp.data(), src[k], sizeof(float) * static_cast<size_t>(w), hipMemcpyDeviceToHost, s));
             SCAL_HIP(hipStreamSynchronize(s));

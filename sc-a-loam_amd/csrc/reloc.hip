@@ -13,35 +13,23 @@
 //   scal_icp_align_guess_device                                  from Rz(-yaw)
 #include "common.hpp"
 #include "voxel_dev.hpp"
+#include "gather_dev.hpp"
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 namespace scal {
 
-// One keyframe of a submap: target positions [dst, next entry's dst) are arena records src, src + 1, ... moved by m (row-major 3x4,
-// local2global's f32 arithmetic), or copied as they are when `copy` is set (the candidate keyframe itself).  The table ends with a
-// sentinel whose dst is the submap's size.
-struct RlXf {
-    float m[12];
-    int src, dst, copy, pad;
-};
-
-// Streaming gather: one 16-byte load and one 16-byte store per point.  The table has at most 2 h + 2 entries (52 at the reference's
-// h = 25): every thread finds its entry by bisection (six steps over a table that stays in cache) and re-reads the transform only when
-// the entry changes along its grid-stride walk.
-__global__ void __launch_bounds__(256) k_rl_submap(const float4* __restrict__ arena, const RlXf* __restrict__ xf, int n_sel, int n,
+// Streaming gather of a submap (GatherXf table; `copy` marks the candidate keyframe itself): one 16-byte load and one 16-byte store per
+// point.  The table has at most 2 h + 2 entries (52 at the reference's h = 25): every thread finds its entry by bisection (six steps
+// over a table that stays in cache) and re-reads the transform only when the entry changes along its grid-stride walk.
+__global__ void __launch_bounds__(256) k_rl_submap(const float4* __restrict__ arena, const GatherXf* __restrict__ xf, int n_sel, int n,
                                                    float4* __restrict__ out, int* __restrict__ d_n) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *d_n = n;  // the filter's device-side count
     int cur = -1, s_src = 0, s_dst = 0, s_copy = 1;
     float T[12];
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        int s = 0;
-        for (int hi = n_sel - 1; s < hi;) {  // the last entry with dst <= i (entries of empty keyframes share their dst)
-            const int mid = (s + hi + 1) >> 1;
-            if (xf[mid].dst <= i) s = mid;
-            else hi = mid - 1;
-        }
+        const int s = gather_find(xf, n_sel, i);
         if (s != cur) {
             cur = s;
             s_src = xf[s].src, s_dst = xf[s].dst, s_copy = xf[s].copy;
@@ -49,13 +37,7 @@ __global__ void __launch_bounds__(256) k_rl_submap(const float4* __restrict__ ar
             for (int k = 0; k < 12; ++k) T[k] = xf[s].m[k];
         }
         const float4 p = arena[s_src + (i - s_dst)];
-        float4 q = p;
-        if (!s_copy) {
-            q.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[0], p.x), __fmul_rn(T[1], p.y)), __fmul_rn(T[2], p.z)), T[3]);
-            q.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[4], p.x), __fmul_rn(T[5], p.y)), __fmul_rn(T[6], p.z)), T[7]);
-            q.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T[8], p.x), __fmul_rn(T[9], p.y)), __fmul_rn(T[10], p.z)), T[11]);
-        }
-        out[i] = q;
+        out[i] = s_copy ? p : xf_point(T, p);
     }
 }
 
@@ -68,16 +50,12 @@ struct scal_reloc {
     LaneStream stream;      // released by `delete c`, after scal_reloc_destroy has synchronised it
     scal_sc_t* sc = nullptr;
     scal_icp_t* icp = nullptr;
-    VoxelFilter vf;
+    CloudFilter cf;
     int work = 0;                          // records the work buffers hold (max_query_points)
     DevBuf<float4> arena, raw, ds_src, ds_tgt;
-    DevBuf<float> ix, iy, iz, iw, ox, oy, oz, ow;
-    DevBuf<int> d_n;                       // [0] filter input count, [1] output count
     DevBuf<double> d_desc;                 // the query's descriptor (single query)
-    DevBuf<RlXf> d_xf;
-    PinBuf<RlXf> h_xf;
-    PinBuf<int> h_n;                       // [0] input count going up, [1] output count coming down
-    PinBuf<VoxMeta> h_meta;
+    DevBuf<GatherXf> d_xf;
+    PinBuf<GatherXf> h_xf;
     std::vector<int> off{0};               // arena offsets, one more than keyframes
     std::vector<double> poses;             // 12 per keyframe
     // query_batch: the filtered sources and descriptors of all queries (grown on demand)
@@ -114,13 +92,13 @@ extern "C" int scal_reloc_create(const scal_reloc_config* cfg, scal_reloc_t** ou
     int rc = SCAL_OK;
     auto A = [&](int r) { if (rc == SCAL_OK) rc = r; };
     A(c->stream.acquire(g.device, 0));
-    A(c->vf.init(c->work));
+    // the arena and the clouds ICP reads in front of the filter's buffers: measured, queries are 0.4 % slower the other way round
     A(c->arena.alloc(static_cast<size_t>(g.max_points)));
     A(c->raw.alloc(w)); A(c->ds_src.alloc(w)); A(c->ds_tgt.alloc(w));
-    for (DevBuf<float>* b : {&c->ix, &c->iy, &c->iz, &c->iw, &c->ox, &c->oy, &c->oz, &c->ow}) A(b->alloc(w));
-    A(c->d_n.alloc(2)); A(c->d_desc.alloc(1200)); A(c->d_xf.alloc(n_xf)); A(c->h_xf.alloc(n_xf)); A(c->h_n.alloc(2)); A(c->h_meta.alloc(1));
+    A(c->cf.init(c->work));
+    A(c->d_desc.alloc(1200)); A(c->d_xf.alloc(n_xf)); A(c->h_xf.alloc(n_xf));
     if (rc == SCAL_OK) {
-        c->vf.set_tag(".R");
+        c->cf.set_tag(".R");
         scal_sc_config sc{};
         sc.max_radius = g.sc_max_radius, sc.dist_thres = g.sc_dist_thres, sc.max_keyframes = g.max_keyframes, sc.float_math = g.float_math;
         sc.device = g.device, sc.n_shards = 1;
@@ -158,28 +136,13 @@ extern "C" int scal_reloc_size(scal_reloc_t* c) {
 
 extern "C" scal_sc_t* scal_reloc_sc(scal_reloc_t* c) { return c ? c->sc : nullptr; }
 
-// VoxelGrid(leaf) of the n records at d_in (device, AoS) into d_out, exactly as scal_voxel_downsample_device runs it; waits and
-// returns the number of centroids.  d_n[0] must hold n on the device already when n_on_device is set (k_rl_submap writes it).
-static int reloc_filter(scal_reloc* c, const float4* d_in, int n, float4* d_out, bool n_on_device, int* n_out) {
-    hipStream_t s = c->stream;
-    *n_out = 0;
-    if (n == 0) return SCAL_OK;
-    if (!n_on_device) {
-        c->h_n.p[0] = n;
-        SCAL_HIP(hipMemcpyAsync(c->d_n.p, c->h_n.p, sizeof(int), hipMemcpyHostToDevice, s));
-    }
-    const SoA4 in{c->ix.p, c->iy.p, c->iz.p, c->iw.p}, o{c->ox.p, c->oy.p, c->oz.p, c->ow.p};
-    launch_deinterleave(s, reinterpret_cast<const float*>(d_in), n, in);
-    SCAL_TRY(c->vf.run(s, CSoA4{in.x, in.y, in.z, in.w}, c->d_n.p, n, c->cfg.leaf, 45, o, c->d_n.p + 1));
-    launch_interleave(s, c->d_n.p + 1, n, CSoA4{o.x, o.y, o.z, o.w}, reinterpret_cast<float*>(d_out));
-    SCAL_HIP(hipMemcpyAsync(c->h_meta.p, c->vf.meta.p, sizeof(VoxMeta), hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipMemcpyAsync(c->h_n.p + 1, c->d_n.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipStreamSynchronize(s));
-    if (c->h_meta.p->error) {
-        set_error("scal_reloc: voxel grid bounding box needs more than 45 key bits (or 16383 cells per axis on the small-cloud path)");
-        return SCAL_E_CAPACITY;
-    }
-    *n_out = c->h_n.p[1];
+// VoxelGrid(leaf) of the n > 0 records loaded into the filter, exactly as scal_voxel_downsample_device runs it, into d_out; waits
+static int reloc_filter(scal_reloc* c, int n, float4* d_out, int* n_out) {
+    SCAL_TRY(c->cf.filter(c->stream, n, c->cfg.leaf));
+    c->cf.store(c->stream, n, reinterpret_cast<float*>(d_out));
+    const int m = c->cf.wait(c->stream, "scal_reloc");
+    if (m < 0) return m;
+    *n_out = m;
     return SCAL_OK;
 }
 
@@ -216,7 +179,8 @@ extern "C" int scal_reloc_add_keyframe(scal_reloc_t* c, const float* xyzi, int n
     int m = 0;
     if (n > 0) {
         SCAL_HIP(hipMemcpyAsync(c->raw.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, s));
-        SCAL_TRY(reloc_filter(c, c->raw.p, n, c->ds_src.p, false, &m));  // downSizeFilterScancontext (:629-631)
+        SCAL_TRY(c->cf.load(s, reinterpret_cast<const float*>(c->raw.p), n));
+        SCAL_TRY(reloc_filter(c, n, c->ds_src.p, &m));  // downSizeFilterScancontext (:629-631)
     }
     if (m > c->cfg.max_points - c->off[j]) {
         set_error("scal_reloc_add_keyframe: the cloud store is full (max_points = %d, keyframe %d has %d points after the filter)", c->cfg.max_points,
@@ -228,8 +192,9 @@ extern "C" int scal_reloc_add_keyframe(scal_reloc_t* c, const float* xyzi, int n
         SCAL_TRY(scal_sc_insert_descriptor(c->sc, desc));  // saveScancontextAndKeys
     } else {
         // an empty cloud: the filter did not run, the count it would have left is zero
-        if (m == 0) SCAL_HIP(hipMemsetAsync(c->d_n.p + 1, 0, sizeof(int), s));
-        SCAL_TRY(scal_sc_insert_cloud_device(c->sc, c->ox.p, c->oy.p, c->oz.p, c->d_n.p + 1, m));  // makeAndSaveScancontextAndKeys (:639)
+        if (m == 0) SCAL_HIP(hipMemsetAsync(c->cf.d_n_out(), 0, sizeof(int), s));
+        const SoA4 o = c->cf.out();
+        SCAL_TRY(scal_sc_insert_cloud_device(c->sc, o.x, o.y, o.z, c->cf.d_n_out(), m));  // makeAndSaveScancontextAndKeys (:639)
     }
     if (m > 0) SCAL_HIP(hipMemcpyAsync(c->arena.p + c->off[j], c->ds_src.p, sizeof(float4) * static_cast<size_t>(m), hipMemcpyDeviceToDevice, s));
     SCAL_HIP(hipStreamSynchronize(s));
@@ -268,22 +233,23 @@ static int reloc_verify(scal_reloc* c, const float4* d_src, int n_src, scal_relo
     const double* Pc = c->poses.data() + 12 * static_cast<size_t>(cand);
     int n_sel = 0, dst = 0;
     for (int j = j0; j <= j1; ++j, ++n_sel) {
-        RlXf& e = c->h_xf.p[n_sel];
+        GatherXf& e = c->h_xf.p[n_sel];
         e.src = c->off[j], e.dst = dst, e.copy = j == cand ? 1 : 0, e.pad = 0;
         reloc_relative(Pc, c->poses.data() + 12 * static_cast<size_t>(j), e.m);
         dst += c->off[j + 1] - c->off[j];
     }
-    RlXf& end = c->h_xf.p[n_sel];
+    GatherXf& end = c->h_xf.p[n_sel];
     std::memset(&end, 0, sizeof end);
     end.dst = dst, end.copy = 1;
     const int n = dst;
     int n_tgt = 0;
     if (n > 0) {
-        SCAL_HIP(hipMemcpyAsync(c->d_xf.p, c->h_xf.p, sizeof(RlXf) * (static_cast<size_t>(n_sel) + 1), hipMemcpyHostToDevice, s));
+        SCAL_HIP(hipMemcpyAsync(c->d_xf.p, c->h_xf.p, sizeof(GatherXf) * (static_cast<size_t>(n_sel) + 1), hipMemcpyHostToDevice, s));
         SCAL_LAUNCH_PROF("k_rl_submap", k_rl_submap, dim3(std::min(div_up(n, 256), 1024)), dim3(256), 0, s, c->arena.p, c->d_xf.p, n_sel, n, c->raw.p,
-                         c->d_n.p);
+                         c->cf.d_n_in());
         SCAL_HIP(hipGetLastError());
-        SCAL_TRY(reloc_filter(c, c->raw.p, n, c->ds_tgt.p, true, &n_tgt));  // downSizeFilterICP (:491-492)
+        c->cf.load_counted(s, reinterpret_cast<const float*>(c->raw.p), n);
+        SCAL_TRY(reloc_filter(c, n, c->ds_tgt.p, &n_tgt));  // downSizeFilterICP (:491-492)
     }
     out->n_tgt = n_tgt;
     float G[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -310,11 +276,13 @@ static int reloc_front(scal_reloc* c, const float* xyzi, int n, float4* d_src, d
     *n_src = 0;
     if (n > 0) {
         SCAL_HIP(hipMemcpyAsync(c->raw.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, s));
-        SCAL_TRY(reloc_filter(c, c->raw.p, n, d_src, false, n_src));
+        SCAL_TRY(c->cf.load(s, reinterpret_cast<const float*>(c->raw.p), n));
+        SCAL_TRY(reloc_filter(c, n, d_src, n_src));
     } else {  // no pinned word involved: nothing waits for this before the next query's filter writes its own count
-        SCAL_HIP(hipMemsetAsync(c->d_n.p + 1, 0, sizeof(int), s));
+        SCAL_HIP(hipMemsetAsync(c->cf.d_n_out(), 0, sizeof(int), s));
     }
-    return sc_make_cloud_device(c->sc, c->ox.p, c->oy.p, c->oz.p, c->d_n.p + 1, *n_src, d_desc);
+    const SoA4 o = c->cf.out();
+    return sc_make_cloud_device(c->sc, o.x, o.y, o.z, c->cf.d_n_out(), *n_src, d_desc);
 }
 
 extern "C" int scal_reloc_query(scal_reloc_t* c, const float* xyzi, int n, scal_reloc_result* out) {

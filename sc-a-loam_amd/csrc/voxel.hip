@@ -439,6 +439,32 @@ void launch_interleave(hipStream_t s, const int* d_n, int n_cap, CSoA4 in, float
     if (n_cap > 0) SCAL_LAUNCH("k_interleave4", k_interleave4, dim3(div_up(n_cap, 256)), dim3(256), 0, s, d_n, in, aos);
 }
 
+int CloudFilter::init(int capacity) {
+    SCAL_TRY(vf.init(capacity));
+    for (DevBuf<float>* b : {plane_in, plane_out})
+        for (int k = 0; k < 4; ++k) SCAL_TRY(b[k].alloc(static_cast<size_t>(capacity)));
+    SCAL_TRY(d_n.alloc(2));
+    return h.alloc(1);
+}
+
+int CloudFilter::load(hipStream_t s, const float* d_xyzi, int n) {
+    h.p->n_in = n;
+    SCAL_HIP(op_memcpy_async(d_n.p, &h.p->n_in, sizeof(int), hipMemcpyHostToDevice, s));
+    load_counted(s, d_xyzi, n);
+    return SCAL_OK;
+}
+
+int CloudFilter::wait(hipStream_t s, const char* who) {
+    SCAL_HIP(op_memcpy_async(&h.p->meta, vf.meta.p, sizeof(VoxMeta), hipMemcpyDeviceToHost, s));
+    SCAL_HIP(op_memcpy_async(&h.p->n_out, d_n.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+    SCAL_HIP(op_stream_synchronize(s));
+    if (h.p->meta.error) {
+        set_error("%s: voxel grid bounding box needs more than 45 key bits (or 16383 cells per axis on the small-cloud path)", who);
+        return SCAL_E_CAPACITY;
+    }
+    return h.p->n_out;
+}
+
 }  // namespace scal
 
 using namespace scal;
@@ -446,10 +472,9 @@ using namespace scal;
 struct scal_voxel {
     int device = 0, cap = 0;
     LaneStream stream;  // released by `delete c`, after scal_voxel_destroy has synchronised it
-    VoxelFilter vf;
-    DevBuf<float> aos, ix, iy, iz, iw, ox, oy, oz, ow;
-    DevBuf<int> d_n;  // [0] in, [1] out
-    HostStage hs;     // pinned staging of the host-array entry point (first call)
+    CloudFilter cf;
+    DevBuf<float> aos;
+    HostStage hs;  // pinned staging of the host-array entry point (first call)
     std::mutex mu;
 };
 
@@ -462,12 +487,8 @@ extern "C" int scal_voxel_create(int max_points, int device, scal_voxel_t** out)
     SCAL_TRY(select_device(device));
     auto* c = new scal_voxel();
     c->device = device, c->cap = max_points;
-    int rc = c->vf.init(max_points);
-    auto A = [&](int r) { if (rc == SCAL_OK) rc = r; };
-    A(c->aos.alloc((size_t)max_points * 4));
-    A(c->ix.alloc(max_points)); A(c->iy.alloc(max_points)); A(c->iz.alloc(max_points)); A(c->iw.alloc(max_points));
-    A(c->ox.alloc(max_points)); A(c->oy.alloc(max_points)); A(c->oz.alloc(max_points)); A(c->ow.alloc(max_points));
-    A(c->d_n.alloc(2));
+    int rc = c->cf.init(max_points);
+    if (rc == SCAL_OK) rc = c->aos.alloc((size_t)max_points * 4);
     if (rc == SCAL_OK) rc = c->stream.acquire(c->device, 0);
     if (rc != SCAL_OK) {
         delete c;
@@ -505,21 +526,12 @@ static int voxel_downsample(scal_voxel_t* c, const float* xyzi, int n, float lea
         SCAL_HIP(c->hs.h2d(c->aos.p, xyzi, sizeof(float) * 4 * n, s));
         d_in = c->aos.p;
     }
-    SCAL_HIP(op_memcpy_async(c->d_n.p, &n, sizeof(int), hipMemcpyHostToDevice, s));
-    SoA4 in{c->ix.p, c->iy.p, c->iz.p, c->iw.p}, o{c->ox.p, c->oy.p, c->oz.p, c->ow.p};
-    launch_deinterleave(s, d_in, n, in);
-    SCAL_TRY(c->vf.run(s, CSoA4{in.x, in.y, in.z, in.w}, c->d_n.p, n, leaf, 45, o, c->d_n.p + 1));
-    launch_interleave(s, c->d_n.p + 1, n, CSoA4{o.x, o.y, o.z, o.w}, on_device ? out_xyzi : c->aos.p);
-    VoxMeta hm;
-    SCAL_HIP(op_memcpy_async(&hm, c->vf.meta.p, sizeof hm, hipMemcpyDeviceToHost, s));
-    int m = 0;
-    SCAL_HIP(op_memcpy_async(&m, c->d_n.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    SCAL_HIP(op_stream_synchronize(s));
+    SCAL_TRY(c->cf.load(s, d_in, n));
+    SCAL_TRY(c->cf.filter(s, n, leaf));
+    c->cf.store(s, n, on_device ? out_xyzi : c->aos.p);
+    const int m = c->cf.wait(s, "scal_voxel_downsample");
     c->hs.finish();  // the upload's staging is free again
-    if (hm.error) {
-        set_error("voxel grid bounding box needs more than 45 key bits (or 16383 cells per axis on the small-cloud path)");
-        return SCAL_E_CAPACITY;
-    }
+    if (m < 0) return m;
     if (!on_device) {
         SCAL_HIP(c->hs.d2h(out_xyzi, c->aos.p, sizeof(float) * 4 * m, s));
         SCAL_HIP(op_stream_synchronize(s));

@@ -13,11 +13,12 @@ struct VoxMeta {
     int b0, b1;                 // bit widths of the x and y voxel coordinates inside the key
 };
 
-struct SoA4 {
-    float *x, *y, *z, *w;
-};
 struct CSoA4 {
     const float *x, *y, *z, *w;
+};
+struct SoA4 {
+    float *x, *y, *z, *w;
+    operator CSoA4() const { return CSoA4{x, y, z, w}; }
 };
 
 // Optional epilogue of a filter run, executed by its last kernel (saves one-thread launches on dependent chains):
@@ -55,6 +56,41 @@ struct VoxelFilter {
     // bounding-box launches are skipped, the key kernel reduces the parts itself.
     int run(hipStream_t s, CSoA4 in, const int* d_n, int n_bound, float leaf, int max_bits, SoA4 out, int* d_n_out, const VoxTail* tail = nullptr,
             const unsigned* ext_parts = nullptr, int n_parts = 0);
+};
+
+void launch_deinterleave(hipStream_t s, const float* aos, int n, SoA4 o);
+void launch_interleave(hipStream_t s, const int* d_n, int n_cap, CSoA4 in, float* aos);
+
+// pcl::VoxelGrid over a cloud of 16-byte xyzi records in HBM (45 key bits): the filter, its SoA planes, the device counts and the
+// pinned words the host reads the result from.  A caller chains the steps it needs on its stream, `n` being the host-known bound of
+// the input count throughout:
+//   load (or load_counted behind a producer of the records, or a producer of the input planes) -> filter -> store -> wait
+struct CloudFilter {
+    struct Host {
+        int n_in, n_out;
+        VoxMeta meta;
+    };
+    VoxelFilter vf;
+    DevBuf<float> plane_in[4], plane_out[4];
+    DevBuf<int> d_n;  // [0] points in, [1] centroids out
+    PinBuf<Host> h;
+
+    int init(int capacity);
+    bool ready() const { return h.p != nullptr; }
+    void set_tag(const char* tag) { vf.set_tag(tag); }
+    SoA4 in() const { return SoA4{plane_in[0].p, plane_in[1].p, plane_in[2].p, plane_in[3].p}; }      // a producer may fill these itself (and *d_n_in())
+    SoA4 out() const { return SoA4{plane_out[0].p, plane_out[1].p, plane_out[2].p, plane_out[3].p}; }  // *d_n_out() centroids, valid behind filter()
+    int* d_n_in() const { return d_n.p; }
+    int* d_n_out() const { return d_n.p + 1; }
+    // n records at d_xyzi -> the input planes; load() also uploads n, load_counted() expects a kernel to have written *d_n_in()
+    int load(hipStream_t s, const float* d_xyzi, int n);
+    void load_counted(hipStream_t s, const float* d_xyzi, int n) { launch_deinterleave(s, d_xyzi, n, in()); }
+    int filter(hipStream_t s, int n, float leaf, const unsigned* ext_parts = nullptr, int n_parts = 0) {
+        return vf.run(s, in(), d_n.p, n, leaf, 45, out(), d_n.p + 1, nullptr, ext_parts, n_parts);
+    }
+    void store(hipStream_t s, int n, float* d_xyzi) { launch_interleave(s, d_n.p + 1, n, out(), d_xyzi); }
+    // reads the count and the filter's error word back and synchronises s: the number of centroids, or SCAL_E_CAPACITY ("<who>: ...")
+    int wait(hipStream_t s, const char* who);
 };
 
 }  // namespace scal
@@ -97,6 +133,4 @@ __device__ inline void vox_bbox_block_store(unsigned* parts, int block, bool hav
     vox_bbox_block_store(parts, block, lo, hi);
 }
 #endif
-void launch_deinterleave(hipStream_t s, const float* aos, int n, SoA4 o);
-void launch_interleave(hipStream_t s, const int* d_n, int n_cap, CSoA4 in, float* aos);
 }  // namespace scal

@@ -42,6 +42,38 @@ def test_voxel_edge_cases(O, S):
     vg.close()
 
 
+def test_voxel_small_path_axis_limit(O, S):
+    """The one filter error reachable from outside: a cloud of <= 8192 points with more than 16383 cells along an axis
+    (25001 x 1 x 1 voxels here, far below PCL's 2^31 guard) is refused with E_CAPACITY by the host-array and the device
+    entry alike, and the context filters small and large clouds correctly afterwards."""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    hip.hipFree.argtypes = [ctypes.c_void_p]
+    vg = S.VoxelGrid(max_points=100000)
+    wide = np.array([[0.0, 0.0, 0.0, 1.0], [10000.0, 0.0, 0.0, 1.0]], np.float32)
+    with pytest.raises(S.ScalError) as e:
+        vg.filter(wide, 0.4)
+    assert e.value.code == S.E_CAPACITY
+    rng = np.random.default_rng(1)
+    p = rng.uniform(-30, 30, (5000, 4)).astype(np.float32)
+    p = np.concatenate([p, p[:500]])
+    big = np.random.default_rng(2).uniform(-30, 30, (9000, 4)).astype(np.float32)
+    for cloud in (p, big):
+        o, guard = O.voxel_grid(cloud, 0.4, order_mode=1)
+        assert guard == 0
+        assert np.array_equal(_bits(vg.filter(cloud, 0.4)), _bits(o))
+    d_in, d_out = ctypes.c_void_p(), ctypes.c_void_p()
+    assert hip.hipMalloc(ctypes.byref(d_in), wide.nbytes) == 0 and hip.hipMalloc(ctypes.byref(d_out), wide.nbytes) == 0
+    assert hip.hipMemcpy(d_in, wide.ctypes.data, wide.nbytes, 1) == 0
+    with pytest.raises(S.ScalError) as e:
+        vg.filter_device(d_in, 2, 0.4, d_out)
+    assert e.value.code == S.E_CAPACITY
+    hip.hipFree(d_out), hip.hipFree(d_in)
+    vg.close()
+
+
 def test_voxel_idempotent_and_order(O, S, golden):
     """Size-independent properties: output sorted by voxel index, one point per voxel, re-filtering is stable."""
     a = golden("KAIST03_000007.npy")

@@ -40,7 +40,8 @@ def run_pipeline(S, d_scans, ns, cap, W, kf_points, ahead=4):
             rec = p.pop_loop(wait=wait)
             if rec is None:
                 return
-            lat.append(time.perf_counter() - t_det[rec["seq"]])
+            now = time.perf_counter()
+            lat.append(now - t_det.get(rec["seq"], now))  # a record can be ready before its scan's result has been popped: no wait
             loops.append(rec)
 
     t0 = None
