@@ -827,6 +827,73 @@ int scal_reloc_query(scal_reloc_t* ctx, const float* xyzi, int n, scal_reloc_res
 int scal_reloc_query_batch(scal_reloc_t* ctx, const float* xyzi, const int* offsets /* [nq + 1] */, int nq, scal_reloc_result* out /* [nq] */);
 scal_sc_t* scal_reloc_sc(scal_reloc_t* ctx);    /* the session's database (owned by the context), e.g. for scal_sc_cross_search between two sessions */
 
+/* ------------------------------------------------------------------ dynamic-point removal from a merged keyframe map
+ * An extension: the reference's README names the second offline use of a saved session (Scans/ + optimized_poses.txt) - "remove
+ * dynamic points using these saved keyframe poses and scans ... see our Removert project" - and ships no code for it.  The semantics
+ * are those of the CPU restatement python/scaloam/removert.py, which the device path equals bit for bit (DESIGN.md section 8.10 has
+ * the differences from Removert itself).
+ *
+ * Projection of a point p from a pose [R|t] (sensor to world) at `res` degrees per pixel, H = max(1, lround((fov_up - fov_down) / res)),
+ * W = lround(360 / res); all in f64, every operation rounded once (no fused multiply-add), in this order:
+ *     d = p - t,   x = (R00 d0 + R10 d1) + R20 d2   (y, z: columns 1, 2),   r = (float)sqrt((x x + y y) + z z),
+ *     az = atan2(y, x),   el = atan2(z, sqrt(x x + y y)),   u = (az + pi) / (2 pi) * W,   col = min((int)u, W - 1),
+ *     v = (fu - el) / (fu - fd) * H   with fu = fov_up_deg * (pi / 180), fd likewise.
+ * The point takes part iff min_range <= r <= max_range (both in f32) and 0 <= v < H; row = (int)v.  Scan points are projected from
+ * the identity pose.  A scan's range image at `res` holds per pixel the smallest r of its points (empty where none falls).
+ * Keyframe k HITS map point m at `res` iff m takes part in k's view, its pixel in k's image is not empty and (scan_r - r_m) >
+ * diff_thres in f32: k's ray went through the place where m lies.  hits(m, res) = the number of keyframes that hit m, and
+ *     dynamic(m) = [some remove resolution has hits >= min_hits] AND [every revert resolution has hits >= 1].
+ * Pointwise: the result does not depend on the order of points or keyframes.  Hit counts saturate at 65535.
+ *
+ * Device memory comes from the config and does not grow with the session: a run of more than max_keyframes keyframes, or of more
+ * than max_scan_points scan records, goes through the device in chunks of consecutive keyframes (hits add up, the result is the
+ * same).  (point, keyframe) pairs are culled by XY cells of cell_size: a cell's points are tested against the keyframes within
+ * max_range plus the cell's half diagonal of its centre, which drops no pair the range test would accept. */
+typedef struct {
+    int max_points;           /* map records (<= 2^30) */
+    int max_keyframes;        /* keyframes resident at once */
+    int max_scan_points;      /* scan records resident at once; no single scan may have more */
+    int max_resolutions;      /* remove + revert resolutions of one run, 1 .. 8 */
+    int min_hits;             /* >= 1 (and <= 65535) */
+    int device;
+    double fov_up_deg, fov_down_deg;          /* -90 <= fov_down < fov_up <= 90 */
+    double min_range, max_range, diff_thres;  /* all > 0, min_range <= max_range */
+    double min_res_deg;       /* the finest resolution a run may ask for (it sizes the images); 0 = 1.0 */
+    double cell_size;         /* culling cells; 0 = max_range / 8 */
+} scal_removert_config;
+typedef struct {
+    long long points, keyframes, dynamic;
+    long long pairs_tested;       /* (point, keyframe) pairs that were projected */
+    long long pairs_bruteforce;   /* points * keyframes */
+} scal_removert_stats;
+typedef struct scal_removert scal_removert_t;
+/* SCAL_E_NO_DEVICE without a gfx950 device; SCAL_E_ARG (before any device work) for a NULL pointer, a capacity < 1, max_resolutions
+ * > 8, a range, threshold, min_res_deg or cell_size that is NaN, infinite or negative (zero too where the config has no default for
+ * it), fov_up <= fov_down or outside +-90, min_range > max_range, min_hits < 1 */
+int scal_removert_create(const scal_removert_config* cfg, scal_removert_t** ctx);
+void scal_removert_destroy(scal_removert_t* ctx);
+/* the map: n xyzi records in the world frame, copied to the device and binned into cells.  Records that are not finite never take
+ * part.  SCAL_E_TOO_MANY: n > max_points. */
+int scal_removert_set_map(scal_removert_t* ctx, const float* xyzi, int n);
+/* the same for records already in device memory, as scal_mapmerge_device_points returns them (wait for the merge first:
+ * scal_mapmerge_size does).  Nothing is copied: the records must stay where they are until the next set_map. */
+int scal_removert_set_map_device(scal_removert_t* ctx, const float* d_xyzi, int n);
+/* K keyframes: scan k = host records [offsets[k], offsets[k + 1]) of scans_xyzi in its sensor frame (offsets[0] = 0, non-decreasing),
+ * poses12 [K][12] as optimized_poses.txt has them.  dynamic_out [n] (host), hits_out [n] (host, may be NULL): hits at the finest
+ * remove resolution (the first of the smallest).  SCAL_E_STATE: no map set.  SCAL_E_ARG: a NULL pointer, K < 0, n_remove < 1,
+ * n_revert < 0, more than max_resolutions in all, a resolution that is NaN, below min_res_deg or above 360, bad offsets, a pose that
+ * is not finite.  SCAL_E_TOO_MANY: one scan has more than max_scan_points records. */
+int scal_removert_run(scal_removert_t* ctx, const float* scans_xyzi, const int* offsets, int K, const double* poses12,
+                      const double* remove_res, int n_remove, const double* revert_res, int n_revert, unsigned char* dynamic_out,
+                      unsigned short* hits_out_or_NULL, scal_removert_stats* stats);
+/* the map records of the last run that are static (which = 0) or dynamic (which = 1), in input order: *n_out of them, the first cap
+ * written to out_xyzi (host; may be NULL with cap 0).  SCAL_E_STATE before the first run on this map. */
+int scal_removert_compact(scal_removert_t* ctx, int which, float* out_xyzi, int cap, int* n_out);
+/* keyframe k's range image at resolution res_index (remove resolutions first, then revert) of the last run, +inf where empty: for
+ * tracing a parity failure to the half of the algorithm that caused it.  SCAL_E_ARG unless H and W are that image's; SCAL_E_STATE
+ * before the first run or for a keyframe that is not in the last chunk the run processed (its images are gone). */
+int scal_removert_scan_image(scal_removert_t* ctx, int k, int res_index, float* out /* [H * W] */, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

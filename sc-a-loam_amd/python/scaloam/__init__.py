@@ -97,6 +97,18 @@ class RelocResult(C.Structure):
     _fields_ = [("sc", SCResult), ("status", C.c_int), ("n_src", C.c_int), ("n_tgt", C.c_int), ("icp", ICPResult), ("pose12", C.c_double * 12)]
 
 
+class RemovertConfig(C.Structure):
+    _fields_ = [("max_points", C.c_int), ("max_keyframes", C.c_int), ("max_scan_points", C.c_int), ("max_resolutions", C.c_int),
+                ("min_hits", C.c_int), ("device", C.c_int), ("fov_up_deg", C.c_double), ("fov_down_deg", C.c_double),
+                ("min_range", C.c_double), ("max_range", C.c_double), ("diff_thres", C.c_double), ("min_res_deg", C.c_double),
+                ("cell_size", C.c_double)]
+
+
+class RemovertStats(C.Structure):
+    _fields_ = [("points", C.c_longlong), ("keyframes", C.c_longlong), ("dynamic", C.c_longlong), ("pairs_tested", C.c_longlong),
+                ("pairs_bruteforce", C.c_longlong)]
+
+
 class MapMergeConfig(C.Structure):
     _fields_ = [("max_points", C.c_longlong), ("max_frame_points", C.c_int), ("device", C.c_int)]
 
@@ -178,6 +190,7 @@ EXPORTED_SYMBOLS = [
     "scal_posegraph_add_between", "scal_posegraph_clear_edges", "scal_posegraph_optimize", "scal_posegraph_get_nodes", "scal_posegraph_get_edge_weights",
     "scal_sc_detect_between", "scal_sc_detect_between_device", "scal_sc_cross_matrix", "scal_sc_cross_search", "scal_icp_align_guess", "scal_icp_align_guess_device",
     "scal_reloc_create", "scal_reloc_destroy", "scal_reloc_size", "scal_reloc_add_keyframe", "scal_reloc_query", "scal_reloc_query_batch", "scal_reloc_sc",
+    "scal_removert_create", "scal_removert_destroy", "scal_removert_set_map", "scal_removert_set_map_device", "scal_removert_run", "scal_removert_compact", "scal_removert_scan_image",
 ]
 
 _lib = None
@@ -355,6 +368,16 @@ def lib():
         L.scal_reloc_query_batch.argtypes = [vp, _f32p, _i32p, C.c_int, C.POINTER(RelocResult)]
         L.scal_reloc_sc.argtypes = [vp]
         L.scal_reloc_sc.restype = C.c_void_p
+    if hasattr(L, "scal_removert_create"):  # absent from older builds compared through SCALOAM_LIB
+        L.scal_removert_create.argtypes = [C.POINTER(RemovertConfig), C.POINTER(vp)]
+        L.scal_removert_destroy.argtypes = [vp]
+        L.scal_removert_destroy.restype = None
+        L.scal_removert_set_map.argtypes = [vp, _f32p, C.c_int]
+        L.scal_removert_set_map_device.argtypes = [vp, vp, C.c_int]
+        L.scal_removert_run.argtypes = [vp, _f32p, _i32p, C.c_int, _f64p, _f64p, C.c_int, _f64p, C.c_int, C.POINTER(C.c_ubyte),
+                                        C.POINTER(C.c_ushort), C.POINTER(RemovertStats)]
+        L.scal_removert_compact.argtypes = [vp, C.c_int, _f32p, C.c_int, _i32p]
+        L.scal_removert_scan_image.argtypes = [vp, C.c_int, C.c_int, _f32p, C.c_int, C.c_int]
     L.scal_keyframe_gate_init.argtypes = [C.POINTER(KeyframeGateState), C.c_double, C.c_double]
     L.scal_keyframe_gate.argtypes = [C.POINTER(KeyframeGateState), _f64p, _f64p, _i32p]
     for fn in ("scal_pipeline_sc_of", "scal_pipeline_map_of"):
@@ -1049,6 +1072,89 @@ class Relocalizer:
         res = (RelocResult * max(1, len(cs)))()
         _check(lib().scal_reloc_query_batch(self.h, _p(cat, _f32p), _p(off, _i32p), len(cs), res))
         return [self._result(r) for r in res[:len(cs)]]
+
+
+class Removert:
+    """scal_removert: dynamic-point removal from a merged keyframe map.  A keyframe whose ray passes through the place of a map point
+    hits it; a point is dynamic when some remove resolution has min_hits hits and every revert resolution has one
+    (include/scaloam_hip.h has the projection, scaloam/removert.py the CPU restatement the device equals bit for bit).  A session
+    longer than max_keyframes, or with more scan points than max_scan_points, is run in chunks with the same result."""
+
+    def __init__(self, max_points, max_keyframes, max_scan_points, max_resolutions=4, fov_up_deg=25.0, fov_down_deg=-25.0, min_range=0.5,
+                 max_range=80.0, diff_thres=0.1, min_hits=1, min_res_deg=0.0, cell_size=0.0, device=0):
+        self.h = C.c_void_p()
+        self.fov = (float(fov_up_deg), float(fov_down_deg))
+        cfg = RemovertConfig(int(max_points), int(max_keyframes), int(max_scan_points), int(max_resolutions), int(min_hits), device,
+                             fov_up_deg, fov_down_deg, min_range, max_range, diff_thres, min_res_deg, cell_size)
+        _check(lib().scal_removert_create(C.byref(cfg), C.byref(self.h)))
+        self.n = 0
+        self.res = ()
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.scal_removert_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def set_map(self, map_xyzi):
+        m = _f32(map_xyzi).reshape(-1, 4)
+        _check(lib().scal_removert_set_map(self.h, _p(m, _f32p), m.shape[0]))
+        self.n = m.shape[0]
+
+    def set_map_device(self, d_xyzi_ptr, n):
+        """n 16-byte xyzi records in device memory; they are used in place and must stay valid until the next set_map"""
+        _check(lib().scal_removert_set_map_device(self.h, d_xyzi_ptr, int(n)))
+        self.n = int(n)
+
+    def run(self, scans, poses12, remove_res=(2.5, 2.0, 1.5), revert_res=(5.0,), want_hits=False):
+        """on the map set last; returns (mask uint8 [n], stats dict[, hits uint16 [n] at the finest remove resolution])"""
+        cs = [_f32(s).reshape(-1, 4) for s in scans]
+        off = np.zeros(len(cs) + 1, np.int64)
+        off[1:] = np.cumsum([s.shape[0] for s in cs])
+        if off[-1] > 2**31 - 1:
+            raise ValueError("more points than 32-bit offsets hold")
+        off = off.astype(np.int32)
+        P = _f64(np.asarray(poses12, np.float64).reshape(-1, 12))
+        if P.shape[0] != len(cs):
+            raise ValueError("one pose12 row per scan is needed")
+        cat = np.ascontiguousarray(np.concatenate(cs, 0)) if cs else np.zeros((0, 4), np.float32)
+        rm, rv = _f64(np.asarray(remove_res, np.float64).reshape(-1)), _f64(np.asarray(revert_res, np.float64).reshape(-1))
+        mask = np.zeros(max(self.n, 1), np.uint8)
+        hits = np.zeros(max(self.n, 1), np.uint16) if want_hits else None
+        st = RemovertStats()
+        _check(lib().scal_removert_run(self.h, _p(cat, _f32p), _p(off, _i32p), len(cs), _p(P, _f64p), _p(rm, _f64p), rm.shape[0], _p(rv, _f64p),
+                                       rv.shape[0], _p(mask, C.POINTER(C.c_ubyte)), _p(hits, C.POINTER(C.c_ushort)), C.byref(st)))
+        self.res = tuple(rm) + tuple(rv)
+        stats = dict(points=st.points, keyframes=st.keyframes, dynamic=st.dynamic, pairs_tested=st.pairs_tested,
+                     pairs_bruteforce=st.pairs_bruteforce)
+        return (mask[:self.n], stats, hits[:self.n]) if want_hits else (mask[:self.n], stats)
+
+    def remove(self, map_xyzi, scans, poses12, remove_res=(2.5, 2.0, 1.5), revert_res=(5.0,), want_hits=False):
+        self.set_map(map_xyzi)
+        return self.run(scans, poses12, remove_res, revert_res, want_hits)
+
+    def remove_device(self, mapmerge, scans, poses12, remove_res=(2.5, 2.0, 1.5), revert_res=(5.0,), want_hits=False):
+        """on the points a MapMerge holds in device memory (they never leave it); size() waits for the merge"""
+        self.set_map_device(mapmerge.device_points(), mapmerge.size())
+        return self.run(scans, poses12, remove_res, revert_res, want_hits)
+
+    def scan_image(self, k, i):
+        """keyframe k's [H, W] range image at resolution i of the last run (remove resolutions first), +inf where empty"""
+        if not 0 <= i < len(self.res):
+            raise ValueError("no such resolution in the last run")
+        from . import removert as _rv
+        H, W = _rv.image_shape(self.res[i], *self.fov)
+        out = np.zeros((H, W), np.float32)
+        _check(lib().scal_removert_scan_image(self.h, int(k), int(i), _p(out, _f32p), H, W))
+        return out
+
+    def compact(self, which):
+        """the static (0) or dynamic (1) points of the last run, in input order"""
+        m = C.c_int(0)
+        out = np.zeros((max(self.n, 1), 4), np.float32)
+        _check(lib().scal_removert_compact(self.h, int(which), _p(out, _f32p), self.n, C.byref(m)))
+        return out[:m.value].copy()
 
 
 class MapMerge:

@@ -3,7 +3,9 @@
 optimized_poses.txt), merges the keyframes into the global frame (near-range removal 2 m) with scal_mapmerge_*, writes the map as
 a binary PCD.  `--check` also runs the CPU oracle and compares bit for bit.  `--refine ROUNDS` first refines the poses with
 scal_refine_* (every keyframe thinned at --refine-leaf and aligned against all the others, keyframe 0 held), writes them to
-refined_poses.txt beside the session's optimized_poses.txt and merges with them."""
+refined_poses.txt beside the session's optimized_poses.txt and merges with them.  `--remove-dynamic` runs scal_removert_* on the merged map
+where it lies in device memory, with the poses the merge used (the refined ones after --refine), reports the counts and writes the
+static points beside the map as *_static.pcd - after VoxelGrid(--leaf) if a leaf is given."""
 import argparse
 import glob
 import os
@@ -25,6 +27,10 @@ def main():
     ap.add_argument("--refine", type=int, default=0, metavar="ROUNDS", help="multiview refine of the poses before the merge")
     ap.add_argument("--refine-leaf", type=float, default=0.4)
     ap.add_argument("--max-corr", type=float, default=2.0)
+    ap.add_argument("--remove-dynamic", action="store_true", help="remove the points other keyframes look through (scal_removert)")
+    ap.add_argument("--remove-res", type=float, nargs="+", default=[2.5, 2.0, 1.5], help="remove resolutions, degrees per pixel")
+    ap.add_argument("--revert-res", type=float, nargs="*", default=[5.0], help="revert resolutions, degrees per pixel (may be empty)")
+    ap.add_argument("--leaf", type=float, default=0.0, help="VoxelGrid leaf for the static map (0 = none)")
     a = ap.parse_args()
     import scaloam as S
     from scaloam import formats as F
@@ -57,6 +63,23 @@ def main():
     path = a.out or os.path.join(a.data_dir, f"map_{lo}_to_{hi}_with_intensity.pcd")
     F.write_pcd_binary(path, out)
     print("written", path)
+    if a.remove_dynamic:
+        n_res = len(a.remove_res) + len(a.revert_res)
+        rm = S.Removert(out.shape[0] + 1, min(len(frames), 256), 256 * max(f.shape[0] for f in frames), max_resolutions=n_res,
+                        min_res_deg=min(a.remove_res + a.revert_res + [1.0]))
+        mask, st = rm.remove_device(mm, frames, poses, a.remove_res, a.revert_res)
+        print(f"remove-dynamic: {st['dynamic']} of {st['points']} points dynamic; {st['pairs_tested']} of {st['pairs_bruteforce']} "
+              f"(point, keyframe) pairs tested")
+        static = rm.compact(0)
+        rm.close()
+        if a.leaf > 0 and static.shape[0]:
+            vg = S.VoxelGrid(max_points=static.shape[0])
+            static = vg.filter(static, a.leaf)
+            vg.close()
+            print(f"VoxelGrid({a.leaf}): {static.shape[0]} points")
+        path = os.path.splitext(path)[0] + "_static.pcd"
+        F.write_pcd_binary(path, static)
+        print("written", path)
 
 
 if __name__ == "__main__":
