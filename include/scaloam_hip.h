@@ -894,6 +894,47 @@ int scal_removert_compact(scal_removert_t* ctx, int which, float* out_xyzi, int 
  * before the first run or for a keyframe that is not in the last chunk the run processed (its images are gone). */
 int scal_removert_scan_image(scal_removert_t* ctx, int k, int res_index, float* out /* [H * W] */, int H, int W);
 
+/* ------------------------------------------------------------------ radius neighbour index
+ * An extension (no counterpart in the reference): how many records of an indexed cloud lie within a fixed radius of each query, and
+ * how near the nearest of them is.  It is the primitive of the map diff between two sessions that share a frame and of a
+ * RadiusOutlierRemoval-style noise filter (python/scaloam/nbr.py, which is also the CPU restatement the device equals bit for bit;
+ * DESIGN.md section 8.11).
+ *
+ * Index set I and query set Q: xyzi records; intensity is carried along and never read.  r finite and > 0, r2 = (float)r * (float)r
+ * rounded to f32.  For a query q and an index record p, both finite in x, y, z:
+ *     d2 = ((qx - px)*(qx - px) + (qy - py)*(qy - py)) + (qz - pz)*(qz - pz)      f32, every operation rounded once (no FMA)
+ * p is WITHIN q iff d2 <= r2.  count(q) = the number of index records within q, saturating at 65535; min_d2(q) = the smallest such
+ * d2, or +inf when there is none.  A record that is not finite takes no part as an index record and gets count 0 and +inf as a
+ * query.  In a self query (Q = I) a point counts itself, as PCL's radiusSearch does.  min and a saturating count do not depend on the
+ * order of evaluation: the result is defined bit for bit, pointwise, with no margin condition.
+ *
+ * Device memory comes from the config and does not grow with the map. */
+typedef struct {
+    int device;
+    int max_index_points;     /* 1 .. 2^30 */
+    int max_query_points;     /* 1 .. 2^30; queries of one call (a self query may have max_index_points) */
+} scal_nbr_config;
+typedef struct scal_nbr scal_nbr_t;
+/* SCAL_E_NO_DEVICE without a gfx950 device; SCAL_E_ARG (before any device work) for a NULL pointer or a capacity < 1 */
+int scal_nbr_create(const scal_nbr_config* cfg, scal_nbr_t** ctx);
+void scal_nbr_destroy(scal_nbr_t* ctx);
+/* the index: n xyzi records (host), n = 0 allowed (every later count is 0).  A second call replaces index and radius.
+ * SCAL_E_ARG: a radius that is not finite and > 0 (as a double and as the float it is rounded to), n < 0, a NULL pointer with n > 0.
+ * SCAL_E_CAPACITY: n > max_index_points. */
+int scal_nbr_set_index(scal_nbr_t* ctx, const float* xyzi, int n, double radius);
+/* the same for records in device memory, as scal_mapmerge_device_points returns them (wait for the merge first: scal_mapmerge_size
+ * does).  The records are copied into the index's own order before the call returns. */
+int scal_nbr_set_index_device(scal_nbr_t* ctx, const float* d_xyzi, int n, double radius);
+/* n queries (host) -> count_u16 [n], min_d2 [n] (host; either may be NULL).  SCAL_E_STATE before any set_index; SCAL_E_CAPACITY:
+ * n > max_query_points (nothing runs; callers split the set, the result does not depend on how). */
+int scal_nbr_query(scal_nbr_t* ctx, const float* xyzi, int n, unsigned short* count_u16, float* min_d2);
+/* queries and outputs in device memory; waits for the result */
+int scal_nbr_query_device(scal_nbr_t* ctx, const float* d_xyzi, int n, unsigned short* d_count_u16, float* d_min_d2);
+/* the index records themselves as the queries, outputs (host) in the order the index was given in */
+int scal_nbr_query_self(scal_nbr_t* ctx, unsigned short* count_u16, float* min_d2);
+/* of the last query: (query, record) pairs tested and work items (pieces of up to 64 queries of one cell) */
+int scal_nbr_stats(scal_nbr_t* ctx, long long* pairs, int* work_items);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,355 @@
+// Radius neighbour index (scal_nbr_*, include/scaloam_hip.h has the semantics; python/scaloam/nbr.py is the CPU restatement the device
+// equals bit for bit): per query the number of index records within r (saturating u16) and the smallest f32 d^2 among them.  The
+// primitive behind the session map diff and the radius outlier filter.
+//
+// One context, one stream (lane 0).  set_index:
+//   k_nb_keys -> RadixSort (stable, 48-bit keys) -> k_nb_index (records in cell order with their input position in .w, the cells'
+//   [start, end) ranges behind an open-addressing hash table) - the shape of refine.hip's k_rf_keys / k_rf_index, with the key, the
+//   clamp, the slot function and the table's insert shared with it through cellhash_dev.hpp (which holds the lookup as well).
+// query: the queries are sorted by the same key (k_nb_keys, RadixSort, k_nb_gather; a self query reuses the index's own order), then
+//   k_nb_query: one wave per 64 consecutive sorted queries, a query per lane.  The wave takes the runs of equal cells among its 64
+//   queries one after the other (a run that crosses a multiple of 64 is cut there): such a piece is a work item - up to 64 queries of
+//   ONE cell, so the 27 cell ranges around it are wave-uniform.  Lanes 0 .. 26 look one range up each; the wave then streams the
+//   ranges' records 64 at a time, one 16-byte load per lane, and hands them round by v_readlane_b32 with a uniform lane index: the
+//   record's x, y, z arrive as scalar operands of the subtractions, every lane tests the record against its own query.  Count and
+//   minimum stay in registers and are written once, through the permutation, into the caller's order: no atomics on the outputs.
+//   An LDS stage for the broadcast was not built: it would add a ds_write / s_waitcnt / ds_read round trip per 64 records to save
+//   three VALU issues per record; see DESIGN.md for the instruction count of the inner loop as built.
+//
+// Cell width.  w = the smallest power of two GREATER than r (never below 2^-62; one cell for everything when r r overflows), cell
+// coordinate floor(v * (1 / w)) in f32.  1 / w is a power of two, so the product is exact and so is the floor: the coordinate is
+// floor(v / w) of the real numbers (f32 denormals are on for gfx9; a product that overflows gives +-inf, which the clamp takes; one
+// that is lost below the denormals belongs to a |v| so far below w that no float lies between it and the cell's edge).
+// Claim: a pair that passes d2 <= r2 has |qv - pv| < w on every axis, so its cell coordinates differ by at most 1.  Every term of d2
+// is >= 0 and rounding is monotone, so fl(dv'^2) <= d2 <= r2 for dv' = fl(qv - pv).  r < w are floats, so r <= w (1 - 2^-24) and
+// r2 = fl(r r) <= w^2 (1 - 2^-23); fl(dv'^2) <= that forces dv' < w, i.e. dv' <= w (1 - 2^-24), and the true difference is within
+// half an ulp of dv': |qv - pv| <= w (1 - 2^-24) + w 2^-25 < w.  (With w = r for a power of two r the claim fails: q = 0.5,
+// p = -2^-30, r = 0.5 has fl(q - p) = 0.5 and passes, and the cells are 1 and -1.)  Where the squares fall below the normal range
+// (r2 or dv'^2 < 2^-126) dv' < 2^-63 < w by the lower bound on w.  Clamping the coordinate to the key range is monotone and keeps
+// the difference <= 1.  So the 27 cells around a query's cell hold every record within r: an argument, no slack factor; the cost is
+// a cell up to twice r wide.
+#include "common.hpp"
+#include "cellhash_dev.hpp"
+#include "radix_sort.hpp"
+#include <algorithm>
+#include <cmath>
+
+namespace scal {
+
+// cell coordinates: 17 bits in x and y, 14 in z, clamped beyond (refine.hip's layout)
+constexpr int NB_XB = 17, NB_ZB = 14, NB_KEY_BITS = 2 * NB_XB + NB_ZB;
+constexpr unsigned long long NB_NO_CELL = (1ull << NB_KEY_BITS) - 1;  // records that are not finite: sorted behind every cell, in no cell
+constexpr unsigned NB_INF = 0x7f800000u;
+
+__device__ __forceinline__ bool nb_finite(const float4 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
+__device__ __forceinline__ int nb_coord(float v, float inv, int bits) { return ch_clamp_coord(v * inv, bits); }
+// key of cell (x, y, z), NB_NO_CELL outside the coordinate range (nothing is stored there)
+__device__ __forceinline__ unsigned long long nb_key(int x, int y, int z) { return ch_key<NB_XB, NB_ZB>(x, y, z); }
+
+__global__ void __launch_bounds__(256) k_nb_keys(const float4* __restrict__ pts, int n, float inv, unsigned long long* __restrict__ keys,
+                                                 int* __restrict__ vals) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float4 p = pts[i];
+    keys[i] = nb_finite(p) ? nb_key(nb_coord(p.x, inv, NB_XB), nb_coord(p.y, inv, NB_XB), nb_coord(p.z, inv, NB_ZB)) : NB_NO_CELL;
+    vals[i] = i;
+}
+
+// sorted position i: the record with its input position in .w (the queries of a set, in cell order)
+__global__ void __launch_bounds__(256) k_nb_gather(const int* __restrict__ vals, int n, const float4* __restrict__ pts, float4* __restrict__ sorted) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int idx = vals[i];
+    float4 p = pts[idx];
+    p.w = __int_as_float(idx);
+    sorted[i] = p;
+}
+
+// the same for the index, and the first and the last position of a cell enter the cell's range into the hash table
+__global__ void __launch_bounds__(256) k_nb_index(const unsigned long long* __restrict__ keys, const int* __restrict__ vals, int n,
+                                                  const float4* __restrict__ pts, float4* __restrict__ sorted, unsigned long long* __restrict__ hkeys,
+                                                  int2* __restrict__ hrange, unsigned mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = keys[i];
+    const int idx = vals[i];
+    float4 p = pts[idx];
+    p.w = __int_as_float(idx);
+    sorted[i] = p;
+    if (key == NB_NO_CELL) return;
+    const bool head = i == 0 || keys[i - 1] != key, tail = i == n - 1 || keys[i + 1] != key;
+    if (!head && !tail) return;
+    ch_insert(hkeys, hrange, mask, key, i, head, tail);
+}
+
+__device__ __forceinline__ float nb_lane_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
+
+// qs: nq queries in cell order with their output position in .w; a wave per 64 of them (four waves per block, independent).
+// cnt_out / d2_out may be null.  stats: [0] (query, record) pairs tested, [1] work items.
+__global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs, int nq, float inv, float r2, const unsigned long long* __restrict__ hkeys,
+                                                  const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
+                                                  unsigned short* __restrict__ cnt_out, float* __restrict__ d2_out, unsigned long long* __restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const int i = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + lane;
+    const bool have = i < nq;
+    const float4 q = have ? qs[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool fin = have && nb_finite(q);
+    const int out = __float_as_int(q.w);
+    const int cx = nb_coord(q.x, inv, NB_XB), cy = nb_coord(q.y, inv, NB_XB), cz = nb_coord(q.z, inv, NB_ZB);
+    if (have && !fin) {  // a query that is not finite: count 0, +inf
+        if (cnt_out) cnt_out[out] = 0;
+        if (d2_out) d2_out[out] = __uint_as_float(NB_INF);
+    }
+    unsigned long long waiting = __ballot(fin), pairs = 0;
+    int items = 0;
+    while (waiting) {
+        const int leader = __ffsll(static_cast<long long>(waiting)) - 1;
+        const int lx = __builtin_amdgcn_readlane(cx, leader), ly = __builtin_amdgcn_readlane(cy, leader), lz = __builtin_amdgcn_readlane(cz, leader);
+        const bool mine = fin && cx == lx && cy == ly && cz == lz;
+        const unsigned long long peers = __ballot(mine);  // holds the leader's bit: every round takes lanes out of `waiting`
+        int s0 = 0, e0 = 0;
+        if (lane < 27) {
+            const int az = lane / 9, ay = (lane - 9 * az) / 3, ax = lane - 9 * az - 3 * ay;
+            const unsigned long long key = nb_key(lx + ax - 1, ly + ay - 1, lz + az - 1);
+            int2 r;
+            if (key != NB_NO_CELL && ch_find(hkeys, hrange, mask, key, r)) s0 = r.x, e0 = r.y;
+        }
+        int count = 0, seen = 0;
+        float best = __uint_as_float(NB_INF);
+        for (int c = 0; c < 27; ++c) {
+            const int s = __builtin_amdgcn_readlane(s0, c), e = __builtin_amdgcn_readlane(e0, c);
+            seen += e - s;
+            for (int b = s; b < e; b += 64) {
+                const int m = __builtin_amdgcn_readfirstlane(min(64, e - b));  // keeps the loop counter on the scalar side
+                const float4 p = lane < m ? sorted[b + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+                for (int j = 0; j < m; ++j) {
+                    const float dx = q.x - nb_lane_f(p.x, j), dy = q.y - nb_lane_f(p.y, j), dz = q.z - nb_lane_f(p.z, j);
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (d2 <= r2) {
+                        ++count;
+                        best = d2 < best ? d2 : best;  // no NaN can arrive here: both records are finite
+                    }
+                }
+            }
+        }
+        if (mine) {
+            if (cnt_out) cnt_out[out] = static_cast<unsigned short>(min(count, 65535));
+            if (d2_out) d2_out[out] = best;
+        }
+        pairs += static_cast<unsigned long long>(seen) * __popcll(peers);
+        ++items;
+        waiting &= ~peers;
+    }
+    if (lane == 0 && items) {
+        atomicAdd(stats, pairs);
+        atomicAdd(stats + 1, static_cast<unsigned long long>(items));
+    }
+}
+
+}  // namespace scal
+
+using namespace scal;
+
+struct scal_nbr {
+    scal_nbr_config cfg;
+    LaneStream stream;
+    int cap = 0;  // max(max_index_points, max_query_points): a self query has as many queries as the index has records
+    unsigned hmask = 0;
+    DevBuf<float4> stage, sorted, qsorted;  // stage: host records staged in (index or queries), allocated on first use
+    DevBuf<unsigned long long> keys, hkeys, d_stats;
+    DevBuf<int> vals, d_n;
+    DevBuf<int2> hrange;
+    DevBuf<unsigned short> d_cnt;
+    DevBuf<float> d_d2;
+    RadixSort sorter;
+    int n = -1;  // -1: no index set
+    float inv = 0.f, r2 = 0.f;
+    long long pairs = 0;
+    int work_items = 0;
+};
+
+extern "C" int scal_nbr_create(const scal_nbr_config* cfg, scal_nbr_t** out) {
+    if (!cfg || !out || cfg->max_index_points < 1 || cfg->max_index_points > (1 << 30) || cfg->max_query_points < 1 || cfg->max_query_points > (1 << 30)) {
+        set_error("scal_nbr_create: bad argument");
+        return SCAL_E_ARG;
+    }
+    *out = nullptr;
+    SCAL_TRY(select_device(cfg->device));
+    auto* c = new scal_nbr();
+    c->cfg = *cfg;
+    c->cap = std::max(cfg->max_index_points, cfg->max_query_points);
+    const size_t ni = static_cast<size_t>(cfg->max_index_points), nq = static_cast<size_t>(cfg->max_query_points), nc = static_cast<size_t>(c->cap);
+    size_t slots = 1024;
+    while (slots < 2 * ni) slots <<= 1;
+    c->hmask = static_cast<unsigned>(slots - 1);
+    int rc = SCAL_OK;
+    auto A = [&](int r) { if (rc == SCAL_OK) rc = r; };
+    A(c->stream.acquire(cfg->device, 0));
+    A(c->sorted.alloc(ni)); A(c->qsorted.alloc(nq)); A(c->keys.alloc(nc)); A(c->vals.alloc(nc)); A(c->d_n.alloc(1));
+    A(c->hkeys.alloc(slots)); A(c->hrange.alloc(slots)); A(c->d_stats.alloc(2)); A(c->d_cnt.alloc(nc)); A(c->d_d2.alloc(nc));
+    A(c->sorter.init(c->cap));
+    if (rc != SCAL_OK) {
+        scal_nbr_destroy(c);
+        return rc;
+    }
+    *out = c;
+    return SCAL_OK;
+}
+
+extern "C" void scal_nbr_destroy(scal_nbr_t* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->cfg.device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    delete c;
+}
+
+// keys of the n records at pts, sorted: the pairs are in *sp afterwards
+static int nb_sort(scal_nbr* c, const float4* pts, int n, SortedPairs* sp) {
+    hipStream_t s = c->stream;
+    SCAL_HIP(hipMemcpyAsync(c->d_n.p, &n, sizeof(int), hipMemcpyHostToDevice, s));
+    SCAL_LAUNCH_PROF("k_nb_keys", k_nb_keys, dim3(div_up(n, 256)), dim3(256), 0, s, pts, n, c->inv, c->keys.p, c->vals.p);
+    SCAL_HIP(hipGetLastError());
+    SCAL_TRY(c->sorter.sort(s, c->keys.p, c->vals.p, c->d_n.p, n, NB_KEY_BITS, nullptr, sp));
+    return SCAL_OK;
+}
+
+static int nb_check_index(scal_nbr* c, const char* who, const float* xyzi, int n, double radius) {
+    const float r = static_cast<float>(radius);
+    if (!c || n < 0 || (n > 0 && !xyzi) || !(radius > 0) || !std::isfinite(radius) || !(r > 0.f) || !std::isfinite(r)) {
+        set_error("%s: bad argument (the radius must be finite and > 0 as a float)", who);
+        return SCAL_E_ARG;
+    }
+    if (n > c->cfg.max_index_points) {
+        set_error("%s: %d records, max_index_points is %d", who, n, c->cfg.max_index_points);
+        return SCAL_E_CAPACITY;
+    }
+    return SCAL_OK;
+}
+
+static int nb_build(scal_nbr* c, const float4* pts, int n, double radius) {
+    hipStream_t s = c->stream;
+    c->n = -1, c->pairs = 0, c->work_items = 0;
+    const float r = static_cast<float>(radius);
+    c->r2 = r * r;
+    // 1 / w for w = the smallest power of two > r: r = mant 2^e with mant in [0.5, 1), so w = 2^e
+    int e = 0;
+    (void)std::frexp(r, &e);
+    c->inv = std::isinf(c->r2) ? 0.f : std::ldexp(1.f, -std::max(e, -62));
+    SCAL_HIP(hipMemsetAsync(c->hkeys.p, 0xff, sizeof(unsigned long long) * (static_cast<size_t>(c->hmask) + 1), s));
+    if (n > 0) {
+        SortedPairs sp;
+        SCAL_TRY(nb_sort(c, pts, n, &sp));
+        SCAL_LAUNCH_PROF("k_nb_index", k_nb_index, dim3(div_up(n, 256)), dim3(256), 0, s, sp.keys[sp.fixed_sel], sp.vals[sp.fixed_sel], n, pts,
+                         c->sorted.p, c->hkeys.p, c->hrange.p, c->hmask);
+        SCAL_HIP(hipGetLastError());
+    }
+    SCAL_HIP(hipStreamSynchronize(s));  // the caller's records have been read
+    c->n = n;
+    return SCAL_OK;
+}
+
+extern "C" int scal_nbr_set_index(scal_nbr_t* c, const float* xyzi, int n, double radius) {
+    SCAL_TRY(nb_check_index(c, "scal_nbr_set_index", xyzi, n, radius));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    c->n = -1;
+    if (!c->stage.p) SCAL_TRY(c->stage.alloc(static_cast<size_t>(c->cap)));  // a context fed from the device never needs it
+    if (n > 0) SCAL_HIP(hipMemcpyAsync(c->stage.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, c->stream));
+    return nb_build(c, c->stage.p, n, radius);
+}
+
+extern "C" int scal_nbr_set_index_device(scal_nbr_t* c, const float* d_xyzi, int n, double radius) {
+    SCAL_TRY(nb_check_index(c, "scal_nbr_set_index_device", d_xyzi, n, radius));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    return nb_build(c, reinterpret_cast<const float4*>(d_xyzi), n, radius);
+}
+
+// the nq queries at qs (cell order, output position in .w) -> d_cnt / d_d2 (either may be null); waits, reads the counters
+static int nb_run(scal_nbr* c, const float4* qs, int nq, unsigned short* d_cnt, float* d_d2) {
+    hipStream_t s = c->stream;
+    c->pairs = 0, c->work_items = 0;
+    if (nq == 0) return SCAL_OK;
+    SCAL_HIP(hipMemsetAsync(c->d_stats.p, 0, 2 * sizeof(unsigned long long), s));
+    SCAL_LAUNCH_PROF("k_nb_query", k_nb_query, dim3(div_up(nq, 256)), dim3(256), 0, s, qs, nq, c->inv, c->r2, c->hkeys.p, c->hrange.p, c->hmask,
+                     c->sorted.p, d_cnt, d_d2, c->d_stats.p);
+    SCAL_HIP(hipGetLastError());
+    unsigned long long st[2] = {0, 0};
+    SCAL_HIP(hipMemcpyAsync(st, c->d_stats.p, sizeof st, hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipStreamSynchronize(s));
+    c->pairs = static_cast<long long>(st[0]), c->work_items = static_cast<int>(std::min<unsigned long long>(st[1], 0x7fffffffull));
+    return SCAL_OK;
+}
+
+static int nb_check_query(scal_nbr* c, const char* who, const float* xyzi, int n) {
+    if (!c || n < 0 || (n > 0 && !xyzi)) {
+        set_error("%s: bad argument", who);
+        return SCAL_E_ARG;
+    }
+    if (c->n < 0) {
+        set_error("%s: no index set", who);
+        return SCAL_E_STATE;
+    }
+    if (n > c->cfg.max_query_points) {
+        set_error("%s: %d queries, max_query_points is %d", who, n, c->cfg.max_query_points);
+        return SCAL_E_CAPACITY;
+    }
+    return SCAL_OK;
+}
+
+// sorts the n queries at pts into qsorted
+static int nb_sort_queries(scal_nbr* c, const float4* pts, int n) {
+    if (n == 0) return SCAL_OK;
+    SortedPairs sp;
+    SCAL_TRY(nb_sort(c, pts, n, &sp));
+    SCAL_LAUNCH_PROF("k_nb_gather", k_nb_gather, dim3(div_up(n, 256)), dim3(256), 0, c->stream, sp.vals[sp.fixed_sel], n, pts, c->qsorted.p);
+    SCAL_HIP(hipGetLastError());
+    return SCAL_OK;
+}
+
+static int nb_download(scal_nbr* c, int n, unsigned short* count_u16, float* min_d2) {
+    if (n == 0) return SCAL_OK;
+    hipStream_t s = c->stream;
+    if (count_u16) SCAL_HIP(hipMemcpyAsync(count_u16, c->d_cnt.p, sizeof(unsigned short) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+    if (min_d2) SCAL_HIP(hipMemcpyAsync(min_d2, c->d_d2.p, sizeof(float) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipStreamSynchronize(s));
+    return SCAL_OK;
+}
+
+extern "C" int scal_nbr_query(scal_nbr_t* c, const float* xyzi, int n, unsigned short* count_u16, float* min_d2) {
+    SCAL_TRY(nb_check_query(c, "scal_nbr_query", xyzi, n));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    if (!c->stage.p) SCAL_TRY(c->stage.alloc(static_cast<size_t>(c->cap)));
+    if (n > 0) SCAL_HIP(hipMemcpyAsync(c->stage.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, c->stream));
+    SCAL_TRY(nb_sort_queries(c, c->stage.p, n));
+    SCAL_TRY(nb_run(c, c->qsorted.p, n, count_u16 ? c->d_cnt.p : nullptr, min_d2 ? c->d_d2.p : nullptr));
+    return nb_download(c, n, count_u16, min_d2);
+}
+
+extern "C" int scal_nbr_query_device(scal_nbr_t* c, const float* d_xyzi, int n, unsigned short* d_count_u16, float* d_min_d2) {
+    SCAL_TRY(nb_check_query(c, "scal_nbr_query_device", d_xyzi, n));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(nb_sort_queries(c, reinterpret_cast<const float4*>(d_xyzi), n));
+    return nb_run(c, c->qsorted.p, n, d_count_u16, d_min_d2);
+}
+
+extern "C" int scal_nbr_query_self(scal_nbr_t* c, unsigned short* count_u16, float* min_d2) {
+    if (!c) {
+        set_error("scal_nbr_query_self: bad argument");
+        return SCAL_E_ARG;
+    }
+    if (c->n < 0) {
+        set_error("scal_nbr_query_self: no index set");
+        return SCAL_E_STATE;
+    }
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(nb_run(c, c->sorted.p, c->n, count_u16 ? c->d_cnt.p : nullptr, min_d2 ? c->d_d2.p : nullptr));
+    return nb_download(c, c->n, count_u16, min_d2);
+}
+
+extern "C" int scal_nbr_stats(scal_nbr_t* c, long long* pairs, int* work_items) {
+    if (!c || !pairs || !work_items) {
+        set_error("scal_nbr_stats: bad argument");
+        return SCAL_E_ARG;
+    }
+    *pairs = c->pairs, *work_items = c->work_items;
+    return SCAL_OK;
+}

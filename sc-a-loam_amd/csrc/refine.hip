@@ -21,6 +21,7 @@
 //   host          icp_host_step (icp_host.hpp, shared with icp.hip) per frame; K 3x4 increments and the active mask go back in one copy
 // Frames that have finished cost an early return per workgroup.
 #include "common.hpp"
+#include "cellhash_dev.hpp"
 #include "device_utils.hpp"
 #include "icp_host.hpp"
 #include "mapmerge_dev.hpp"
@@ -42,7 +43,6 @@ constexpr int RF_DENSE_WG = 2048;  // workgroups of the dense sweep
 // search has not examined is still at least k cells away from the query along some axis and the stop rule holds out there too.
 constexpr int RF_XB = 17, RF_ZB = 14, RF_KEY_BITS = 2 * RF_XB + RF_ZB;
 constexpr unsigned long long RF_NO_CELL = (1ull << RF_KEY_BITS) - 1;  // non-finite points: sorted behind every cell, in no cell
-constexpr unsigned long long RF_EMPTY = ~0ull;
 
 struct RfBlock {
     int first, end, frame;  // 256 source points of one frame: [first, min(first + 256, end)) of G
@@ -62,22 +62,9 @@ __global__ void __launch_bounds__(256) k_rf_write(const float4* __restrict__ in,
     mm_write_body<true>(in, blocks, poses, thres, blkoff, 0, cap, out, frame_of);
 }
 
-__device__ __forceinline__ int rf_coord(float v, int bits) {  // NaN -> the lowest cell
-    const float lim = static_cast<float>(1 << (bits - 1));
-    return static_cast<int>(fminf(fmaxf(floorf(v), -lim), lim - 2.f));
-}
+__device__ __forceinline__ int rf_coord(float v, int bits) { return ch_clamp_coord(v, bits); }  // NaN -> the lowest cell
 // key of cell (x, y, z), RF_NO_CELL outside the coordinate range (nothing is stored there)
-__device__ __forceinline__ unsigned long long rf_key(int x, int y, int z) {
-    const int bx = x + (1 << (RF_XB - 1)), by = y + (1 << (RF_XB - 1)), bz = z + (1 << (RF_ZB - 1));
-    if (static_cast<unsigned>(bx) >= (1u << RF_XB) - 1 || static_cast<unsigned>(by) >= (1u << RF_XB) - 1 || static_cast<unsigned>(bz) >= (1u << RF_ZB) - 1)
-        return RF_NO_CELL;
-    return (static_cast<unsigned long long>(bz) << (2 * RF_XB)) | (static_cast<unsigned long long>(by) << RF_XB) | static_cast<unsigned long long>(bx);
-}
-__device__ __forceinline__ unsigned rf_slot(unsigned long long key, unsigned mask) {
-    unsigned long long h = key * 0x9E3779B97F4A7C15ull;
-    h ^= h >> 29;
-    return static_cast<unsigned>(h) & mask;
-}
+__device__ __forceinline__ unsigned long long rf_key(int x, int y, int z) { return ch_key<RF_XB, RF_ZB>(x, y, z); }
 
 __global__ void __launch_bounds__(256) k_rf_keys(const float4* __restrict__ g, int n, unsigned long long* __restrict__ keys, int* __restrict__ vals) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -104,14 +91,7 @@ __global__ void __launch_bounds__(256) k_rf_index(const unsigned long long* __re
     if (key == RF_NO_CELL) return;
     const bool head = i == 0 || keys[i - 1] != key, tail = i == n - 1 || keys[i + 1] != key;
     if (!head && !tail) return;
-    unsigned slot = rf_slot(key, mask);
-    for (;;) {  // the table has at least twice as many slots as there are points
-        const unsigned long long prev = atomicCAS(&hkeys[slot], RF_EMPTY, key);
-        if (prev == RF_EMPTY || prev == key) break;
-        slot = (slot + 1) & mask;
-    }
-    if (head) hrange[slot].x = i;
-    if (tail) hrange[slot].y = i + 1;
+    ch_insert(hkeys, hrange, mask, key, i, head, tail);
 }
 
 __global__ void __launch_bounds__(256) k_rf_apply(float4* __restrict__ cur, const RfBlock* __restrict__ blocks, const RfCtrl* __restrict__ ctrl) {
@@ -172,7 +152,7 @@ __global__ void __launch_bounds__(256) k_rf_grid_nn(const float4* __restrict__ c
                 const bool fresh = k == 1 || max(max(abs(ax), abs(ay)), abs(az)) == k;  // inner cells were examined in an earlier ring
                 const unsigned long long key = fresh ? rf_key(cx + ax, cy + ay, cz + az) : RF_NO_CELL;
                 if (key != RF_NO_CELL) {
-                    unsigned slot = rf_slot(key, mask);
+                    unsigned slot = ch_slot(key, mask);
                     for (;;) {
                         const unsigned long long hk = hkeys[slot];
                         if (hk == key) {
@@ -180,7 +160,7 @@ __global__ void __launch_bounds__(256) k_rf_grid_nn(const float4* __restrict__ c
                             s0 = r.x, cnt = r.y - r.x;
                             break;
                         }
-                        if (hk == RF_EMPTY) break;
+                        if (hk == CH_EMPTY) break;
                         slot = (slot + 1) & mask;
                     }
                 }

@@ -14,6 +14,8 @@ int main(void) {
     scal_refine_t* rf = NULL;
     scal_reloc_config rl_cfg;
     scal_reloc_t* rl = NULL;
+    scal_nbr_config nb_cfg;
+    scal_nbr_t* nb = NULL;
     int rc, n = scal_device_count();
     memset(&fc, 0, sizeof fc);
     fc.lidar_type = SCAL_HDL64, fc.n_scans = 64, fc.minimum_range = 5.0, fc.max_points = 1000, fc.check_finite = 1;
@@ -63,6 +65,19 @@ int main(void) {
         }
         scal_reloc_destroy(rl);
     }
+    memset(&nb_cfg, 0, sizeof nb_cfg);
+    nb_cfg.max_index_points = 1000;
+    if (scal_nbr_create(&nb_cfg, &nb) != SCAL_E_ARG) {
+        printf("scal_nbr_create accepted max_query_points = 0\n");
+        return 1;
+    }
+    nb_cfg.max_query_points = 1000;
+    rc = scal_nbr_create(&nb_cfg, &nb);
+    if (n < 1 && rc != SCAL_E_NO_DEVICE) {
+        printf("scal_nbr_create: expected SCAL_E_NO_DEVICE without a GPU, got %d (%s)\n", rc, scal_last_error());
+        return 1;
+    }
+    if (rc == SCAL_OK) scal_nbr_destroy(nb);
     printf("abi ok %s devices=%d\n", scal_version(), n);
     return 0;
 }

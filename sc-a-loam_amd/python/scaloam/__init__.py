@@ -109,6 +109,10 @@ class RemovertStats(C.Structure):
                 ("pairs_bruteforce", C.c_longlong)]
 
 
+class NbrConfig(C.Structure):
+    _fields_ = [("device", C.c_int), ("max_index_points", C.c_int), ("max_query_points", C.c_int)]
+
+
 class MapMergeConfig(C.Structure):
     _fields_ = [("max_points", C.c_longlong), ("max_frame_points", C.c_int), ("device", C.c_int)]
 
@@ -191,6 +195,7 @@ EXPORTED_SYMBOLS = [
     "scal_sc_detect_between", "scal_sc_detect_between_device", "scal_sc_cross_matrix", "scal_sc_cross_search", "scal_icp_align_guess", "scal_icp_align_guess_device",
     "scal_reloc_create", "scal_reloc_destroy", "scal_reloc_size", "scal_reloc_add_keyframe", "scal_reloc_query", "scal_reloc_query_batch", "scal_reloc_sc",
     "scal_removert_create", "scal_removert_destroy", "scal_removert_set_map", "scal_removert_set_map_device", "scal_removert_run", "scal_removert_compact", "scal_removert_scan_image",
+    "scal_nbr_create", "scal_nbr_destroy", "scal_nbr_set_index", "scal_nbr_set_index_device", "scal_nbr_query", "scal_nbr_query_device", "scal_nbr_query_self", "scal_nbr_stats",
 ]
 
 _lib = None
@@ -378,6 +383,17 @@ def lib():
                                         C.POINTER(C.c_ushort), C.POINTER(RemovertStats)]
         L.scal_removert_compact.argtypes = [vp, C.c_int, _f32p, C.c_int, _i32p]
         L.scal_removert_scan_image.argtypes = [vp, C.c_int, C.c_int, _f32p, C.c_int, C.c_int]
+    if hasattr(L, "scal_nbr_create"):  # absent from older builds compared through SCALOAM_LIB
+        _u16p = C.POINTER(C.c_ushort)
+        L.scal_nbr_create.argtypes = [C.POINTER(NbrConfig), C.POINTER(vp)]
+        L.scal_nbr_destroy.argtypes = [vp]
+        L.scal_nbr_destroy.restype = None
+        L.scal_nbr_set_index.argtypes = [vp, _f32p, C.c_int, C.c_double]
+        L.scal_nbr_set_index_device.argtypes = [vp, vp, C.c_int, C.c_double]
+        L.scal_nbr_query.argtypes = [vp, _f32p, C.c_int, _u16p, _f32p]
+        L.scal_nbr_query_device.argtypes = [vp, vp, C.c_int, vp, vp]
+        L.scal_nbr_query_self.argtypes = [vp, _u16p, _f32p]
+        L.scal_nbr_stats.argtypes = [vp, C.POINTER(C.c_longlong), _i32p]
     L.scal_keyframe_gate_init.argtypes = [C.POINTER(KeyframeGateState), C.c_double, C.c_double]
     L.scal_keyframe_gate.argtypes = [C.POINTER(KeyframeGateState), _f64p, _f64p, _i32p]
     for fn in ("scal_pipeline_sc_of", "scal_pipeline_map_of"):
@@ -1155,6 +1171,72 @@ class Removert:
         out = np.zeros((max(self.n, 1), 4), np.float32)
         _check(lib().scal_removert_compact(self.h, int(which), _p(out, _f32p), self.n, C.byref(m)))
         return out[:m.value].copy()
+
+
+class RadiusIndex:
+    """scal_nbr: per query the number of index records within r (uint16, saturating) and the smallest f32 d^2 among them (+inf when
+    none) - include/scaloam_hip.h has the definition, scaloam/nbr.py the CPU restatement the device equals bit for bit.  A query
+    set larger than max_query_points goes through in chunks; the result does not depend on the chunking."""
+
+    def __init__(self, max_index_points, max_query_points, device=0):
+        self.h = C.c_void_p()
+        self.max_query_points = int(max_query_points)
+        cfg = NbrConfig(device, int(max_index_points), int(max_query_points))
+        _check(lib().scal_nbr_create(C.byref(cfg), C.byref(self.h)))
+        self.n = 0
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            _lib.scal_nbr_destroy(self.h)
+        self.h = None
+
+    __del__ = close
+
+    def set_index(self, xyzi, r):
+        a = _f32(xyzi).reshape(-1, 4)
+        _check(lib().scal_nbr_set_index(self.h, _p(a, _f32p), a.shape[0], float(r)))
+        self.n = a.shape[0]
+
+    def set_index_device(self, mapmerge, r):
+        """the points a MapMerge holds in device memory; size() waits for the merge"""
+        n = mapmerge.size()
+        _check(lib().scal_nbr_set_index_device(self.h, mapmerge.device_points(), n, float(r)))
+        self.n = n
+
+    def query(self, xyzi):
+        """(count uint16 [n], min_d2 float32 [n]); stats() afterwards covers all chunks"""
+        q = _f32(xyzi).reshape(-1, 4)
+        n = q.shape[0]
+        count, d2 = np.zeros(max(n, 1), np.uint16), np.zeros(max(n, 1), np.float32)
+        pairs, items = 0, 0
+        for i in range(0, max(n, 1), self.max_query_points):
+            m = min(self.max_query_points, n - i)
+            _check(lib().scal_nbr_query(self.h, _p(q[i:i + m], _f32p), m, _p(count[i:], C.POINTER(C.c_ushort)), _p(d2[i:], _f32p)))
+            st = self._stats()
+            pairs, items = pairs + st[0], items + st[1]
+        self._sum = (pairs, items)
+        return count[:n], d2[:n]
+
+    def query_self(self):
+        count, d2 = np.zeros(max(self.n, 1), np.uint16), np.zeros(max(self.n, 1), np.float32)
+        _check(lib().scal_nbr_query_self(self.h, _p(count, C.POINTER(C.c_ushort)), _p(d2, _f32p)))
+        self._sum = self._stats()
+        return count[:self.n], d2[:self.n]
+
+    def query_device(self, d_xyzi_ptr, n, d_count_ptr, d_min_d2_ptr):
+        """queries and outputs in device memory (either output may be None); at most max_query_points"""
+        _check(lib().scal_nbr_query_device(self.h, d_xyzi_ptr, int(n), d_count_ptr, d_min_d2_ptr))
+        self._sum = self._stats()
+
+    def _stats(self):
+        pairs, items = C.c_longlong(0), C.c_int(0)
+        _check(lib().scal_nbr_stats(self.h, C.byref(pairs), C.byref(items)))
+        return pairs.value, items.value
+
+    def stats(self):
+        """of the last query: dict(pairs_tested, work_items)"""
+        pairs, items = getattr(self, "_sum", (0, 0))
+        return dict(pairs_tested=pairs, work_items=items)
 
 
 class MapMerge:

@@ -1,0 +1,169 @@
+"""CPU restatement of scal_nbr_* (include/scaloam_hip.h) and the two uses built on it: the map diff between two sessions that share a
+frame, and a radius outlier filter.  radius_counts is the specification csrc/nbr.hip is held to bit for bit, in the role removert.py
+has for scal_removert; numpy and scipy only, every f32 expression elementwise in the order the header states.  DESIGN.md section
+8.11 has the reasoning.  The functions that take device=True run the same steps on the GPU through scaloam.RadiusIndex and
+scaloam.Removert (imported only then); nothing else here touches the device.
+
+PCL is not on the machines this was written on, so radius_outlier_mask restates PCL 1.8's RadiusOutlierRemoval rule from its
+source text - parity unpinned, as DESIGN.md section 2 says of the other PCL restatements."""
+import numpy as np
+
+from . import removert as _rv
+
+# Twice the project's 0.4 m map leaf.  Two maps filtered on the same global voxel lattice can put their centroids of one surface up
+# to a voxel diagonal apart (0.4 sqrt(3) = 0.69 m): a radius below that would call a surface both sessions saw "changed".  A
+# setting, not a measured value.
+DEFAULT_RADIUS = 0.8
+BRUTE_LIMIT = 4000        # index and query sets up to this size take the dense path
+TREE_SLACK = 1e-3         # the tree's f64 radius is wider by this factor; it only widens the candidate list
+COMMON, UNOBSERVED, CHANGED = 0, 1, 2
+
+
+def _xyzi(a):
+    return np.ascontiguousarray(a, np.float32).reshape(-1, 4)
+
+
+def _radius(r):
+    with np.errstate(over="ignore", under="ignore"):
+        r32 = np.float32(r)
+    if not (np.isfinite(r) and r > 0 and np.isfinite(r32) and r32 > 0):
+        raise ValueError("the radius must be finite and > 0 (as a float32 too)")
+    with np.errstate(over="ignore", under="ignore"):
+        return r32, np.float32(r32 * r32)
+
+
+def _d2(q, p):
+    """the header's f32 d2 of q [.., 3] and p [.., 3], every operation rounded once"""
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        dx, dy, dz = q[..., 0] - p[..., 0], q[..., 1] - p[..., 1], q[..., 2] - p[..., 2]
+        return ((dx * dx + dy * dy) + dz * dz).astype(np.float32)
+
+
+def _brute(I, Q, r2, count, best):
+    """every finite query against every finite index record; Q in slabs that keep the dense block small"""
+    if I.shape[0] == 0:
+        return
+    step = max(1, (1 << 22) // I.shape[0])
+    for a in range(0, Q.shape[0], step):
+        d2 = _d2(Q[a:a + step, None, :], I[None, :, :])
+        within = d2 <= r2
+        count[a:a + step] = within.sum(1)
+        best[a:a + step] = np.where(within, d2, np.float32(np.inf)).min(1)
+
+
+def _tree(I, Q, r32, r2, count, best, progress=None):
+    from scipy.spatial import cKDTree
+    if I.shape[0] == 0:
+        return
+    tree = cKDTree(I.astype(np.float64))
+    step = 1 << 16
+    for a in range(0, Q.shape[0], step):
+        if progress:
+            progress(a, Q.shape[0])
+        q = Q[a:a + step]
+        lists = tree.query_ball_point(q.astype(np.float64), float(r32) * (1.0 + TREE_SLACK), return_sorted=False)
+        lens = np.fromiter((len(l) for l in lists), np.int64, len(lists))
+        if lens.sum() == 0:
+            continue
+        pi = np.concatenate([np.asarray(l, np.int64) for l in lists if len(l)])
+        qi = np.repeat(np.arange(q.shape[0]), lens)
+        d2 = _d2(q[qi], I[pi])
+        within = d2 <= r2
+        count[a:a + step] = np.bincount(qi[within], minlength=q.shape[0])
+        b = np.full(q.shape[0], np.inf, np.float32)
+        np.minimum.at(b, qi[within], d2[within])
+        best[a:a + step] = b
+
+
+def radius_counts(index_xyzi, query_xyzi, r, path=None, progress=None):
+    """(count uint16 [nq] saturating at 65535, min_d2 float32 [nq], +inf where count is 0).  path: "brute", "tree" or None = by size.
+    progress(done, total) is called by the tree path before every slab of 65536 queries (long runs of the benchmark)."""
+    I, Q = _xyzi(index_xyzi), _xyzi(query_xyzi)
+    r32, r2 = _radius(r)
+    fi, fq = np.isfinite(I[:, :3]).all(1), np.isfinite(Q[:, :3]).all(1)
+    Ifin, Qfin = I[fi, :3], Q[fq, :3]
+    cnt, best = np.zeros(Qfin.shape[0], np.int64), np.full(Qfin.shape[0], np.inf, np.float32)
+    if path is None:
+        path = "brute" if max(I.shape[0], Q.shape[0]) <= BRUTE_LIMIT else "tree"
+    if path == "brute":
+        _brute(Ifin, Qfin, r2, cnt, best)
+    elif path == "tree":
+        _tree(Ifin, Qfin, r32, r2, cnt, best, progress)
+    else:
+        raise ValueError("path is 'brute', 'tree' or None")
+    count, min_d2 = np.zeros(Q.shape[0], np.uint16), np.full(Q.shape[0], np.inf, np.float32)
+    count[fq], min_d2[fq] = np.minimum(cnt, 65535).astype(np.uint16), best
+    return count, min_d2
+
+
+def _device_counts(index_xyzi, query_xyzi, r, self_query=False):
+    from . import RadiusIndex
+    I = _xyzi(index_xyzi)
+    Q = I if self_query else _xyzi(query_xyzi)
+    idx = RadiusIndex(max(I.shape[0], 1), max(min(Q.shape[0], 1 << 24), 1))
+    try:
+        idx.set_index(I, r)
+        return idx.query_self() if self_query else idx.query(Q)
+    finally:
+        idx.close()
+
+
+def radius_outlier_mask(xyzi, r, min_neighbors, device=False):
+    """bool [n]: the records to keep.  PCL 1.8 RadiusOutlierRemoval: radiusSearch returns the point itself among its neighbours and
+    a point stays iff that number is > min_neighbors (setMinNeighborsInRadius; filters/impl/radius_outlier_removal.hpp compares
+    `k <= min_pts_radius_` to drop).  Records that are not finite are dropped.  Counts saturate at 65535: min_neighbors above
+    65534 keeps nothing."""
+    P = _xyzi(xyzi)
+    _radius(r)
+    if int(min_neighbors) < 0:
+        raise ValueError("min_neighbors must be >= 0")
+    count, _ = _device_counts(P, None, r, self_query=True) if device else radius_counts(P, P, r)
+    return (count.astype(np.int64) > int(min_neighbors)) & np.isfinite(P[:, :3]).all(1)
+
+
+def map_diff(map_x, map_y, scans_y, poses12_y, r=DEFAULT_RADIUS, device=False, **removert_settings):
+    """What is in map X and not in map Y, for two maps in one frame, and whether session Y saw through that place.
+    scans_y, poses12_y: Y's keyframes (sensor frame, sensor to world), as scaloam.removert.remove_dynamic_points takes them, and
+    removert_settings its keyword arguments (remove_res, revert_res, fov_up_deg, fov_down_deg, min_range, max_range, diff_thres,
+    min_hits).  Returns (labels uint8 [N_x], stats): COMMON 0 - a Y point lies within r; UNOBSERVED 1 - none does and no ray of Y
+    went through the point; CHANGED 2 - none does and remove_dynamic_points, run on these points alone against Y's keyframes, flags
+    it.  From the old map towards the new session 2 reads "disappeared"; from the new map towards the old session it reads
+    "appeared" and 1 "newly explored".  stats: common, unobserved, changed, candidates, removert (its stats) and margin - the
+    restatement's Removert margin (removert.View.pixels) on the candidates, None on the device path, inf without candidates.
+    On the device the candidates go through the host between scaloam.RadiusIndex and scaloam.Removert: they are a small share of the map."""
+    X, Y = _xyzi(map_x), _xyzi(map_y)
+    P = np.asarray(poses12_y, np.float64).reshape(-1, 12)
+    if P.shape[0] != len(scans_y):
+        raise ValueError("one pose12 row per scan is needed")
+    count, _ = _device_counts(Y, X, r) if device else radius_counts(Y, X, r)
+    labels = np.zeros(X.shape[0], np.uint8)
+    cand = np.flatnonzero(count == 0)
+    margin, rstats = (None if device else np.inf), None
+    if cand.size:
+        if device:
+            from . import Removert
+            kw = dict(removert_settings)
+            rm_res, rv_res = kw.pop("remove_res", _rv.DEFAULT_REMOVE_RES), kw.pop("revert_res", _rv.DEFAULT_REVERT_RES)
+            rm = Removert(max_points=cand.size, max_keyframes=max(len(scans_y), 1), max_scan_points=max(sum(len(s) for s in scans_y), 1),
+                          max_resolutions=max(len(rm_res) + len(rv_res), 1), **kw)
+            try:
+                mask, rstats = rm.remove(X[cand], scans_y, P, rm_res, rv_res)
+            finally:
+                rm.close()
+        else:
+            res = _rv.remove_dynamic_points(X[cand], scans_y, P, keep_images=False, **removert_settings)
+            mask, rstats, margin = res.mask, res.stats, res.margin
+        labels[cand] = UNOBSERVED + mask.astype(np.uint8)
+    n2 = int((labels == CHANGED).sum())
+    stats = dict(common=int(X.shape[0] - cand.size), unobserved=int(cand.size - n2), changed=n2, candidates=int(cand.size), removert=rstats,
+                 margin=margin)
+    return labels, stats
+
+
+def update_map(map_old, labels_old, map_new, labels_new):
+    """the old points that did not disappear, in order, followed by the new points the old map does not already hold, in order"""
+    A, B = _xyzi(map_old), _xyzi(map_new)
+    la, lb = np.asarray(labels_old).reshape(-1), np.asarray(labels_new).reshape(-1)
+    if la.shape[0] != A.shape[0] or lb.shape[0] != B.shape[0]:
+        raise ValueError("one label per point is needed")
+    return np.concatenate([A[la != CHANGED], B[lb != COMMON]], 0)

@@ -5,7 +5,9 @@ a binary PCD.  `--check` also runs the CPU oracle and compares bit for bit.  `--
 scal_refine_* (every keyframe thinned at --refine-leaf and aligned against all the others, keyframe 0 held), writes them to
 refined_poses.txt beside the session's optimized_poses.txt and merges with them.  `--remove-dynamic` runs scal_removert_* on the merged map
 where it lies in device memory, with the poses the merge used (the refined ones after --refine), reports the counts and writes the
-static points beside the map as *_static.pcd - after VoxelGrid(--leaf) if a leaf is given."""
+static points beside the map as *_static.pcd - after VoxelGrid(--leaf) if a leaf is given.  `--radius-filter R,MIN` drops the isolated
+returns before either map is written: a point stays iff more than MIN points of the merged map, itself included, lie within R
+(scal_nbr_*, the map indexed where it lies in device memory; scaloam.nbr.radius_outlier_mask is the rule)."""
 import argparse
 import glob
 import os
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--remove-res", type=float, nargs="+", default=[2.5, 2.0, 1.5], help="remove resolutions, degrees per pixel")
     ap.add_argument("--revert-res", type=float, nargs="*", default=[5.0], help="revert resolutions, degrees per pixel (may be empty)")
     ap.add_argument("--leaf", type=float, default=0.0, help="VoxelGrid leaf for the static map (0 = none)")
+    ap.add_argument("--radius-filter", default=None, metavar="R,MIN", help="keep a point iff more than MIN map points lie within R metres of it")
     a = ap.parse_args()
     import scaloam as S
     from scaloam import formats as F
@@ -60,8 +63,17 @@ def main():
         import oracle_py as O
         ref = O.mapmerge(frames, poses, a.near)
         print("bit-exact vs oracle:", bool(ref.shape == out.shape and np.array_equal(ref.view(np.uint32), out.view(np.uint32))))
+    keep = None
+    if a.radius_filter:
+        r, min_nb = a.radius_filter.split(",")
+        idx = S.RadiusIndex(out.shape[0] + 1, 1)
+        idx.set_index_device(mm, float(r))
+        count, _ = idx.query_self()
+        idx.close()
+        keep = (count.astype(np.int64) > int(min_nb)) & np.isfinite(out[:, :3]).all(1)
+        print(f"radius-filter: {int(keep.sum())} of {out.shape[0]} points have more than {int(min_nb)} points within {float(r)} m")
     path = a.out or os.path.join(a.data_dir, f"map_{lo}_to_{hi}_with_intensity.pcd")
-    F.write_pcd_binary(path, out)
+    F.write_pcd_binary(path, out if keep is None else out[keep])
     print("written", path)
     if a.remove_dynamic:
         n_res = len(a.remove_res) + len(a.revert_res)
@@ -70,7 +82,7 @@ def main():
         mask, st = rm.remove_device(mm, frames, poses, a.remove_res, a.revert_res)
         print(f"remove-dynamic: {st['dynamic']} of {st['points']} points dynamic; {st['pairs_tested']} of {st['pairs_bruteforce']} "
               f"(point, keyframe) pairs tested")
-        static = rm.compact(0)
+        static = rm.compact(0) if keep is None else out[keep & (mask == 0)]
         rm.close()
         if a.leaf > 0 and static.shape[0]:
             vg = S.VoxelGrid(max_points=static.shape[0])
