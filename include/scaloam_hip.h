@@ -908,7 +908,21 @@ int scal_removert_scan_image(scal_removert_t* ctx, int k, int res_index, float* 
  * query.  In a self query (Q = I) a point counts itself, as PCL's radiusSearch does.  min and a saturating count do not depend on the
  * order of evaluation: the result is defined bit for bit, pointwise, with no margin condition.
  *
- * Device memory comes from the config and does not grow with the map. */
+ * k nearest neighbours.  Call p a CANDIDATE of q iff both are finite and d2 <= r2, d2 and r2 as above.  The
+ * candidates of q are ordered by the pair (d2, input position of p in I), ascending: a total order, so duplicates and equidistant
+ * records have a defined place.  knn(q, k), 1 <= k <= SCAL_NBR_MAX_K, is the first k candidates: one row of idx (int32 input
+ * positions) and one row of d2 (float32) per query.  A row with fewer than k candidates is padded with -1 in idx and +inf in d2; a
+ * query that is not finite gets a fully padded row.  A self query returns the point itself first, or an exact duplicate of it with a
+ * lower position (PCL's nearestKSearch behaviour).  The result is defined bit for bit, with no margin condition.
+ * A full row is the k nearest of ALL of I: every record that is not a candidate has d2 > r2 >= the row's last d2, strictly, so no tie
+ * crosses the bound.  Unbounded k-NN is therefore exact by asking the short rows again at twice the radius (scaloam.nbr.knn); the
+ * device primitive is the bounded one and uses the index as it is.
+ *
+ * Device memory comes from the config and does not grow with the map, with one exception: the k-NN rows of scal_nbr_knn and
+ * scal_nbr_knn_self are staged in 8 bytes x k x the queries of the call (4 for an output that is NULL), allocated at the first such
+ * call and grown to the largest so far - 1.2 GB for a self query of 7.1 M points at k = 21.  A context that never asks for
+ * neighbours pays nothing, and scal_nbr_knn_device writes to the caller's buffers and stages nothing. */
+#define SCAL_NBR_MAX_K 64
 typedef struct {
     int device;
     int max_index_points;     /* 1 .. 2^30 */
@@ -932,7 +946,15 @@ int scal_nbr_query(scal_nbr_t* ctx, const float* xyzi, int n, unsigned short* co
 int scal_nbr_query_device(scal_nbr_t* ctx, const float* d_xyzi, int n, unsigned short* d_count_u16, float* d_min_d2);
 /* the index records themselves as the queries, outputs (host) in the order the index was given in */
 int scal_nbr_query_self(scal_nbr_t* ctx, unsigned short* count_u16, float* min_d2);
-/* of the last query: (query, record) pairs tested and work items (pieces of up to 64 queries of one cell) */
+/* n queries (host), 1 <= k <= SCAL_NBR_MAX_K -> idx [n][k], d2 [n][k] (host; either may be NULL), rows as defined above.
+ * SCAL_E_ARG (before any device work): a NULL context, n < 0, a NULL query pointer with n > 0, k out of range.  SCAL_E_STATE: no index
+ * set.  SCAL_E_CAPACITY: n > max_query_points.  SCAL_E_HIP: the staging could not be allocated; the context stays usable. */
+int scal_nbr_knn(scal_nbr_t* ctx, const float* xyzi, int n, int k, int* idx, float* d2);
+/* queries and outputs in device memory; waits for the result */
+int scal_nbr_knn_device(scal_nbr_t* ctx, const float* d_xyzi, int n, int k, int* d_idx, float* d_d2);
+/* the index records themselves as the queries, rows (host) in the order the index was given in */
+int scal_nbr_knn_self(scal_nbr_t* ctx, int k, int* idx, float* d2);
+/* of the last query, radius or k-NN: (query, record) pairs tested and work items (pieces of up to 64 queries of one cell) */
 int scal_nbr_stats(scal_nbr_t* ctx, long long* pairs, int* work_items);
 
 #ifdef __cplusplus

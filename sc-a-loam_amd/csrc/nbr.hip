@@ -15,6 +15,9 @@
 //   minimum stay in registers and are written once, through the permutation, into the caller's order: no atomics on the outputs.
 //   An LDS stage for the broadcast was not built: it would add a ds_write / s_waitcnt / ds_read round trip per 64 records to save
 //   three VALU issues per record; see DESIGN.md for the instruction count of the inner loop as built.
+// knn (scal_nbr_knn*): the same sorted queries and the same index, then k_nb_knn<KC>: k_nb_query's front end
+//   with a sorted k-best list of 64-bit keys (d2 bits, input position) per lane in LDS; the rows go out padded with -1 / +inf, into
+//   staging that exists only once a host k-NN entry point has been called.
 //
 // Cell width.  w = the smallest power of two GREATER than r (never below 2^-62; one cell for everything when r r overflows), cell
 // coordinate floor(v * (1 / w)) in f32.  1 / w is a power of two, so the product is exact and so is the floor: the coordinate is
@@ -146,6 +149,93 @@ __global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs,
     }
 }
 
+constexpr unsigned long long NB_NO_KEY = ~0ull;  // above every key: d2 bits are at most +inf's, positions below 2^30
+
+// The k nearest candidates of every query (d2 <= r2), ordered by (d2, input position): k_nb_query's front end - sorted queries, a
+// wave per 64 of them, runs of one cell as work items, lanes 0 .. 26 on the ranges, records streamed 64 at a time and handed round by
+// v_readlane_b32 - with a k-best list per lane in place of count and minimum.  A list entry is the 64-bit key (d2 bits << 32) |
+// input position: d2 is >= +0 and not NaN, so its bits order as its value does, and the whole key orders as (d2, position) however
+// the records arrive from the cells.  The lists are in LDS as list[slot][lane], so one slot of the wave's 64 lanes is 512 contiguous
+// bytes: ds_read_b64 takes it in two conflict-free halves.  A lane's list is kept sorted; its length and its current k-th key (NB_NO_KEY
+// until the list is full) are in registers, so a record that does not enter costs the distance, one 64-bit compare and no LDS access.
+// One wave per block: the waves share nothing, and the block's LDS is KC * 512 bytes for the class KC >= k the host picks (8, 16, 32, 64),
+// which is what sets the waves per CU.  Only a lane that holds a finite query touches its column, and only in the work item it belongs to.
+// idx_out / d2_out [nq][k] may be null.  stats as in k_nb_query.
+template <int KC>
+__global__ void __launch_bounds__(64) k_nb_knn(const float4* __restrict__ qs, int nq, int k, float inv, float r2, const unsigned long long* __restrict__ hkeys,
+                                               const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
+                                               int* __restrict__ idx_out, float* __restrict__ d2_out, unsigned long long* __restrict__ stats) {
+    __shared__ unsigned long long list[KC * 64];
+    const int lane = threadIdx.x;
+    const long long i = static_cast<long long>(blockIdx.x) * 64 + lane;
+    const bool have = i < nq;
+    const float4 q = have ? qs[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool fin = have && nb_finite(q);
+    const size_t row = static_cast<size_t>(__float_as_int(q.w)) * static_cast<size_t>(k);
+    const int cx = nb_coord(q.x, inv, NB_XB), cy = nb_coord(q.y, inv, NB_XB), cz = nb_coord(q.z, inv, NB_ZB);
+    unsigned long long* const mylist = list + lane;  // slot s at mylist[64 * s]
+    int len = 0;
+    unsigned long long kth = NB_NO_KEY;
+    unsigned long long waiting = __ballot(fin), pairs = 0;
+    int items = 0;
+    while (waiting) {
+        const int leader = __ffsll(static_cast<long long>(waiting)) - 1;
+        const int lx = __builtin_amdgcn_readlane(cx, leader), ly = __builtin_amdgcn_readlane(cy, leader), lz = __builtin_amdgcn_readlane(cz, leader);
+        const bool mine = fin && cx == lx && cy == ly && cz == lz;
+        const unsigned long long peers = __ballot(mine);
+        int s0 = 0, e0 = 0;
+        if (lane < 27) {
+            const int az = lane / 9, ay = (lane - 9 * az) / 3, ax = lane - 9 * az - 3 * ay;
+            const unsigned long long key = nb_key(lx + ax - 1, ly + ay - 1, lz + az - 1);
+            int2 r;
+            if (key != NB_NO_CELL && ch_find(hkeys, hrange, mask, key, r)) s0 = r.x, e0 = r.y;
+        }
+        int seen = 0;
+        for (int c = 0; c < 27; ++c) {
+            const int s = __builtin_amdgcn_readlane(s0, c), e = __builtin_amdgcn_readlane(e0, c);
+            seen += e - s;
+            for (int b = s; b < e; b += 64) {
+                const int m = __builtin_amdgcn_readfirstlane(min(64, e - b));
+                const float4 p = lane < m ? sorted[b + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+                for (int j = 0; j < m; ++j) {
+                    const float dx = q.x - nb_lane_f(p.x, j), dy = q.y - nb_lane_f(p.y, j), dz = q.z - nb_lane_f(p.z, j);
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    const unsigned pos = static_cast<unsigned>(__builtin_amdgcn_readlane(__float_as_int(p.w), j));
+                    const unsigned long long key = (static_cast<unsigned long long>(__float_as_uint(d2)) << 32) | pos;
+                    if (mine && d2 <= r2 && key < kth) {
+                        // the list is sorted in slots [0, len); a full list drops its last entry
+                        int t = len < k ? len : k - 1;
+                        while (t > 0) {
+                            const unsigned long long prev = mylist[64 * (t - 1)];
+                            if (prev < key) break;
+                            mylist[64 * t] = prev;
+                            --t;
+                        }
+                        mylist[64 * t] = key;
+                        len += len < k;
+                        if (len == k) kth = mylist[64 * (k - 1)];
+                    }
+                }
+            }
+        }
+        pairs += static_cast<unsigned long long>(seen) * __popcll(peers);
+        ++items;
+        waiting &= ~peers;
+    }
+    if (have) {  // a query that is not finite has len 0: a fully padded row
+        for (int s = 0; s < k; ++s) {
+            const bool in = s < len;
+            const unsigned long long key = in ? mylist[64 * s] : 0ull;
+            if (idx_out) idx_out[row + s] = in ? static_cast<int>(static_cast<unsigned>(key)) : -1;
+            if (d2_out) d2_out[row + s] = __uint_as_float(in ? static_cast<unsigned>(key >> 32) : NB_INF);
+        }
+    }
+    if (lane == 0 && items) {
+        atomicAdd(stats, pairs);
+        atomicAdd(stats + 1, static_cast<unsigned long long>(items));
+    }
+}
+
 }  // namespace scal
 
 using namespace scal;
@@ -161,6 +251,8 @@ struct scal_nbr {
     DevBuf<int2> hrange;
     DevBuf<unsigned short> d_cnt;
     DevBuf<float> d_d2;
+    DevBuf<int> d_kidx;   // k-NN rows staged for the host: allocated at the first k-NN call, grown to the largest n * k so far
+    DevBuf<float> d_kd2;
     RadixSort sorter;
     int n = -1;  // -1: no index set
     float inv = 0.f, r2 = 0.f;
@@ -343,6 +435,91 @@ extern "C" int scal_nbr_query_self(scal_nbr_t* c, unsigned short* count_u16, flo
     SCAL_HIP(hipSetDevice(c->cfg.device));
     SCAL_TRY(nb_run(c, c->sorted.p, c->n, count_u16 ? c->d_cnt.p : nullptr, min_d2 ? c->d_d2.p : nullptr));
     return nb_download(c, c->n, count_u16, min_d2);
+}
+
+// the k nearest candidates of the nq queries at qs (cell order, output position in .w) -> d_idx / d_d2 [nq][k] (either may be null)
+static int nb_run_knn(scal_nbr* c, const float4* qs, int nq, int k, int* d_idx, float* d_d2) {
+    hipStream_t s = c->stream;
+    c->pairs = 0, c->work_items = 0;
+    if (nq == 0) return SCAL_OK;
+    SCAL_HIP(hipMemsetAsync(c->d_stats.p, 0, 2 * sizeof(unsigned long long), s));
+    const dim3 grid(div_up(nq, 64)), block(64);
+#define NB_KNN(KC)                                                                                                                          \
+    SCAL_LAUNCH_PROF("k_nb_knn", k_nb_knn<KC>, grid, block, 0, s, qs, nq, k, c->inv, c->r2, c->hkeys.p, c->hrange.p, c->hmask, c->sorted.p, \
+                     d_idx, d_d2, c->d_stats.p)
+    if (k <= 8) NB_KNN(8);
+    else if (k <= 16) NB_KNN(16);
+    else if (k <= 32) NB_KNN(32);
+    else NB_KNN(64);
+#undef NB_KNN
+    SCAL_HIP(hipGetLastError());
+    unsigned long long st[2] = {0, 0};
+    SCAL_HIP(hipMemcpyAsync(st, c->d_stats.p, sizeof st, hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipStreamSynchronize(s));
+    c->pairs = static_cast<long long>(st[0]), c->work_items = static_cast<int>(std::min<unsigned long long>(st[1], 0x7fffffffull));
+    return SCAL_OK;
+}
+
+static int nb_check_knn(scal_nbr* c, const char* who, const float* xyzi, int n, int k, bool self) {
+    if (!c || (!self && (n < 0 || (n > 0 && !xyzi))) || k < 1 || k > SCAL_NBR_MAX_K) {
+        set_error("%s: bad argument (k is 1 .. %d)", who, SCAL_NBR_MAX_K);
+        return SCAL_E_ARG;
+    }
+    if (c->n < 0) {
+        set_error("%s: no index set", who);
+        return SCAL_E_STATE;
+    }
+    if (!self && n > c->cfg.max_query_points) {
+        set_error("%s: %d queries, max_query_points is %d", who, n, c->cfg.max_query_points);
+        return SCAL_E_CAPACITY;
+    }
+    return SCAL_OK;
+}
+
+// staging for n rows of k: a failed allocation leaves the buffer empty and the context as it was
+template <class T>
+static int nb_grow(DevBuf<T>& b, bool wanted, int n, int k) {
+    const size_t need = static_cast<size_t>(n) * static_cast<size_t>(k);
+    if (!wanted || need == 0 || (b.p && b.n >= need)) return SCAL_OK;
+    return b.alloc(need);
+}
+
+static int nb_download_knn(scal_nbr* c, int n, int k, int* idx, float* d2) {
+    if (n == 0) return SCAL_OK;
+    hipStream_t s = c->stream;
+    const size_t m = static_cast<size_t>(n) * static_cast<size_t>(k);
+    if (idx) SCAL_HIP(hipMemcpyAsync(idx, c->d_kidx.p, sizeof(int) * m, hipMemcpyDeviceToHost, s));
+    if (d2) SCAL_HIP(hipMemcpyAsync(d2, c->d_kd2.p, sizeof(float) * m, hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipStreamSynchronize(s));
+    return SCAL_OK;
+}
+
+extern "C" int scal_nbr_knn(scal_nbr_t* c, const float* xyzi, int n, int k, int* idx, float* d2) {
+    SCAL_TRY(nb_check_knn(c, "scal_nbr_knn", xyzi, n, k, false));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(nb_grow(c->d_kidx, idx != nullptr, n, k));
+    SCAL_TRY(nb_grow(c->d_kd2, d2 != nullptr, n, k));
+    if (!c->stage.p) SCAL_TRY(c->stage.alloc(static_cast<size_t>(c->cap)));
+    if (n > 0) SCAL_HIP(hipMemcpyAsync(c->stage.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, c->stream));
+    SCAL_TRY(nb_sort_queries(c, c->stage.p, n));
+    SCAL_TRY(nb_run_knn(c, c->qsorted.p, n, k, idx ? c->d_kidx.p : nullptr, d2 ? c->d_kd2.p : nullptr));
+    return nb_download_knn(c, n, k, idx, d2);
+}
+
+extern "C" int scal_nbr_knn_device(scal_nbr_t* c, const float* d_xyzi, int n, int k, int* d_idx, float* d_d2) {
+    SCAL_TRY(nb_check_knn(c, "scal_nbr_knn_device", d_xyzi, n, k, false));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(nb_sort_queries(c, reinterpret_cast<const float4*>(d_xyzi), n));
+    return nb_run_knn(c, c->qsorted.p, n, k, d_idx, d_d2);
+}
+
+extern "C" int scal_nbr_knn_self(scal_nbr_t* c, int k, int* idx, float* d2) {
+    SCAL_TRY(nb_check_knn(c, "scal_nbr_knn_self", nullptr, 0, k, true));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(nb_grow(c->d_kidx, idx != nullptr, c->n, k));
+    SCAL_TRY(nb_grow(c->d_kd2, d2 != nullptr, c->n, k));
+    SCAL_TRY(nb_run_knn(c, c->sorted.p, c->n, k, idx ? c->d_kidx.p : nullptr, d2 ? c->d_kd2.p : nullptr));
+    return nb_download_knn(c, c->n, k, idx, d2);
 }
 
 extern "C" int scal_nbr_stats(scal_nbr_t* c, long long* pairs, int* work_items) {

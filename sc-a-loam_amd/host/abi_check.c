@@ -78,6 +78,10 @@ int main(void) {
         return 1;
     }
     if (rc == SCAL_OK) scal_nbr_destroy(nb);
+    if (scal_nbr_knn_self(NULL, SCAL_NBR_MAX_K, NULL, NULL) != SCAL_E_ARG) {
+        printf("scal_nbr_knn_self accepted a NULL context\n");
+        return 1;
+    }
     printf("abi ok %s devices=%d\n", scal_version(), n);
     return 0;
 }

@@ -113,6 +113,9 @@ class NbrConfig(C.Structure):
     _fields_ = [("device", C.c_int), ("max_index_points", C.c_int), ("max_query_points", C.c_int)]
 
 
+NBR_MAX_K = 64   # SCAL_NBR_MAX_K
+
+
 class MapMergeConfig(C.Structure):
     _fields_ = [("max_points", C.c_longlong), ("max_frame_points", C.c_int), ("device", C.c_int)]
 
@@ -196,6 +199,7 @@ EXPORTED_SYMBOLS = [
     "scal_reloc_create", "scal_reloc_destroy", "scal_reloc_size", "scal_reloc_add_keyframe", "scal_reloc_query", "scal_reloc_query_batch", "scal_reloc_sc",
     "scal_removert_create", "scal_removert_destroy", "scal_removert_set_map", "scal_removert_set_map_device", "scal_removert_run", "scal_removert_compact", "scal_removert_scan_image",
     "scal_nbr_create", "scal_nbr_destroy", "scal_nbr_set_index", "scal_nbr_set_index_device", "scal_nbr_query", "scal_nbr_query_device", "scal_nbr_query_self", "scal_nbr_stats",
+    "scal_nbr_knn", "scal_nbr_knn_device", "scal_nbr_knn_self",
 ]
 
 _lib = None
@@ -394,6 +398,10 @@ def lib():
         L.scal_nbr_query_device.argtypes = [vp, vp, C.c_int, vp, vp]
         L.scal_nbr_query_self.argtypes = [vp, _u16p, _f32p]
         L.scal_nbr_stats.argtypes = [vp, C.POINTER(C.c_longlong), _i32p]
+    if hasattr(L, "scal_nbr_knn"):
+        L.scal_nbr_knn.argtypes = [vp, _f32p, C.c_int, C.c_int, _i32p, _f32p]
+        L.scal_nbr_knn_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
+        L.scal_nbr_knn_self.argtypes = [vp, C.c_int, _i32p, _f32p]
     L.scal_keyframe_gate_init.argtypes = [C.POINTER(KeyframeGateState), C.c_double, C.c_double]
     L.scal_keyframe_gate.argtypes = [C.POINTER(KeyframeGateState), _f64p, _f64p, _i32p]
     for fn in ("scal_pipeline_sc_of", "scal_pipeline_map_of"):
@@ -1176,7 +1184,8 @@ class Removert:
 class RadiusIndex:
     """scal_nbr: per query the number of index records within r (uint16, saturating) and the smallest f32 d^2 among them (+inf when
     none) - include/scaloam_hip.h has the definition, scaloam/nbr.py the CPU restatement the device equals bit for bit.  A query
-    set larger than max_query_points goes through in chunks; the result does not depend on the chunking."""
+    set larger than max_query_points goes through in chunks; the result does not depend on the chunking.  knn / knn_self / knn_device
+    give the k nearest of those records per query, ordered by (d2, input position), on the same index (scaloam.nbr.knn_within)."""
 
     def __init__(self, max_index_points, max_query_points, device=0):
         self.h = C.c_void_p()
@@ -1226,6 +1235,36 @@ class RadiusIndex:
     def query_device(self, d_xyzi_ptr, n, d_count_ptr, d_min_d2_ptr):
         """queries and outputs in device memory (either output may be None); at most max_query_points"""
         _check(lib().scal_nbr_query_device(self.h, d_xyzi_ptr, int(n), d_count_ptr, d_min_d2_ptr))
+        self._sum = self._stats()
+
+    def knn(self, xyzi, k):
+        """(idx int32 [n, k], d2 float32 [n, k]): per query its k nearest index records within r by (d2, input position), padded with
+        -1 / +inf; chunked by max_query_points, and stats() afterwards covers all chunks"""
+        q = _f32(xyzi).reshape(-1, 4)
+        n, k = q.shape[0], int(k)
+        kk = min(max(k, 1), NBR_MAX_K)   # the buffers' width; a k out of range is the library's to refuse
+        idx, d2 = np.zeros((max(n, 1), kk), np.int32), np.zeros((max(n, 1), kk), np.float32)
+        pairs, items = 0, 0
+        for i in range(0, max(n, 1), self.max_query_points):
+            m = min(self.max_query_points, n - i)
+            _check(lib().scal_nbr_knn(self.h, _p(q[i:i + m], _f32p), m, k, _p(idx[i:], _i32p), _p(d2[i:], _f32p)))
+            st = self._stats()
+            pairs, items = pairs + st[0], items + st[1]
+        self._sum = (pairs, items)
+        return idx[:n], d2[:n]
+
+    def knn_self(self, k):
+        """the index records as the queries, rows in the order the index was given in"""
+        k = int(k)
+        kk = min(max(k, 1), NBR_MAX_K)
+        idx, d2 = np.zeros((max(self.n, 1), kk), np.int32), np.zeros((max(self.n, 1), kk), np.float32)
+        _check(lib().scal_nbr_knn_self(self.h, k, _p(idx, _i32p), _p(d2, _f32p)))
+        self._sum = self._stats()
+        return idx[:self.n], d2[:self.n]
+
+    def knn_device(self, d_xyzi_ptr, n, k, d_idx_ptr, d_d2_ptr):
+        """queries and the [n, k] outputs in device memory (either output may be None); at most max_query_points"""
+        _check(lib().scal_nbr_knn_device(self.h, d_xyzi_ptr, int(n), int(k), d_idx_ptr, d_d2_ptr))
         self._sum = self._stats()
 
     def _stats(self):

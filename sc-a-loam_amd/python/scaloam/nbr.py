@@ -4,8 +4,12 @@ has for scal_removert; numpy and scipy only, every f32 expression elementwise in
 8.11 has the reasoning.  The functions that take device=True run the same steps on the GPU through scaloam.RadiusIndex and
 scaloam.Removert (imported only then); nothing else here touches the device.
 
-PCL is not on the machines this was written on, so radius_outlier_mask restates PCL 1.8's RadiusOutlierRemoval rule from its
-source text - parity unpinned, as DESIGN.md section 2 says of the other PCL restatements."""
+knn_within is the specification of scal_nbr_knn* in the same way (the k nearest candidates within r by (d2, input position), DESIGN.md
+section 8.12); knn makes exact unbounded k-NN of it by escalating the radius, statistical_outlier_mask is the filter built on that.
+
+PCL is not on the machines this was written on, so radius_outlier_mask and statistical_outlier_mask restate PCL 1.8's
+RadiusOutlierRemoval and StatisticalOutlierRemoval rules from their source text - parity unpinned, as DESIGN.md section 2 says of the
+other PCL restatements."""
 import numpy as np
 
 from . import removert as _rv
@@ -17,6 +21,8 @@ DEFAULT_RADIUS = 0.8
 BRUTE_LIMIT = 4000        # index and query sets up to this size take the dense path
 TREE_SLACK = 1e-3         # the tree's f64 radius is wider by this factor; it only widens the candidate list
 COMMON, UNOBSERVED, CHANGED = 0, 1, 2
+MAX_K = 64                # SCAL_NBR_MAX_K
+_NO_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 def _xyzi(a):
@@ -119,6 +125,155 @@ def radius_outlier_mask(xyzi, r, min_neighbors, device=False):
         raise ValueError("min_neighbors must be >= 0")
     count, _ = _device_counts(P, None, r, self_query=True) if device else radius_counts(P, P, r)
     return (count.astype(np.int64) > int(min_neighbors)) & np.isfinite(P[:, :3]).all(1)
+
+
+def _k(k):
+    if int(k) != k or not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"k must be an integer in 1 .. {MAX_K}")
+    return int(k)
+
+
+def _rows(keys):
+    """sorted uint64 keys (d2 bits << 32 | position, _NO_KEY as padding) -> (idx int32, d2 float32)"""
+    pad = keys == _NO_KEY
+    idx = np.where(pad, -1, (keys & np.uint64(0xFFFFFFFF)).astype(np.int64)).astype(np.int32)
+    d2 = np.where(pad, np.float32(np.inf), (keys >> np.uint64(32)).astype(np.uint32).view(np.float32)).astype(np.float32)
+    return idx, d2
+
+
+def _knn_brute(I, pos, Q, r2, k, keys):
+    """dense: the key (d2 bits, position) of every candidate pair, the k smallest per query.  d2 is >= +0 and never NaN, so its bits
+    order as its value does - the device keeps the same keys"""
+    if I.shape[0] == 0:
+        return
+    step = max(1, (1 << 21) // I.shape[0])
+    for a in range(0, Q.shape[0], step):
+        d2 = _d2(Q[a:a + step, None, :], I[None, :, :])
+        key = np.where(d2 <= r2, (d2.view(np.uint32).astype(np.uint64) << np.uint64(32)) | pos[None, :], _NO_KEY)
+        m = min(k, key.shape[1])
+        if m < key.shape[1]:
+            key = np.partition(key, m - 1, axis=1)[:, :m]
+        keys[a:a + step, :m] = np.sort(key, axis=1)
+
+
+def _knn_tree(I, pos, Q, r32, r2, k, keys):
+    """candidates from the tree at a slightly wider f64 radius, the exact f32 decision, a lexsort on (d2, position) per query"""
+    from scipy.spatial import cKDTree
+    if I.shape[0] == 0:
+        return
+    tree = cKDTree(I.astype(np.float64))
+    step = 1 << 16
+    for a in range(0, Q.shape[0], step):
+        q = Q[a:a + step]
+        lists = tree.query_ball_point(q.astype(np.float64), float(r32) * (1.0 + TREE_SLACK), return_sorted=False)
+        lens = np.fromiter((len(l) for l in lists), np.int64, len(lists))
+        if lens.sum() == 0:
+            continue
+        pi = np.concatenate([np.asarray(l, np.int64) for l in lists if len(l)])
+        qi = np.repeat(np.arange(q.shape[0]), lens)
+        d2 = _d2(q[qi], I[pi])
+        within = d2 <= r2
+        pi, qi, d2 = pi[within], qi[within], d2[within]
+        order = np.lexsort((pos[pi], d2, qi))
+        pi, qi, d2 = pi[order], qi[order], d2[order]
+        first = np.searchsorted(qi, np.arange(q.shape[0]))       # where each query's candidates begin
+        rank = np.arange(qi.shape[0]) - first[qi]
+        take = rank < k
+        keys[a + qi[take], rank[take]] = (d2[take].view(np.uint32).astype(np.uint64) << np.uint64(32)) | pos[pi[take]]
+
+
+def knn_within(index_xyzi, query_xyzi, k, r, path=None):
+    """(idx int32 [nq, k], d2 float32 [nq, k]): per query its first k candidates - the finite index records with d2 <= r2 - in the
+    order (d2, input position), padded with -1 and +inf; a query that is not finite gets a padded row.  path as in radius_counts."""
+    I, Q = _xyzi(index_xyzi), _xyzi(query_xyzi)
+    k = _k(k)
+    r32, r2 = _radius(r)
+    fi, fq = np.isfinite(I[:, :3]).all(1), np.isfinite(Q[:, :3]).all(1)
+    Ifin, Qfin, pos = I[fi, :3], Q[fq, :3], np.flatnonzero(fi).astype(np.uint64)
+    keys = np.full((Qfin.shape[0], k), _NO_KEY, np.uint64)
+    if path is None:
+        path = "brute" if max(I.shape[0], Q.shape[0]) <= BRUTE_LIMIT else "tree"
+    if path == "brute":
+        _knn_brute(Ifin, pos, Qfin, r2, k, keys)
+    elif path == "tree":
+        _knn_tree(Ifin, pos, Qfin, r32, r2, k, keys)
+    else:
+        raise ValueError("path is 'brute', 'tree' or None")
+    out = np.full((Q.shape[0], k), _NO_KEY, np.uint64)
+    out[fq] = keys
+    return _rows(out)
+
+
+def knn(index_xyzi, query_xyzi, k, r0, r_max=None, device=False):
+    """Exact k nearest neighbours without a radius, by escalation: knn_within at r0, then again at twice the radius for the queries
+    whose row is not full, and so on.  A full row is final: what the bound left out is strictly farther than its last entry.  It stops
+    when no row is short; when a short row holds every finite index record - the radius covers them all, I has fewer than k; when
+    the next radius would pass r_max (short rows then stay as the last level left them: padded behind the neighbours within that
+    radius); or when the radius leaves the float32 range.  query_xyzi None is the self query.  device=True swaps the bounded
+    primitive for scaloam.RadiusIndex (the index rebuilt per level, only the unresolved queries sent) and nothing else.
+    Returns (idx int32 [nq, k], d2 float32 [nq, k], levels)."""
+    I = _xyzi(index_xyzi)
+    Q = I if query_xyzi is None else _xyzi(query_xyzi)
+    k = _k(k)
+    _radius(r0)
+    if r_max is not None and not r_max >= r0:
+        raise ValueError("r_max must be >= r0")
+    nq = Q.shape[0]
+    idx, d2 = np.full((nq, k), -1, np.int32), np.full((nq, k), np.inf, np.float32)
+    need = min(k, int(np.isfinite(I[:, :3]).all(1).sum()))       # the longest a row can get
+    pending = np.flatnonzero(np.isfinite(Q[:, :3]).all(1)) if need else np.zeros(0, np.int64)
+    ctx = None
+    if device and pending.size:
+        from . import RadiusIndex
+        ctx = RadiusIndex(max(I.shape[0], 1), max(min(nq, 1 << 22), 1))
+    levels, r = 0, float(r0)
+    try:
+        while pending.size:
+            if ctx is not None:
+                ctx.set_index(I, r)
+                whole = query_xyzi is None and pending.size == nq == I.shape[0]
+                li, ld = ctx.knn_self(k) if whole else ctx.knn(Q[pending], k)
+                if whole:
+                    li, ld = li[pending], ld[pending]
+            else:
+                li, ld = knn_within(I, Q[pending], k, r)
+            idx[pending], d2[pending] = li, ld
+            levels += 1
+            pending = pending[(li >= 0).sum(1) < need]
+            r *= 2.0
+            with np.errstate(over="ignore"):
+                if (r_max is not None and r > r_max) or not np.isfinite(np.float32(r)):
+                    break
+    finally:
+        if ctx is not None:
+            ctx.close()
+    return idx, d2, levels
+
+
+def statistical_outlier_mask(xyzi, mean_k, std_mul, r0, r_max=None, device=False):
+    """bool [n]: the records to keep.  PCL 1.8 StatisticalOutlierRemoval (filters/impl/statistical_outlier_removal.hpp), restated:
+    nearestKSearch with mean_k + 1 returns the point itself first and it is dropped; dist_i is the f64 mean of sqrt(float64(d2))
+    over the other mean_k; over the n_v valid points mean = sum / n_v, var = (sq_sum - sum sum / n_v) / (n_v - 1) and a point stays
+    iff dist_i <= mean + std_mul sqrt(var).  A record that is not finite, or whose row is short (fewer than mean_k + 1 finite records
+    within r_max, or in the cloud), has dist_i = +inf: it is dropped and takes no part in the statistics.  With fewer than two
+    valid points the variance is taken as 0 (PCL divides by zero there), and a variance that rounding left below 0 likewise.  The neighbour lists come from knn (r0, r_max, device as
+    there); everything after them is the same host numpy for both paths, so equal lists give equal masks."""
+    P = _xyzi(xyzi)
+    if int(mean_k) != mean_k or not 1 <= int(mean_k) <= MAX_K - 1:
+        raise ValueError(f"mean_k must be an integer in 1 .. {MAX_K - 1}")
+    if not np.isfinite(std_mul):
+        raise ValueError("std_mul must be finite")
+    idx, d2, _ = knn(P, None, int(mean_k) + 1, r0, r_max, device)
+    valid = idx[:, -1] >= 0
+    dist = np.full(P.shape[0], np.inf, np.float64)
+    dist[valid] = np.sqrt(d2[valid, 1:].astype(np.float64)).mean(1)
+    n_v = int(valid.sum())
+    if n_v == 0:
+        return np.zeros(P.shape[0], bool)
+    total, sq = float(dist[valid].sum()), float((dist[valid] * dist[valid]).sum())
+    mean = total / n_v
+    var = max((sq - total * total / n_v) / (n_v - 1), 0.0) if n_v > 1 else 0.0
+    return dist <= mean + float(std_mul) * np.sqrt(var)
 
 
 def map_diff(map_x, map_y, scans_y, poses12_y, r=DEFAULT_RADIUS, device=False, **removert_settings):

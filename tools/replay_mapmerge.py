@@ -7,7 +7,11 @@ refined_poses.txt beside the session's optimized_poses.txt and merges with them.
 where it lies in device memory, with the poses the merge used (the refined ones after --refine), reports the counts and writes the
 static points beside the map as *_static.pcd - after VoxelGrid(--leaf) if a leaf is given.  `--radius-filter R,MIN` drops the isolated
 returns before either map is written: a point stays iff more than MIN points of the merged map, itself included, lie within R
-(scal_nbr_*, the map indexed where it lies in device memory; scaloam.nbr.radius_outlier_mask is the rule)."""
+(scal_nbr_*, the map indexed where it lies in device memory; scaloam.nbr.radius_outlier_mask is the rule).  `--sor-filter
+MEAN_K,STD_MUL[,R0]` drops the statistical outliers in the same place: a point stays iff the mean distance to its MEAN_K nearest
+neighbours is at most the map's mean of that figure plus STD_MUL standard deviations (scaloam.nbr.statistical_outlier_mask on the
+device: exact k-NN from scal_nbr_knn*, the search radius doubled from R0, default 0.5 m, until every list is full).  With both filters
+each is computed on the whole merged map and a point has to pass both."""
 import argparse
 import glob
 import os
@@ -34,7 +38,19 @@ def main():
     ap.add_argument("--revert-res", type=float, nargs="*", default=[5.0], help="revert resolutions, degrees per pixel (may be empty)")
     ap.add_argument("--leaf", type=float, default=0.0, help="VoxelGrid leaf for the static map (0 = none)")
     ap.add_argument("--radius-filter", default=None, metavar="R,MIN", help="keep a point iff more than MIN map points lie within R metres of it")
+    ap.add_argument("--sor-filter", default=None, metavar="MEAN_K,STD_MUL[,R0]",
+                    help="keep a point iff its mean distance to its MEAN_K nearest neighbours is within STD_MUL standard deviations of the map's mean")
     a = ap.parse_args()
+    sor = None
+    if a.sor_filter:
+        try:
+            f = a.sor_filter.split(",")
+            sor = (int(f[0]), float(f[1]), float(f[2]) if len(f) > 2 else 0.5)
+            ok = len(f) in (2, 3) and 1 <= sor[0] <= 63 and np.isfinite(sor[1]) and np.isfinite(sor[2]) and sor[2] > 0
+        except (ValueError, IndexError):
+            ok = False
+        if not ok:
+            ap.error("--sor-filter takes MEAN_K,STD_MUL[,R0]: MEAN_K in 1 .. 63, STD_MUL finite, R0 > 0")
     import scaloam as S
     from scaloam import formats as F
     files = sorted(glob.glob(os.path.join(a.data_dir, "Scans", "*.pcd")))
@@ -72,6 +88,11 @@ def main():
         idx.close()
         keep = (count.astype(np.int64) > int(min_nb)) & np.isfinite(out[:, :3]).all(1)
         print(f"radius-filter: {int(keep.sum())} of {out.shape[0]} points have more than {int(min_nb)} points within {float(r)} m")
+    if sor:
+        from scaloam import nbr
+        good = nbr.statistical_outlier_mask(out, sor[0], sor[1], sor[2], device=True)
+        print(f"sor-filter: {int(good.sum())} of {out.shape[0]} points lie within {sor[1]} standard deviations of the mean {sor[0]}-neighbour distance")
+        keep = good if keep is None else keep & good
     path = a.out or os.path.join(a.data_dir, f"map_{lo}_to_{hi}_with_intensity.pcd")
     F.write_pcd_binary(path, out if keep is None else out[keep])
     print("written", path)
