@@ -921,8 +921,30 @@ int scal_removert_scan_image(scal_removert_t* ctx, int k, int res_index, float* 
  * Device memory comes from the config and does not grow with the map, with one exception: the k-NN rows of scal_nbr_knn and
  * scal_nbr_knn_self are staged in 8 bytes x k x the queries of the call (4 for an output that is NULL), allocated at the first such
  * call and grown to the largest so far - 1.2 GB for a self query of 7.1 M points at k = 21.  A context that never asks for
- * neighbours pays nothing, and scal_nbr_knn_device writes to the caller's buffers and stages nothing. */
+ * neighbours pays nothing, and scal_nbr_knn_device writes to the caller's buffers and stages nothing.
+ *
+ * Normals and point-to-plane distances (scaloam.nbr.normals_within is the restatement).  The neighbourhood of
+ * a query q is its knn(q, k) row exactly as defined above, 3 <= k <= SCAL_NBR_MAX_K; m is its number of entries, p_s its records in
+ * row order.  Everything below is f64, every operation rounded once (no FMA), and every sum runs sequentially in row order from +0:
+ * the order of the sums is part of the interface.
+ *   centroid     c = (sum_s p_s) / m per axis, p_s converted exactly from f32.
+ *   covariance   d_s = p_s - c; the six sums of dx dx, dx dy, dx dz, dy dy, dy dz, dz dz over a second pass, each divided by m.
+ *   eigenvectors cyclic Jacobi on A = the covariance, V = identity, with + - * / sqrt, compares and selects only: up to 8 sweeps over
+ *                the pairs (p, q) = (0, 1), (0, 2), (1, 2), r the third index.  A pair with a_pq == 0 leaves A and V untouched.
+ *                Otherwise theta = (a_qq - a_pp) / (2 a_pq), t = 1 / (|theta| + sqrt(theta theta + 1)), negated where theta < 0,
+ *                c = 1 / sqrt(t t + 1), s = t c, h = t a_pq; a_pp -= h, a_qq += h, a_pq = 0; (a_rp, a_rq) becomes
+ *                (c a_rp - s a_rq, s a_rp + c a_rq), and so does (v_ip, v_iq) for every row i of V.
+ *   normal       the column of V under the smallest diagonal entry lambda_min, the lowest column on ties.
+ *   curvature    (lambda_min > 0 ? lambda_min : 0) / tr for tr = (a_00 + a_11) + a_22, and 0 where tr <= 0.
+ *   viewpoint    three doubles, optional: with v = viewpoint - q, the normal is negated iff (nx vx + ny vy) + nz vz < 0.  Without a
+ *                viewpoint the sign is what the rotations deliver - deterministic, not oriented.
+ *   distance     (nx ex + ny ey) + nz ez for e = q - c, after the flip: the signed distance of q to the plane through c.
+ * Outputs: nc [n][4] float32 - the normal's components rounded to f32, then the curvature - and dist [n] float32.  Where m < 3
+ * (a query that is not finite has m = 0) all five values are the quiet NaN SCAL_NBR_NAN_BITS.  The host entry points stage nc and
+ * dist in max(max_index_points, max_query_points) entries each, allocated when first asked for, and the first normals call of a
+ * context allocates a position table of 4 bytes x max_index_points, refilled from the index's own records after every set_index. */
 #define SCAL_NBR_MAX_K 64
+#define SCAL_NBR_NAN_BITS 0x7fc00000u
 typedef struct {
     int device;
     int max_index_points;     /* 1 .. 2^30 */
@@ -954,7 +976,14 @@ int scal_nbr_knn(scal_nbr_t* ctx, const float* xyzi, int n, int k, int* idx, flo
 int scal_nbr_knn_device(scal_nbr_t* ctx, const float* d_xyzi, int n, int k, int* d_idx, float* d_d2);
 /* the index records themselves as the queries, rows (host) in the order the index was given in */
 int scal_nbr_knn_self(scal_nbr_t* ctx, int k, int* idx, float* d2);
-/* of the last query, radius or k-NN: (query, record) pairs tested and work items (pieces of up to 64 queries of one cell) */
+/* n queries (host), 3 <= k <= SCAL_NBR_MAX_K, viewpoint3 three doubles or NULL -> nc [n][4], dist [n] (host; either may be NULL), as
+ * defined above.  Error codes as scal_nbr_knn (k < 3 is SCAL_E_ARG). */
+int scal_nbr_normals(scal_nbr_t* ctx, const float* xyzi, int n, int k, const double* viewpoint3, float* nc, float* dist);
+/* queries and outputs in device memory (viewpoint3 stays a host pointer); waits for the result */
+int scal_nbr_normals_device(scal_nbr_t* ctx, const float* d_xyzi, int n, int k, const double* viewpoint3, float* d_nc, float* d_dist);
+/* the index records themselves as the queries, outputs (host) in the order the index was given in */
+int scal_nbr_normals_self(scal_nbr_t* ctx, int k, const double* viewpoint3, float* nc, float* dist);
+/* of the last query, radius, k-NN or normals: (query, record) pairs tested and work items (pieces of up to 64 queries of one cell) */
 int scal_nbr_stats(scal_nbr_t* ctx, long long* pairs, int* work_items);
 
 #ifdef __cplusplus

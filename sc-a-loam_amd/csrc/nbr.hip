@@ -18,6 +18,9 @@
 // knn (scal_nbr_knn*): the same sorted queries and the same index, then k_nb_knn<KC>: k_nb_query's front end
 //   with a sorted k-best list of 64-bit keys (d2 bits, input position) per lane in LDS; the rows go out padded with -1 / +inf, into
 //   staging that exists only once a host k-NN entry point has been called.
+// normals (scal_nbr_normals*): k_nb_normals<KC> has k_nb_knn's front end and list, then fits the plane where
+//   the list is - centroid, covariance and a cyclic Jacobi in f64 per lane - and writes 20 bytes per query.  It finds a neighbour's
+//   record through a position -> place table (k_nb_slots), which exists only once a normals entry point has been called.
 //
 // Cell width.  w = the smallest power of two GREATER than r (never below 2^-62; one cell for everything when r r overflows), cell
 // coordinate floor(v * (1 / w)) in f32.  1 / w is a power of two, so the product is exact and so is the floor: the coordinate is
@@ -161,19 +164,12 @@ constexpr unsigned long long NB_NO_KEY = ~0ull;  // above every key: d2 bits are
 // One wave per block: the waves share nothing, and the block's LDS is KC * 512 bytes for the class KC >= k the host picks (8, 16, 32, 64),
 // which is what sets the waves per CU.  Only a lane that holds a finite query touches its column, and only in the work item it belongs to.
 // idx_out / d2_out [nq][k] may be null.  stats as in k_nb_query.
-template <int KC>
-__global__ void __launch_bounds__(64) k_nb_knn(const float4* __restrict__ qs, int nq, int k, float inv, float r2, const unsigned long long* __restrict__ hkeys,
-                                               const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
-                                               int* __restrict__ idx_out, float* __restrict__ d2_out, unsigned long long* __restrict__ stats) {
-    __shared__ unsigned long long list[KC * 64];
-    const int lane = threadIdx.x;
-    const long long i = static_cast<long long>(blockIdx.x) * 64 + lane;
-    const bool have = i < nq;
-    const float4 q = have ? qs[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool fin = have && nb_finite(q);
-    const size_t row = static_cast<size_t>(__float_as_int(q.w)) * static_cast<size_t>(k);
+// nb_knn_lists is the front end and the list, shared with k_nb_normals: it fills the lane's column (slot s at mylist[64 * s]),
+// returns its length, and sends the wave's statistics out.
+__device__ __forceinline__ int nb_knn_lists(const float4 q, const bool fin, const int lane, const int k, const float inv, const float r2,
+                                            const unsigned long long* __restrict__ hkeys, const int2* __restrict__ hrange, const unsigned mask,
+                                            const float4* __restrict__ sorted, unsigned long long* const mylist, unsigned long long* __restrict__ stats) {
     const int cx = nb_coord(q.x, inv, NB_XB), cy = nb_coord(q.y, inv, NB_XB), cz = nb_coord(q.z, inv, NB_ZB);
-    unsigned long long* const mylist = list + lane;  // slot s at mylist[64 * s]
     int len = 0;
     unsigned long long kth = NB_NO_KEY;
     unsigned long long waiting = __ballot(fin), pairs = 0;
@@ -222,6 +218,26 @@ __global__ void __launch_bounds__(64) k_nb_knn(const float4* __restrict__ qs, in
         ++items;
         waiting &= ~peers;
     }
+    if (lane == 0 && items) {
+        atomicAdd(stats, pairs);
+        atomicAdd(stats + 1, static_cast<unsigned long long>(items));
+    }
+    return len;
+}
+
+template <int KC>
+__global__ void __launch_bounds__(64) k_nb_knn(const float4* __restrict__ qs, int nq, int k, float inv, float r2, const unsigned long long* __restrict__ hkeys,
+                                               const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
+                                               int* __restrict__ idx_out, float* __restrict__ d2_out, unsigned long long* __restrict__ stats) {
+    __shared__ unsigned long long list[KC * 64];
+    const int lane = threadIdx.x;
+    const long long i = static_cast<long long>(blockIdx.x) * 64 + lane;
+    const bool have = i < nq;
+    const float4 q = have ? qs[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool fin = have && nb_finite(q);
+    const size_t row = static_cast<size_t>(__float_as_int(q.w)) * static_cast<size_t>(k);
+    unsigned long long* const mylist = list + lane;  // slot s at mylist[64 * s]
+    const int len = nb_knn_lists(q, fin, lane, k, inv, r2, hkeys, hrange, mask, sorted, mylist, stats);
     if (have) {  // a query that is not finite has len 0: a fully padded row
         for (int s = 0; s < k; ++s) {
             const bool in = s < len;
@@ -230,10 +246,102 @@ __global__ void __launch_bounds__(64) k_nb_knn(const float4* __restrict__ qs, in
             if (d2_out) d2_out[row + s] = __uint_as_float(in ? static_cast<unsigned>(key >> 32) : NB_INF);
         }
     }
-    if (lane == 0 && items) {
-        atomicAdd(stats, pairs);
-        atomicAdd(stats + 1, static_cast<unsigned long long>(items));
+}
+
+constexpr unsigned NB_QNAN = 0x7fc00000u;  // SCAL_NBR_NAN_BITS
+
+// position -> slot: sorted[] is in cell order and a list entry names its record by input position
+__global__ void __launch_bounds__(256) k_nb_slots(const float4* __restrict__ sorted, int n, int* __restrict__ slot_of) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    slot_of[__float_as_int(sorted[i].w)] = i;
+}
+
+// One Jacobi rotation of the symmetric 3x3 A (pair p, q; r the third index) and of V's columns p and q, in the header's operation order.
+// a_pq == 0 leaves everything untouched.  All operands are named scalars: A and V stay in registers.
+__device__ __forceinline__ void nb_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p, double& v0q, double& v1p,
+                                          double& v1q, double& v2p, double& v2q) {
+    if (apq != 0.0) {
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double ta = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double t = theta < 0.0 ? -ta : ta;
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c, h = t * apq;
+        app -= h, aqq += h, apq = 0.0;
+        const double rp = c * arp - s * arq, rq = s * arp + c * arq;
+        arp = rp, arq = rq;
+        const double a0 = c * v0p - s * v0q, b0 = s * v0p + c * v0q, a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
+        const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
+        v0p = a0, v0q = b0, v1p = a1, v1q = b1, v2p = a2, v2q = b2;
     }
+}
+
+// Normal, curvature and point-to-plane distance per query (scal_nbr_normals*): k_nb_knn's front end and list,
+// then the fit where the list is.  The lane walks its column in slot order twice - centroid, then covariance about it - fetching each
+// neighbour's record from sorted[] through slot_of (the first walk leaves the slot in the entry for the second), runs the cyclic Jacobi
+// of the header in f64 on 15 named scalars and writes one float4 and one float through .w: no [n][k] buffer exists on this path.
+// Lanes without a fit (fewer than 3 neighbours, no query) carry A = 0 through the sweeps, which is a no-op, so the wave leaves the
+// sweep loop together on a ballot once every lane's off-diagonals are exactly 0.  nc_out / dist_out may be null.
+template <int KC>
+__global__ void __launch_bounds__(64) k_nb_normals(const float4* __restrict__ qs, int nq, int k, float inv, float r2, const unsigned long long* __restrict__ hkeys,
+                                                   const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
+                                                   const int* __restrict__ slot_of, int use_vp, double vpx, double vpy, double vpz,
+                                                   float4* __restrict__ nc_out, float* __restrict__ dist_out, unsigned long long* __restrict__ stats) {
+    __shared__ unsigned long long list[KC * 64];
+    const int lane = threadIdx.x;
+    const long long i = static_cast<long long>(blockIdx.x) * 64 + lane;
+    const bool have = i < nq;
+    const float4 q = have ? qs[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool fin = have && nb_finite(q);
+    const int out = __float_as_int(q.w);
+    unsigned long long* const mylist = list + lane;
+    const int len = nb_knn_lists(q, fin, lane, k, inv, r2, hkeys, hrange, mask, sorted, mylist, stats);
+    const int m = len >= 3 ? len : 0;
+    const double dm = static_cast<double>(m);
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    for (int s = 0; s < m; ++s) {
+        const int slot = slot_of[static_cast<unsigned>(mylist[64 * s])];
+        mylist[64 * s] = static_cast<unsigned long long>(slot);
+        const float4 p = sorted[slot];
+        sx += static_cast<double>(p.x), sy += static_cast<double>(p.y), sz += static_cast<double>(p.z);
+    }
+    const double cx = sx / dm, cy = sy / dm, cz = sz / dm;  // NaN where m is 0: never used
+    double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0;
+    for (int s = 0; s < m; ++s) {
+        const float4 p = sorted[static_cast<int>(mylist[64 * s])];
+        const double dx = static_cast<double>(p.x) - cx, dy = static_cast<double>(p.y) - cy, dz = static_cast<double>(p.z) - cz;
+        a00 += dx * dx, a01 += dx * dy, a02 += dx * dz, a11 += dy * dy, a12 += dy * dz, a22 += dz * dz;
+    }
+    if (m) a00 /= dm, a01 /= dm, a02 /= dm, a11 /= dm, a12 /= dm, a22 /= dm;
+    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+#pragma unroll 1
+    for (int sweep = 0; sweep < 8; ++sweep) {
+        if (!__ballot(a01 != 0.0 || a02 != 0.0 || a12 != 0.0)) break;
+        nb_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
+        nb_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
+        nb_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
+    }
+    if (!have) return;
+    float4 nc = make_float4(__uint_as_float(NB_QNAN), __uint_as_float(NB_QNAN), __uint_as_float(NB_QNAN), __uint_as_float(NB_QNAN));
+    float dist = __uint_as_float(NB_QNAN);
+    if (m) {
+        int j = 0;
+        double lmin = a00;
+        if (a11 < lmin) lmin = a11, j = 1;
+        if (a22 < lmin) lmin = a22, j = 2;
+        double nx = j == 0 ? v00 : j == 1 ? v01 : v02, ny = j == 0 ? v10 : j == 1 ? v11 : v12, nz = j == 0 ? v20 : j == 1 ? v21 : v22;
+        const double tr = (a00 + a11) + a22;
+        const double curv = tr > 0.0 ? (lmin > 0.0 ? lmin : 0.0) / tr : 0.0;
+        const double qx = static_cast<double>(q.x), qy = static_cast<double>(q.y), qz = static_cast<double>(q.z);
+        if (use_vp) {
+            const double wx = vpx - qx, wy = vpy - qy, wz = vpz - qz;
+            if ((nx * wx + ny * wy) + nz * wz < 0.0) nx = -nx, ny = -ny, nz = -nz;
+        }
+        const double ex = qx - cx, ey = qy - cy, ez = qz - cz;
+        nc = make_float4(static_cast<float>(nx), static_cast<float>(ny), static_cast<float>(nz), static_cast<float>(curv));
+        dist = static_cast<float>((nx * ex + ny * ey) + nz * ez);
+    }
+    if (nc_out) nc_out[out] = nc;
+    if (dist_out) dist_out[out] = dist;
 }
 
 }  // namespace scal
@@ -253,6 +361,10 @@ struct scal_nbr {
     DevBuf<float> d_d2;
     DevBuf<int> d_kidx;   // k-NN rows staged for the host: allocated at the first k-NN call, grown to the largest n * k so far
     DevBuf<float> d_kd2;
+    DevBuf<int> slot_of;  // input position -> place in sorted: allocated at the first normals call, refilled there after a new index
+    bool slots_ok = false;
+    DevBuf<float4> d_nc;  // normals staged for the host, cap entries each, allocated when first asked for
+    DevBuf<float> d_dist;
     RadixSort sorter;
     int n = -1;  // -1: no index set
     float inv = 0.f, r2 = 0.f;
@@ -320,7 +432,7 @@ static int nb_check_index(scal_nbr* c, const char* who, const float* xyzi, int n
 
 static int nb_build(scal_nbr* c, const float4* pts, int n, double radius) {
     hipStream_t s = c->stream;
-    c->n = -1, c->pairs = 0, c->work_items = 0;
+    c->n = -1, c->pairs = 0, c->work_items = 0, c->slots_ok = false;
     const float r = static_cast<float>(radius);
     c->r2 = r * r;
     // 1 / w for w = the smallest power of two > r: r = mant 2^e with mant in [0.5, 1), so w = 2^e
@@ -520,6 +632,95 @@ extern "C" int scal_nbr_knn_self(scal_nbr_t* c, int k, int* idx, float* d2) {
     SCAL_TRY(nb_grow(c->d_kd2, d2 != nullptr, c->n, k));
     SCAL_TRY(nb_run_knn(c, c->sorted.p, c->n, k, idx ? c->d_kidx.p : nullptr, d2 ? c->d_kd2.p : nullptr));
     return nb_download_knn(c, c->n, k, idx, d2);
+}
+
+// normal, curvature and plane distance of the nq queries at qs (cell order, output position in .w) -> d_nc [nq], d_dist [nq] (either may be null)
+static int nb_run_normals(scal_nbr* c, const float4* qs, int nq, int k, const double* vp, float4* d_nc, float* d_dist) {
+    hipStream_t s = c->stream;
+    c->pairs = 0, c->work_items = 0;
+    if (nq == 0) return SCAL_OK;
+    if (!c->slot_of.p) SCAL_TRY(c->slot_of.alloc(static_cast<size_t>(c->cfg.max_index_points)));
+    if (!c->slots_ok && c->n > 0) {  // from the index's own copy of the records: the caller's are not needed
+        SCAL_LAUNCH_PROF("k_nb_slots", k_nb_slots, dim3(div_up(c->n, 256)), dim3(256), 0, s, c->sorted.p, c->n, c->slot_of.p);
+        SCAL_HIP(hipGetLastError());
+    }
+    c->slots_ok = true;
+    SCAL_HIP(hipMemsetAsync(c->d_stats.p, 0, 2 * sizeof(unsigned long long), s));
+    const dim3 grid(div_up(nq, 64)), block(64);
+    const int use_vp = vp != nullptr;
+    const double vx = vp ? vp[0] : 0.0, vy = vp ? vp[1] : 0.0, vz = vp ? vp[2] : 0.0;
+#define NB_NORMALS(KC)                                                                                                                   \
+    SCAL_LAUNCH_PROF("k_nb_normals", k_nb_normals<KC>, grid, block, 0, s, qs, nq, k, c->inv, c->r2, c->hkeys.p, c->hrange.p, c->hmask, \
+                     c->sorted.p, c->slot_of.p, use_vp, vx, vy, vz, d_nc, d_dist, c->d_stats.p)
+    if (k <= 8) NB_NORMALS(8);
+    else if (k <= 16) NB_NORMALS(16);
+    else if (k <= 32) NB_NORMALS(32);
+    else NB_NORMALS(64);
+#undef NB_NORMALS
+    SCAL_HIP(hipGetLastError());
+    unsigned long long st[2] = {0, 0};
+    SCAL_HIP(hipMemcpyAsync(st, c->d_stats.p, sizeof st, hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipStreamSynchronize(s));
+    c->pairs = static_cast<long long>(st[0]), c->work_items = static_cast<int>(std::min<unsigned long long>(st[1], 0x7fffffffull));
+    return SCAL_OK;
+}
+
+static int nb_check_normals(scal_nbr* c, const char* who, const float* xyzi, int n, int k, bool self) {
+    if (!c || (!self && (n < 0 || (n > 0 && !xyzi))) || k < 3 || k > SCAL_NBR_MAX_K) {
+        set_error("%s: bad argument (k is 3 .. %d)", who, SCAL_NBR_MAX_K);
+        return SCAL_E_ARG;
+    }
+    if (c->n < 0) {
+        set_error("%s: no index set", who);
+        return SCAL_E_STATE;
+    }
+    if (!self && n > c->cfg.max_query_points) {
+        set_error("%s: %d queries, max_query_points is %d", who, n, c->cfg.max_query_points);
+        return SCAL_E_CAPACITY;
+    }
+    return SCAL_OK;
+}
+
+// the host outputs' staging, cap entries each, on first use
+static int nb_stage_normals(scal_nbr* c, bool nc, bool dist) {
+    if (nc && !c->d_nc.p) SCAL_TRY(c->d_nc.alloc(static_cast<size_t>(c->cap)));
+    if (dist && !c->d_dist.p) SCAL_TRY(c->d_dist.alloc(static_cast<size_t>(c->cap)));
+    return SCAL_OK;
+}
+
+static int nb_download_normals(scal_nbr* c, int n, float* nc, float* dist) {
+    if (n == 0) return SCAL_OK;
+    hipStream_t s = c->stream;
+    if (nc) SCAL_HIP(hipMemcpyAsync(nc, c->d_nc.p, sizeof(float4) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+    if (dist) SCAL_HIP(hipMemcpyAsync(dist, c->d_dist.p, sizeof(float) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipStreamSynchronize(s));
+    return SCAL_OK;
+}
+
+extern "C" int scal_nbr_normals(scal_nbr_t* c, const float* xyzi, int n, int k, const double* viewpoint3, float* nc, float* dist) {
+    SCAL_TRY(nb_check_normals(c, "scal_nbr_normals", xyzi, n, k, false));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(nb_stage_normals(c, nc != nullptr, dist != nullptr));
+    if (!c->stage.p) SCAL_TRY(c->stage.alloc(static_cast<size_t>(c->cap)));
+    if (n > 0) SCAL_HIP(hipMemcpyAsync(c->stage.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, c->stream));
+    SCAL_TRY(nb_sort_queries(c, c->stage.p, n));
+    SCAL_TRY(nb_run_normals(c, c->qsorted.p, n, k, viewpoint3, nc ? c->d_nc.p : nullptr, dist ? c->d_dist.p : nullptr));
+    return nb_download_normals(c, n, nc, dist);
+}
+
+extern "C" int scal_nbr_normals_device(scal_nbr_t* c, const float* d_xyzi, int n, int k, const double* viewpoint3, float* d_nc, float* d_dist) {
+    SCAL_TRY(nb_check_normals(c, "scal_nbr_normals_device", d_xyzi, n, k, false));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(nb_sort_queries(c, reinterpret_cast<const float4*>(d_xyzi), n));
+    return nb_run_normals(c, c->qsorted.p, n, k, viewpoint3, reinterpret_cast<float4*>(d_nc), d_dist);
+}
+
+extern "C" int scal_nbr_normals_self(scal_nbr_t* c, int k, const double* viewpoint3, float* nc, float* dist) {
+    SCAL_TRY(nb_check_normals(c, "scal_nbr_normals_self", nullptr, 0, k, true));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(nb_stage_normals(c, nc != nullptr, dist != nullptr));
+    SCAL_TRY(nb_run_normals(c, c->sorted.p, c->n, k, viewpoint3, nc ? c->d_nc.p : nullptr, dist ? c->d_dist.p : nullptr));
+    return nb_download_normals(c, c->n, nc, dist);
 }
 
 extern "C" int scal_nbr_stats(scal_nbr_t* c, long long* pairs, int* work_items) {

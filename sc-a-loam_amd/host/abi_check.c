@@ -82,6 +82,11 @@ int main(void) {
         printf("scal_nbr_knn_self accepted a NULL context\n");
         return 1;
     }
+    if (scal_nbr_normals_self(NULL, SCAL_NBR_MAX_K, NULL, NULL, NULL) != SCAL_E_ARG || scal_nbr_normals(NULL, NULL, 0, 3, NULL, NULL, NULL) != SCAL_E_ARG ||
+        scal_nbr_normals_device(NULL, NULL, 0, 3, NULL, NULL, NULL) != SCAL_E_ARG || SCAL_NBR_NAN_BITS != 0x7fc00000u) {
+        printf("scal_nbr_normals* accepted a NULL context\n");
+        return 1;
+    }
     printf("abi ok %s devices=%d\n", scal_version(), n);
     return 0;
 }

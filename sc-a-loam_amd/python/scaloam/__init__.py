@@ -200,6 +200,7 @@ EXPORTED_SYMBOLS = [
     "scal_removert_create", "scal_removert_destroy", "scal_removert_set_map", "scal_removert_set_map_device", "scal_removert_run", "scal_removert_compact", "scal_removert_scan_image",
     "scal_nbr_create", "scal_nbr_destroy", "scal_nbr_set_index", "scal_nbr_set_index_device", "scal_nbr_query", "scal_nbr_query_device", "scal_nbr_query_self", "scal_nbr_stats",
     "scal_nbr_knn", "scal_nbr_knn_device", "scal_nbr_knn_self",
+    "scal_nbr_normals", "scal_nbr_normals_device", "scal_nbr_normals_self",
 ]
 
 _lib = None
@@ -402,6 +403,10 @@ def lib():
         L.scal_nbr_knn.argtypes = [vp, _f32p, C.c_int, C.c_int, _i32p, _f32p]
         L.scal_nbr_knn_device.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
         L.scal_nbr_knn_self.argtypes = [vp, C.c_int, _i32p, _f32p]
+    if hasattr(L, "scal_nbr_normals"):
+        L.scal_nbr_normals.argtypes = [vp, _f32p, C.c_int, C.c_int, _f64p, _f32p, _f32p]
+        L.scal_nbr_normals_device.argtypes = [vp, vp, C.c_int, C.c_int, _f64p, vp, vp]
+        L.scal_nbr_normals_self.argtypes = [vp, C.c_int, _f64p, _f32p, _f32p]
     L.scal_keyframe_gate_init.argtypes = [C.POINTER(KeyframeGateState), C.c_double, C.c_double]
     L.scal_keyframe_gate.argtypes = [C.POINTER(KeyframeGateState), _f64p, _f64p, _i32p]
     for fn in ("scal_pipeline_sc_of", "scal_pipeline_map_of"):
@@ -1185,7 +1190,8 @@ class RadiusIndex:
     """scal_nbr: per query the number of index records within r (uint16, saturating) and the smallest f32 d^2 among them (+inf when
     none) - include/scaloam_hip.h has the definition, scaloam/nbr.py the CPU restatement the device equals bit for bit.  A query
     set larger than max_query_points goes through in chunks; the result does not depend on the chunking.  knn / knn_self / knn_device
-    give the k nearest of those records per query, ordered by (d2, input position), on the same index (scaloam.nbr.knn_within)."""
+    give the k nearest of those records per query, ordered by (d2, input position), on the same index (scaloam.nbr.knn_within);
+    normals / normals_self / normals_device the plane through them - normal, curvature, signed distance (scaloam.nbr.normals_within)."""
 
     def __init__(self, max_index_points, max_query_points, device=0):
         self.h = C.c_void_p()
@@ -1265,6 +1271,45 @@ class RadiusIndex:
     def knn_device(self, d_xyzi_ptr, n, k, d_idx_ptr, d_d2_ptr):
         """queries and the [n, k] outputs in device memory (either output may be None); at most max_query_points"""
         _check(lib().scal_nbr_knn_device(self.h, d_xyzi_ptr, int(n), int(k), d_idx_ptr, d_d2_ptr))
+        self._sum = self._stats()
+
+    @staticmethod
+    def _viewpoint(viewpoint):
+        if viewpoint is None:
+            return None, None
+        v = np.ascontiguousarray(viewpoint, np.float64).reshape(3)
+        return v, _p(v, _f64p)
+
+    def normals(self, xyzi, k, viewpoint=None):
+        """(nc float32 [n, 4], dist float32 [n]): per query the unit normal and the curvature of the plane through its k nearest index
+        records within r, and the query's signed distance to that plane (scaloam.nbr.normals_within); NaN where fewer than 3 records
+        are within r.  viewpoint: three numbers the normals are turned towards, or None.  Chunked by max_query_points, and stats()
+        afterwards covers all chunks"""
+        q = _f32(xyzi).reshape(-1, 4)
+        n, k = q.shape[0], int(k)
+        nc, dist = np.zeros((max(n, 1), 4), np.float32), np.zeros(max(n, 1), np.float32)
+        v, vptr = self._viewpoint(viewpoint)
+        pairs, items = 0, 0
+        for i in range(0, max(n, 1), self.max_query_points):
+            m = min(self.max_query_points, n - i)
+            _check(lib().scal_nbr_normals(self.h, _p(q[i:i + m], _f32p), m, k, vptr, _p(nc[i:], _f32p), _p(dist[i:], _f32p)))
+            st = self._stats()
+            pairs, items = pairs + st[0], items + st[1]
+        self._sum = (pairs, items)
+        return nc[:n], dist[:n]
+
+    def normals_self(self, k, viewpoint=None):
+        """the index records as the queries, outputs in the order the index was given in"""
+        nc, dist = np.zeros((max(self.n, 1), 4), np.float32), np.zeros(max(self.n, 1), np.float32)
+        v, vptr = self._viewpoint(viewpoint)
+        _check(lib().scal_nbr_normals_self(self.h, int(k), vptr, _p(nc, _f32p), _p(dist, _f32p)))
+        self._sum = self._stats()
+        return nc[:self.n], dist[:self.n]
+
+    def normals_device(self, d_xyzi_ptr, n, k, d_nc_ptr, d_dist_ptr, viewpoint=None):
+        """queries and the [n, 4] / [n] outputs in device memory (either output may be None); at most max_query_points"""
+        v, vptr = self._viewpoint(viewpoint)
+        _check(lib().scal_nbr_normals_device(self.h, d_xyzi_ptr, int(n), int(k), vptr, d_nc_ptr, d_dist_ptr))
         self._sum = self._stats()
 
     def _stats(self):

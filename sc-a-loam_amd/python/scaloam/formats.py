@@ -72,6 +72,32 @@ def write_pcd_binary(path, xyzi):
         f.write(pcd_binary_bytes(xyzi))
 
 
+def write_pcd_normals_binary(path, xyzi, nc):
+    """A binary PCD of x y z intensity normal_x normal_y normal_z curvature (eight packed f32 per point, no padding fields and no
+    page tail: not pcl::PointXYZINormal's in-memory layout).  nc [n, 4] as scaloam.nbr.normals_within returns it; read_pcd reads
+    the file back as xyzi and skips the rest."""
+    a, b = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4), np.ascontiguousarray(nc, np.float32).reshape(-1, 4)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError("one normal row per point is needed")
+    n = a.shape[0]
+    head = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity normal_x normal_y normal_z curvature\n"
+            "SIZE 4 4 4 4 4 4 4 4\nTYPE F F F F F F F F\nCOUNT 1 1 1 1 1 1 1 1\n"
+            f"WIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA binary\n").encode("ascii")
+    with open(path, "wb") as f:
+        f.write(head + np.concatenate([a, b], 1).tobytes())
+
+
+def read_pcd_normals(path):
+    """(xyzi float32 [n, 4], nc float32 [n, 4]) of a file write_pcd_normals_binary wrote"""
+    raw = open(path, "rb").read()
+    m = re.search(rb"DATA\s+binary\s*\n", raw)
+    if not m or b"normal_x normal_y normal_z curvature" not in raw[:m.end()]:
+        raise ValueError(f"{path}: not a binary PCD with normals")
+    n = int(re.search(rb"POINTS\s+(\d+)", raw[:m.end()]).group(1))
+    rec = np.frombuffer(raw, "<f4", n * 8, m.end()).reshape(n, 8)
+    return rec[:, :4].copy(), rec[:, 4:].copy()
+
+
 def _g6(v):
     return "%g" % v  # C++ ostream default: %g, precision 6
 

@@ -7,6 +7,9 @@ scaloam.Removert (imported only then); nothing else here touches the device.
 knn_within is the specification of scal_nbr_knn* in the same way (the k nearest candidates within r by (d2, input position), DESIGN.md
 section 8.12); knn makes exact unbounded k-NN of it by escalating the radius, statistical_outlier_mask is the filter built on that.
 
+normals_within is the specification of scal_nbr_normals* (the plane through a query's knn_within row: normal, curvature, signed
+distance; f64, every sum in row order, a cyclic Jacobi); estimate_normals and point_to_plane are its uses.
+
 PCL is not on the machines this was written on, so radius_outlier_mask and statistical_outlier_mask restate PCL 1.8's
 RadiusOutlierRemoval and StatisticalOutlierRemoval rules from their source text - parity unpinned, as DESIGN.md section 2 says of the
 other PCL restatements."""
@@ -274,6 +277,176 @@ def statistical_outlier_mask(xyzi, mean_k, std_mul, r0, r_max=None, device=False
     mean = total / n_v
     var = max((sq - total * total / n_v) / (n_v - 1), 0.0) if n_v > 1 else 0.0
     return dist <= mean + float(std_mul) * np.sqrt(var)
+
+
+NAN_BITS = 0x7FC00000     # SCAL_NBR_NAN_BITS: every output of a query with fewer than MIN_NORMAL_K neighbours
+MIN_NORMAL_K = 3
+JACOBI_SWEEPS = 8
+_PAIRS = ((0, 1, 2), (0, 2, 1), (1, 2, 0))       # (p, q, r) of a sweep
+
+
+def _normal_k(k):
+    if int(k) != k or not MIN_NORMAL_K <= int(k) <= MAX_K:
+        raise ValueError(f"k must be an integer in {MIN_NORMAL_K} .. {MAX_K}")
+    return int(k)
+
+
+def _viewpoint(viewpoint):
+    if viewpoint is None:
+        return None
+    v = np.asarray(viewpoint, np.float64).reshape(-1)
+    if v.shape[0] != 3:
+        raise ValueError("the viewpoint is three numbers")
+    return v
+
+
+def covariances(index_xyzi, idx):
+    """(c float64 [n, 3], A float64 [n, 3, 3] symmetric, m int64 [n]) of the rows idx (knn_within's, padded with -1): the header's two
+    passes, every sum sequential in row order from +0.  Rows with m < 3 hold zeros."""
+    P = _xyzi(index_xyzi)[:, :3].astype(np.float64)
+    idx = np.asarray(idx)
+    n, k = idx.shape
+    m = (idx >= 0).sum(1)
+    m = np.where(m >= MIN_NORMAL_K, m, 0)
+    use = m > 0
+    dm = np.where(use, m, 1).astype(np.float64)
+    c = np.zeros((n, 3), np.float64)
+    for s in range(k):
+        on = use & (idx[:, s] >= 0)
+        c[on] = c[on] + P[idx[on, s]]
+    c = c / dm[:, None]
+    S = np.zeros((n, 6), np.float64)
+    for s in range(k):
+        on = use & (idx[:, s] >= 0)
+        d = P[idx[on, s]] - c[on]
+        S[on] = S[on] + np.stack([d[:, 0] * d[:, 0], d[:, 0] * d[:, 1], d[:, 0] * d[:, 2], d[:, 1] * d[:, 1], d[:, 1] * d[:, 2], d[:, 2] * d[:, 2]], 1)
+    S = S / dm[:, None]
+    A = np.zeros((n, 3, 3), np.float64)
+    for col, (i, j) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        A[:, i, j] = A[:, j, i] = S[:, col]
+    return c, A, m
+
+
+def jacobi_eig3(A, sweeps=JACOBI_SWEEPS, trace=None):
+    """The header's cyclic Jacobi on symmetric A [n, 3, 3] (not changed): (diag float64 [n, 3], V float64 [n, 3, 3], eigenvectors in
+    V's columns).  + - * / sqrt, compares and selects; a pair with a_pq == 0 leaves its row of A and V untouched.  trace, a list,
+    receives the largest |off-diagonal| over all rows before every sweep and after the last."""
+    A = np.array(A, np.float64)
+    n = A.shape[0]
+    V = np.zeros((n, 3, 3), np.float64)
+    V[:, 0, 0] = V[:, 1, 1] = V[:, 2, 2] = 1.0
+
+    def off():
+        return float(np.abs(np.stack([A[:, 0, 1], A[:, 0, 2], A[:, 1, 2]], 1)).max()) if n else 0.0
+
+    with np.errstate(all="ignore"):
+        for _ in range(sweeps):
+            if trace is not None:
+                trace.append(off())
+            for p, q, r in _PAIRS:
+                apq = A[:, p, q]
+                on = apq != 0
+                if not on.any():
+                    continue
+                apq, app, aqq, arp, arq = apq[on], A[on, p, p], A[on, q, q], A[on, r, p], A[on, r, q]
+                theta = (aqq - app) / (2.0 * apq)
+                t = 1.0 / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                t = np.where(theta < 0, -t, t)
+                c = 1.0 / np.sqrt(t * t + 1.0)
+                s = t * c
+                h = t * apq
+                A[on, p, p], A[on, q, q] = app - h, aqq + h
+                A[on, p, q] = A[on, q, p] = 0.0
+                A[on, r, p] = A[on, p, r] = c * arp - s * arq
+                A[on, r, q] = A[on, q, r] = s * arp + c * arq
+                vp, vq = V[on, :, p], V[on, :, q]
+                V[on, :, p], V[on, :, q] = c[:, None] * vp - s[:, None] * vq, s[:, None] * vp + c[:, None] * vq
+    if trace is not None:
+        trace.append(off())
+    return np.stack([A[:, 0, 0], A[:, 1, 1], A[:, 2, 2]], 1), V
+
+
+def normals_within(index_xyzi, query_xyzi, k, r, viewpoint=None, path=None):
+    """The specification of scal_nbr_normals* (include/scaloam_hip.h): (nc float32 [nq, 4], dist float32 [nq]).
+    Per query the plane through its knn_within(k, r) row: nc is the unit normal (the eigenvector of the row's covariance for the
+    smallest eigenvalue, turned towards viewpoint when one is given) and the curvature lambda_min / trace; dist the query's signed
+    distance to the plane through the row's centroid.  All five are NaN (NAN_BITS) where the row has fewer than 3 entries.  Vectorised
+    over the queries, a loop over slots and sweeps; f64, one rounding per operation, sums in row order."""
+    I, Q = _xyzi(index_xyzi), _xyzi(query_xyzi)
+    k = _normal_k(k)
+    vp = _viewpoint(viewpoint)
+    idx, _ = knn_within(I, Q, k, r, path)
+    return fit_rows(I, Q, idx, vp)
+
+
+def fit_rows(index_xyzi, query_xyzi, idx, viewpoint=None):
+    """normals_within's tail: the fit of the rows idx [nq, k] (knn_within's, or the device's - they are equal), one per query"""
+    I, Q, vp = _xyzi(index_xyzi), _xyzi(query_xyzi), _viewpoint(viewpoint)
+    c, A, m = covariances(I, idx)
+    lam, V = jacobi_eig3(A)
+    n = Q.shape[0]
+    rows = np.arange(n)
+    j = np.zeros(n, np.int64)
+    lmin = lam[:, 0].copy()
+    for col in (1, 2):
+        less = lam[:, col] < lmin
+        lmin, j = np.where(less, lam[:, col], lmin), np.where(less, col, j)
+    nrm = V[rows, :, j]
+    with np.errstate(all="ignore"):
+        tr = (lam[:, 0] + lam[:, 1]) + lam[:, 2]
+        curv = np.where(tr > 0, np.where(lmin > 0, lmin, 0.0) / np.where(tr > 0, tr, 1.0), 0.0)
+        q = Q[:, :3].astype(np.float64)
+        if vp is not None:
+            w = vp[None, :] - q
+            flip = (nrm[:, 0] * w[:, 0] + nrm[:, 1] * w[:, 1]) + nrm[:, 2] * w[:, 2] < 0
+            nrm = np.where(flip[:, None], -nrm, nrm)
+        e = q - c
+        dist = ((nrm[:, 0] * e[:, 0] + nrm[:, 1] * e[:, 1]) + nrm[:, 2] * e[:, 2]).astype(np.float32)
+        nc = np.concatenate([nrm, curv[:, None]], 1).astype(np.float32)
+    none = m == 0
+    nc.view(np.uint32)[none] = NAN_BITS
+    dist.view(np.uint32)[none] = NAN_BITS
+    return nc, dist
+
+
+def _device_normals(I, Q, k, r, viewpoint):
+    from . import RadiusIndex
+    ctx = RadiusIndex(max(I.shape[0], 1), max(min(I.shape[0] if Q is None else Q.shape[0], 1 << 22), 1))
+    try:
+        ctx.set_index(I, r)
+        return ctx.normals_self(k, viewpoint) if Q is None else ctx.normals(Q, k, viewpoint)
+    finally:
+        ctx.close()
+
+
+def estimate_normals(xyzi, k, r, viewpoint=None, device=False):
+    """(nc float32 [n, 4], dist float32 [n]) of a cloud against itself: every point's neighbourhood holds the point.  device=True runs
+    scaloam.RadiusIndex.normals_self; the results are equal bit for bit."""
+    P = _xyzi(xyzi)
+    k = _normal_k(k)
+    _radius(r)
+    vp = _viewpoint(viewpoint)
+    return _device_normals(P, None, k, r, vp) if device else normals_within(P, P, k, r, vp)
+
+
+def point_to_plane(map_xyzi, cloud_xyzi, k, r, device=False):
+    """(dist float32 [n], valid bool [n]): the signed distance of every cloud point to the local plane of the map - the plane through
+    the point's k nearest map records within r - and where one exists (at least 3 such records; dist is NaN elsewhere).  The sign
+    follows the unoriented normal: |dist| is the residual.  residual_stats summarises the pair."""
+    M, P = _xyzi(map_xyzi), _xyzi(cloud_xyzi)
+    k = _normal_k(k)
+    _radius(r)
+    _, dist = _device_normals(M, P, k, r, None) if device else normals_within(M, P, k, r)
+    return dist, dist.view(np.uint32) != NAN_BITS
+
+
+def residual_stats(dist, valid):
+    """of point_to_plane's result, in f64 on the host whichever path made it: dict(valid, points, mean_abs, rms, median_abs), the
+    last three None without a valid point"""
+    dist, valid = np.asarray(dist, np.float32).reshape(-1), np.asarray(valid, bool).reshape(-1)
+    a = np.abs(dist[valid].astype(np.float64))
+    return dict(valid=int(valid.sum()), points=int(dist.shape[0]), mean_abs=float(a.mean()) if a.size else None,
+                rms=float(np.sqrt((a * a).mean())) if a.size else None, median_abs=float(np.median(a)) if a.size else None)
 
 
 def map_diff(map_x, map_y, scans_y, poses12_y, r=DEFAULT_RADIUS, device=False, **removert_settings):

@@ -11,7 +11,10 @@ returns before either map is written: a point stays iff more than MIN points of 
 MEAN_K,STD_MUL[,R0]` drops the statistical outliers in the same place: a point stays iff the mean distance to its MEAN_K nearest
 neighbours is at most the map's mean of that figure plus STD_MUL standard deviations (scaloam.nbr.statistical_outlier_mask on the
 device: exact k-NN from scal_nbr_knn*, the search radius doubled from R0, default 0.5 m, until every list is full).  With both filters
-each is computed on the whole merged map and a point has to pass both."""
+each is computed on the whole merged map and a point has to pass both.  `--normals K[,R]` writes the map that was written - after the
+filters - once more beside it as *_normals.pcd with normal_x normal_y normal_z curvature per point: the plane through each point's K
+nearest neighbours within R (default 0.8 m) of the written map, scal_nbr_normals_self (scaloam.nbr.estimate_normals is the rule); the
+normals are not oriented, and a point with fewer than 3 neighbours within R has NaN there."""
 import argparse
 import glob
 import os
@@ -40,7 +43,18 @@ def main():
     ap.add_argument("--radius-filter", default=None, metavar="R,MIN", help="keep a point iff more than MIN map points lie within R metres of it")
     ap.add_argument("--sor-filter", default=None, metavar="MEAN_K,STD_MUL[,R0]",
                     help="keep a point iff its mean distance to its MEAN_K nearest neighbours is within STD_MUL standard deviations of the map's mean")
+    ap.add_argument("--normals", default=None, metavar="K[,R]", help="write *_normals.pcd: normals and curvature from the K nearest neighbours within R")
     a = ap.parse_args()
+    normals = None
+    if a.normals:
+        try:
+            f = a.normals.split(",")
+            normals = (int(f[0]), float(f[1]) if len(f) > 1 else 0.8)
+            ok = len(f) in (1, 2) and 3 <= normals[0] <= 64 and np.isfinite(normals[1]) and normals[1] > 0
+        except (ValueError, IndexError):
+            ok = False
+        if not ok:
+            ap.error("--normals takes K[,R]: K in 3 .. 64, R > 0")
     sor = None
     if a.sor_filter:
         try:
@@ -96,6 +110,14 @@ def main():
     path = a.out or os.path.join(a.data_dir, f"map_{lo}_to_{hi}_with_intensity.pcd")
     F.write_pcd_binary(path, out if keep is None else out[keep])
     print("written", path)
+    if normals:
+        from scaloam import nbr
+        kept = out if keep is None else out[keep]
+        nc, _ = nbr.estimate_normals(kept, normals[0], normals[1], device=True)
+        print(f"normals: {int(np.isfinite(nc[:, 0]).sum())} of {kept.shape[0]} points have at least 3 neighbours within {normals[1]} m")
+        npath = os.path.splitext(path)[0] + "_normals.pcd"
+        F.write_pcd_normals_binary(npath, kept, nc)
+        print("written", npath)
     if a.remove_dynamic:
         n_res = len(a.remove_res) + len(a.revert_res)
         rm = S.Removert(out.shape[0] + 1, min(len(frames), 256), 256 * max(f.shape[0] for f in frames), max_resolutions=n_res,
