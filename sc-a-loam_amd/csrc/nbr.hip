@@ -15,12 +15,15 @@
 //   minimum stay in registers and are written once, through the permutation, into the caller's order: no atomics on the outputs.
 //   An LDS stage for the broadcast was not built: it would add a ds_write / s_waitcnt / ds_read round trip per 64 records to save
 //   three VALU issues per record; see DESIGN.md for the instruction count of the inner loop as built.
-// knn (scal_nbr_knn*): the same sorted queries and the same index, then k_nb_knn<KC>: k_nb_query's front end
-//   with a sorted k-best list of 64-bit keys (d2 bits, input position) per lane in LDS; the rows go out padded with -1 / +inf, into
-//   staging that exists only once a host k-NN entry point has been called.
-// normals (scal_nbr_normals*): k_nb_normals<KC> has k_nb_knn's front end and list, then fits the plane where
-//   the list is - centroid, covariance and a cyclic Jacobi in f64 per lane - and writes 20 bytes per query.  It finds a neighbour's
-//   record through a position -> place table (k_nb_slots), which exists only once a normals entry point has been called.
+//   The traversal - work items, ranges, batches, statistics - is one function, nb_visit, with what happens to a record passed in.
+// knn (scal_nbr_knn*): the same sorted queries and the same index, then k_nb_knn<KC>: the same traversal
+//   (written out once more in nb_knn_lists, see there) with a sorted k-best list of 64-bit keys (d2 bits, input position) per lane in LDS (nb_knn_lists); the rows go out padded with -1 / +inf,
+//   into staging that exists only once a host k-NN entry point has been called.
+// normals (scal_nbr_normals*): k_nb_normals<KC> builds the same lists, then fits the plane where the list
+//   is - centroid, covariance and a cyclic Jacobi in f64 per lane - and writes 20 bytes per query.  It finds a neighbour's record
+//   through a position -> place table (k_nb_slots), which exists only once a normals entry point has been called.
+// Host side: every entry point is the argument check (nb_check), the queries in cell order (nb_queries), where the kernel writes
+//   (nb_out), the launch with the statistics read back (nb_run) and, for a host caller, the download (nb_download).
 //
 // Cell width.  w = the smallest power of two GREATER than r (never below 2^-62; one cell for everything when r r overflows), cell
 // coordinate floor(v * (1 / w)) in f32.  1 / w is a power of two, so the product is exact and so is the floor: the coordinate is
@@ -39,6 +42,7 @@
 #include "radix_sort.hpp"
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 namespace scal {
 
@@ -90,22 +94,20 @@ __global__ void __launch_bounds__(256) k_nb_index(const unsigned long long* __re
 
 __device__ __forceinline__ float nb_lane_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 
-// qs: nq queries in cell order with their output position in .w; a wave per 64 of them (four waves per block, independent).
-// cnt_out / d2_out may be null.  stats: [0] (query, record) pairs tested, [1] work items.
-__global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs, int nq, float inv, float r2, const unsigned long long* __restrict__ hkeys,
-                                                  const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
-                                                  unsigned short* __restrict__ cnt_out, float* __restrict__ d2_out, unsigned long long* __restrict__ stats) {
-    const int lane = threadIdx.x & 63;
-    const int i = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + lane;
-    const bool have = i < nq;
-    const float4 q = have ? qs[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool fin = have && nb_finite(q);
-    const int out = __float_as_int(q.w);
+// The traversal of the query kernels, for one wave with a query per lane (fin: the lane holds a finite one).  The wave takes
+// the runs of equal cells among its queries one after the other: the lowest lane still waiting leads, `mine` are the lanes of its
+// cell - a work item.  Lanes 0 .. 26 look the 27 ranges around that cell up, the wave streams their records 64 at a time and hands
+// them round by v_readlane_b32.  What a kernel does with a record is its own:
+//   begin()                at the start of a work item,
+//   visit(mine, d2, p, j)  per record: p is the batch (a record per lane), j the uniform lane the record sits in, d2 the f32 distance
+//                          of the lane's own query to it - on every lane, `mine` or not,
+//   end(mine)              at the end of a work item.
+// stats: [0] (query, record) pairs tested, [1] work items - the same for every kernel, since they depend on nothing a callable does.
+template <class Begin, class Visit, class End>
+__device__ __forceinline__ void nb_visit(const float4 q, const bool fin, const int lane, const float inv, const unsigned long long* __restrict__ hkeys,
+                                         const int2* __restrict__ hrange, const unsigned mask, const float4* __restrict__ sorted,
+                                         unsigned long long* __restrict__ stats, Begin begin, Visit visit, End end) {
     const int cx = nb_coord(q.x, inv, NB_XB), cy = nb_coord(q.y, inv, NB_XB), cz = nb_coord(q.z, inv, NB_ZB);
-    if (have && !fin) {  // a query that is not finite: count 0, +inf
-        if (cnt_out) cnt_out[out] = 0;
-        if (d2_out) d2_out[out] = __uint_as_float(NB_INF);
-    }
     unsigned long long waiting = __ballot(fin), pairs = 0;
     int items = 0;
     while (waiting) {
@@ -120,8 +122,8 @@ __global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs,
             int2 r;
             if (key != NB_NO_CELL && ch_find(hkeys, hrange, mask, key, r)) s0 = r.x, e0 = r.y;
         }
-        int count = 0, seen = 0;
-        float best = __uint_as_float(NB_INF);
+        begin();
+        int seen = 0;
         for (int c = 0; c < 27; ++c) {
             const int s = __builtin_amdgcn_readlane(s0, c), e = __builtin_amdgcn_readlane(e0, c);
             seen += e - s;
@@ -130,18 +132,11 @@ __global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs,
                 const float4 p = lane < m ? sorted[b + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
                 for (int j = 0; j < m; ++j) {
                     const float dx = q.x - nb_lane_f(p.x, j), dy = q.y - nb_lane_f(p.y, j), dz = q.z - nb_lane_f(p.z, j);
-                    const float d2 = (dx * dx + dy * dy) + dz * dz;
-                    if (d2 <= r2) {
-                        ++count;
-                        best = d2 < best ? d2 : best;  // no NaN can arrive here: both records are finite
-                    }
+                    visit(mine, (dx * dx + dy * dy) + dz * dz, p, j);
                 }
             }
         }
-        if (mine) {
-            if (cnt_out) cnt_out[out] = static_cast<unsigned short>(min(count, 65535));
-            if (d2_out) d2_out[out] = best;
-        }
+        end(mine);
         pairs += static_cast<unsigned long long>(seen) * __popcll(peers);
         ++items;
         waiting &= ~peers;
@@ -152,20 +147,54 @@ __global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs,
     }
 }
 
+// qs: nq queries in cell order with their output position in .w; a wave per 64 of them (four waves per block, independent).
+// cnt_out / d2_out may be null.
+__global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs, int nq, float inv, float r2, const unsigned long long* __restrict__ hkeys,
+                                                  const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
+                                                  unsigned short* __restrict__ cnt_out, float* __restrict__ d2_out, unsigned long long* __restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const int i = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + lane;
+    const bool have = i < nq;
+    const float4 q = have ? qs[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool fin = have && nb_finite(q);
+    const int out = __float_as_int(q.w);
+    if (have && !fin) {  // a query that is not finite: count 0, +inf
+        if (cnt_out) cnt_out[out] = 0;
+        if (d2_out) d2_out[out] = __uint_as_float(NB_INF);
+    }
+    int count = 0;
+    float best = __uint_as_float(NB_INF);
+    nb_visit(
+        q, fin, lane, inv, hkeys, hrange, mask, sorted, stats, [&] { count = 0, best = __uint_as_float(NB_INF); },
+        [&](bool, float d2, const float4&, int) {  // every lane counts, its own work item or not: a predicate here is an issue per record
+            if (d2 <= r2) {
+                ++count;
+                best = d2 < best ? d2 : best;  // no NaN can arrive here: both records are finite
+            }
+        },
+        [&](bool mine) {
+            if (mine) {
+                if (cnt_out) cnt_out[out] = static_cast<unsigned short>(min(count, 65535));
+                if (d2_out) d2_out[out] = best;
+            }
+        });
+}
+
 constexpr unsigned long long NB_NO_KEY = ~0ull;  // above every key: d2 bits are at most +inf's, positions below 2^30
 
-// The k nearest candidates of every query (d2 <= r2), ordered by (d2, input position): k_nb_query's front end - sorted queries, a
-// wave per 64 of them, runs of one cell as work items, lanes 0 .. 26 on the ranges, records streamed 64 at a time and handed round by
-// v_readlane_b32 - with a k-best list per lane in place of count and minimum.  A list entry is the 64-bit key (d2 bits << 32) |
-// input position: d2 is >= +0 and not NaN, so its bits order as its value does, and the whole key orders as (d2, position) however
-// the records arrive from the cells.  The lists are in LDS as list[slot][lane], so one slot of the wave's 64 lanes is 512 contiguous
-// bytes: ds_read_b64 takes it in two conflict-free halves.  A lane's list is kept sorted; its length and its current k-th key (NB_NO_KEY
-// until the list is full) are in registers, so a record that does not enter costs the distance, one 64-bit compare and no LDS access.
-// One wave per block: the waves share nothing, and the block's LDS is KC * 512 bytes for the class KC >= k the host picks (8, 16, 32, 64),
-// which is what sets the waves per CU.  Only a lane that holds a finite query touches its column, and only in the work item it belongs to.
-// idx_out / d2_out [nq][k] may be null.  stats as in k_nb_query.
-// nb_knn_lists is the front end and the list, shared with k_nb_normals: it fills the lane's column (slot s at mylist[64 * s]),
-// returns its length, and sends the wave's statistics out.
+// The k nearest candidates of every query (d2 <= r2), ordered by (d2, input position): nb_visit's traversal with a k-best list per lane
+// in place of count and minimum.  A list entry is the 64-bit key (d2 bits << 32) | input position: d2 is >= +0 and not NaN, so its bits
+// order as its value does, and the whole key orders as (d2, position) however the records arrive from the cells.  The lists are in
+// LDS as list[slot][lane], so one slot of the wave's 64 lanes is 512 contiguous bytes: ds_read_b64 takes it in two conflict-free
+// halves.  A lane's list is kept sorted; its length and its current k-th key (NB_NO_KEY until the list is full) are in registers, so a
+// record that does not enter costs the distance, one 64-bit compare and no LDS access.  One wave per block: the waves share nothing,
+// and the block's LDS is KC * 512 bytes for the class KC >= k the host picks (8, 16, 32, 64), which is what sets the waves per CU.
+// Only a lane that holds a finite query touches its column, and only in the work item it belongs to.
+// nb_knn_lists fills the lane's column (slot s at mylist[64 * s]) and returns its length; k_nb_knn and k_nb_normals start with it.
+// It is NOT a use of nb_visit: the traversal is written out here a second time, statement for statement, and has to be kept equal to
+// nb_visit by hand (the tests pin equal statistics across the calls).  With the insertion passed to nb_visit as a callable - or
+// to any other function - the record and insertion loops compile to the same instructions in other registers, and k_nb_knn and
+// k_nb_normals then run between 4 % faster and 2 % slower, which is outside what identical builds show.
 __device__ __forceinline__ int nb_knn_lists(const float4 q, const bool fin, const int lane, const int k, const float inv, const float r2,
                                             const unsigned long long* __restrict__ hkeys, const int2* __restrict__ hrange, const unsigned mask,
                                             const float4* __restrict__ sorted, unsigned long long* const mylist, unsigned long long* __restrict__ stats) {
@@ -225,6 +254,7 @@ __device__ __forceinline__ int nb_knn_lists(const float4 q, const bool fin, cons
     return len;
 }
 
+// idx_out / d2_out [nq][k] may be null.
 template <int KC>
 __global__ void __launch_bounds__(64) k_nb_knn(const float4* __restrict__ qs, int nq, int k, float inv, float r2, const unsigned long long* __restrict__ hkeys,
                                                const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
@@ -275,8 +305,8 @@ __device__ __forceinline__ void nb_rotate(double& app, double& aqq, double& apq,
     }
 }
 
-// Normal, curvature and point-to-plane distance per query (scal_nbr_normals*): k_nb_knn's front end and list,
-// then the fit where the list is.  The lane walks its column in slot order twice - centroid, then covariance about it - fetching each
+// Normal, curvature and point-to-plane distance per query (scal_nbr_normals*): nb_knn_lists, then the fit
+// where the list is.  The lane walks its column in slot order twice - centroid, then covariance about it - fetching each
 // neighbour's record from sorted[] through slot_of (the first walk leaves the slot in the entry for the second), runs the cyclic Jacobi
 // of the header in f64 on 15 named scalars and writes one float4 and one float through .w: no [n][k] buffer exists on this path.
 // Lanes without a fit (fewer than 3 neighbours, no query) carry A = 0 through the sweeps, which is a no-op, so the wave leaves the
@@ -467,32 +497,21 @@ extern "C" int scal_nbr_set_index_device(scal_nbr_t* c, const float* d_xyzi, int
     return nb_build(c, reinterpret_cast<const float4*>(d_xyzi), n, radius);
 }
 
-// the nq queries at qs (cell order, output position in .w) -> d_cnt / d_d2 (either may be null); waits, reads the counters
-static int nb_run(scal_nbr* c, const float4* qs, int nq, unsigned short* d_cnt, float* d_d2) {
-    hipStream_t s = c->stream;
-    c->pairs = 0, c->work_items = 0;
-    if (nq == 0) return SCAL_OK;
-    SCAL_HIP(hipMemsetAsync(c->d_stats.p, 0, 2 * sizeof(unsigned long long), s));
-    SCAL_LAUNCH_PROF("k_nb_query", k_nb_query, dim3(div_up(nq, 256)), dim3(256), 0, s, qs, nq, c->inv, c->r2, c->hkeys.p, c->hrange.p, c->hmask,
-                     c->sorted.p, d_cnt, d_d2, c->d_stats.p);
-    SCAL_HIP(hipGetLastError());
-    unsigned long long st[2] = {0, 0};
-    SCAL_HIP(hipMemcpyAsync(st, c->d_stats.p, sizeof st, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipStreamSynchronize(s));
-    c->pairs = static_cast<long long>(st[0]), c->work_items = static_cast<int>(std::min<unsigned long long>(st[1], 0x7fffffffull));
-    return SCAL_OK;
-}
+enum NbSource { NB_HOST, NB_DEVICE, NB_SELF };  // where a call's queries are: the caller's host or device memory, or the index itself
 
-static int nb_check_query(scal_nbr* c, const char* who, const float* xyzi, int n) {
-    if (!c || n < 0 || (n > 0 && !xyzi)) {
-        set_error("%s: bad argument", who);
+// kmin: the smallest k the call takes (1: k-NN, 3: normals), 0 for a call without a k.  Refuses in the order ARG, STATE, CAPACITY.
+static int nb_check(scal_nbr* c, const char* who, NbSource src, const float* xyzi, int n, int kmin, int k) {
+    const bool self = src == NB_SELF;
+    if (!c || (!self && (n < 0 || (n > 0 && !xyzi))) || (kmin && (k < kmin || k > SCAL_NBR_MAX_K))) {
+        if (kmin) set_error("%s: bad argument (k is %d .. %d)", who, kmin, SCAL_NBR_MAX_K);
+        else set_error("%s: bad argument", who);
         return SCAL_E_ARG;
     }
     if (c->n < 0) {
         set_error("%s: no index set", who);
         return SCAL_E_STATE;
     }
-    if (n > c->cfg.max_query_points) {
+    if (!self && n > c->cfg.max_query_points) {
         set_error("%s: %d queries, max_query_points is %d", who, n, c->cfg.max_query_points);
         return SCAL_E_CAPACITY;
     }
@@ -509,218 +528,179 @@ static int nb_sort_queries(scal_nbr* c, const float4* pts, int n) {
     return SCAL_OK;
 }
 
-static int nb_download(scal_nbr* c, int n, unsigned short* count_u16, float* min_d2) {
-    if (n == 0) return SCAL_OK;
+// a checked call's queries in cell order, output position in .w: *qs, *nq.  A self query runs on the index's own order.
+static int nb_queries(scal_nbr* c, NbSource src, const float* xyzi, int n, const float4** qs, int* nq) {
+    if (src == NB_SELF) {
+        *qs = c->sorted.p, *nq = c->n;
+        return SCAL_OK;
+    }
+    const float4* pts = reinterpret_cast<const float4*>(xyzi);
+    if (src == NB_HOST) {
+        if (!c->stage.p) SCAL_TRY(c->stage.alloc(static_cast<size_t>(c->cap)));
+        if (n > 0) SCAL_HIP(hipMemcpyAsync(c->stage.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, c->stream));
+        pts = c->stage.p;
+    }
+    SCAL_TRY(nb_sort_queries(c, pts, n));
+    *qs = c->qsorted.p, *nq = n;
+    return SCAL_OK;
+}
+
+// *d: where the kernel writes an output.  A device call's is the caller's buffer; a host caller's is staging of at least m entries,
+// allocated or grown when asked for (a failed allocation leaves the buffer empty and the context as it was); null stays null.
+template <class T>
+static int nb_out(DevBuf<T>& stage, NbSource src, T* user, size_t m, T** d) {
+    *d = user;
+    if (src == NB_DEVICE || !user) return SCAL_OK;
+    if (m && !(stage.p && stage.n >= m)) SCAL_TRY(stage.alloc(m));
+    *d = stage.p;
+    return SCAL_OK;
+}
+
+// launch(stream) runs one query kernel over nq queries; waits, reads the counters
+template <class Launch>
+static int nb_run(scal_nbr* c, int nq, Launch launch) {
     hipStream_t s = c->stream;
-    if (count_u16) SCAL_HIP(hipMemcpyAsync(count_u16, c->d_cnt.p, sizeof(unsigned short) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
-    if (min_d2) SCAL_HIP(hipMemcpyAsync(min_d2, c->d_d2.p, sizeof(float) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
+    c->pairs = 0, c->work_items = 0;
+    if (nq == 0) return SCAL_OK;
+    SCAL_HIP(hipMemsetAsync(c->d_stats.p, 0, 2 * sizeof(unsigned long long), s));
+    SCAL_TRY(launch(s));
+    SCAL_HIP(hipGetLastError());
+    unsigned long long st[2] = {0, 0};
+    SCAL_HIP(hipMemcpyAsync(st, c->d_stats.p, sizeof st, hipMemcpyDeviceToHost, s));
+    SCAL_HIP(hipStreamSynchronize(s));
+    c->pairs = static_cast<long long>(st[0]), c->work_items = static_cast<int>(std::min<unsigned long long>(st[1], 0x7fffffffull));
+    return SCAL_OK;
+}
+
+// f(the list class KC >= k as a std::integral_constant): the kernels with a k-best list are instantiated for 8, 16, 32, 64
+template <class F>
+static void nb_list_class(int k, F f) {
+    if (k <= 8) f(std::integral_constant<int, 8>{});
+    else if (k <= 16) f(std::integral_constant<int, 16>{});
+    else if (k <= 32) f(std::integral_constant<int, 32>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+// a host caller's outputs, m entries each, out of the staging the kernel wrote them to (either may be null)
+template <class A, class B>
+static int nb_download(scal_nbr* c, NbSource src, size_t m, A* a, const A* d_a, B* b, const B* d_b) {
+    if (src == NB_DEVICE || m == 0) return SCAL_OK;
+    hipStream_t s = c->stream;
+    if (a) SCAL_HIP(hipMemcpyAsync(a, d_a, sizeof(A) * m, hipMemcpyDeviceToHost, s));
+    if (b) SCAL_HIP(hipMemcpyAsync(b, d_b, sizeof(B) * m, hipMemcpyDeviceToHost, s));
     SCAL_HIP(hipStreamSynchronize(s));
     return SCAL_OK;
+}
+
+// Each family below is one sequence for its three entry points: check, output staging (before `stage`, so that a failed allocation
+// leaves the context as it was), queries in cell order, kernel, download.
+static int nb_query(scal_nbr* c, const char* who, NbSource src, const float* xyzi, int n, unsigned short* cnt, float* d2) {
+    SCAL_TRY(nb_check(c, who, src, xyzi, n, 0, 0));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    const size_t m = static_cast<size_t>(src == NB_SELF ? c->n : n);
+    unsigned short* d_cnt;
+    float* d_d2;
+    SCAL_TRY(nb_out(c->d_cnt, src, cnt, m, &d_cnt));
+    SCAL_TRY(nb_out(c->d_d2, src, d2, m, &d_d2));
+    const float4* qs;
+    int nq;
+    SCAL_TRY(nb_queries(c, src, xyzi, n, &qs, &nq));
+    SCAL_TRY(nb_run(c, nq, [&](hipStream_t s) -> int {
+        SCAL_LAUNCH_PROF("k_nb_query", k_nb_query, dim3(div_up(nq, 256)), dim3(256), 0, s, qs, nq, c->inv, c->r2, c->hkeys.p, c->hrange.p, c->hmask,
+                         c->sorted.p, d_cnt, d_d2, c->d_stats.p);
+        return SCAL_OK;
+    }));
+    return nb_download(c, src, m, cnt, d_cnt, d2, d_d2);
 }
 
 extern "C" int scal_nbr_query(scal_nbr_t* c, const float* xyzi, int n, unsigned short* count_u16, float* min_d2) {
-    SCAL_TRY(nb_check_query(c, "scal_nbr_query", xyzi, n));
-    SCAL_HIP(hipSetDevice(c->cfg.device));
-    if (!c->stage.p) SCAL_TRY(c->stage.alloc(static_cast<size_t>(c->cap)));
-    if (n > 0) SCAL_HIP(hipMemcpyAsync(c->stage.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, c->stream));
-    SCAL_TRY(nb_sort_queries(c, c->stage.p, n));
-    SCAL_TRY(nb_run(c, c->qsorted.p, n, count_u16 ? c->d_cnt.p : nullptr, min_d2 ? c->d_d2.p : nullptr));
-    return nb_download(c, n, count_u16, min_d2);
+    return nb_query(c, "scal_nbr_query", NB_HOST, xyzi, n, count_u16, min_d2);
 }
 
 extern "C" int scal_nbr_query_device(scal_nbr_t* c, const float* d_xyzi, int n, unsigned short* d_count_u16, float* d_min_d2) {
-    SCAL_TRY(nb_check_query(c, "scal_nbr_query_device", d_xyzi, n));
-    SCAL_HIP(hipSetDevice(c->cfg.device));
-    SCAL_TRY(nb_sort_queries(c, reinterpret_cast<const float4*>(d_xyzi), n));
-    return nb_run(c, c->qsorted.p, n, d_count_u16, d_min_d2);
+    return nb_query(c, "scal_nbr_query_device", NB_DEVICE, d_xyzi, n, d_count_u16, d_min_d2);
 }
 
 extern "C" int scal_nbr_query_self(scal_nbr_t* c, unsigned short* count_u16, float* min_d2) {
-    if (!c) {
-        set_error("scal_nbr_query_self: bad argument");
-        return SCAL_E_ARG;
-    }
-    if (c->n < 0) {
-        set_error("scal_nbr_query_self: no index set");
-        return SCAL_E_STATE;
-    }
+    return nb_query(c, "scal_nbr_query_self", NB_SELF, nullptr, 0, count_u16, min_d2);
+}
+
+// the rows are staged in n * k entries, allocated at the first host k-NN call and grown to the largest so far
+static int nb_knn(scal_nbr* c, const char* who, NbSource src, const float* xyzi, int n, int k, int* idx, float* d2) {
+    SCAL_TRY(nb_check(c, who, src, xyzi, n, 1, k));
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    SCAL_TRY(nb_run(c, c->sorted.p, c->n, count_u16 ? c->d_cnt.p : nullptr, min_d2 ? c->d_d2.p : nullptr));
-    return nb_download(c, c->n, count_u16, min_d2);
-}
-
-// the k nearest candidates of the nq queries at qs (cell order, output position in .w) -> d_idx / d_d2 [nq][k] (either may be null)
-static int nb_run_knn(scal_nbr* c, const float4* qs, int nq, int k, int* d_idx, float* d_d2) {
-    hipStream_t s = c->stream;
-    c->pairs = 0, c->work_items = 0;
-    if (nq == 0) return SCAL_OK;
-    SCAL_HIP(hipMemsetAsync(c->d_stats.p, 0, 2 * sizeof(unsigned long long), s));
-    const dim3 grid(div_up(nq, 64)), block(64);
-#define NB_KNN(KC)                                                                                                                          \
-    SCAL_LAUNCH_PROF("k_nb_knn", k_nb_knn<KC>, grid, block, 0, s, qs, nq, k, c->inv, c->r2, c->hkeys.p, c->hrange.p, c->hmask, c->sorted.p, \
-                     d_idx, d_d2, c->d_stats.p)
-    if (k <= 8) NB_KNN(8);
-    else if (k <= 16) NB_KNN(16);
-    else if (k <= 32) NB_KNN(32);
-    else NB_KNN(64);
-#undef NB_KNN
-    SCAL_HIP(hipGetLastError());
-    unsigned long long st[2] = {0, 0};
-    SCAL_HIP(hipMemcpyAsync(st, c->d_stats.p, sizeof st, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipStreamSynchronize(s));
-    c->pairs = static_cast<long long>(st[0]), c->work_items = static_cast<int>(std::min<unsigned long long>(st[1], 0x7fffffffull));
-    return SCAL_OK;
-}
-
-static int nb_check_knn(scal_nbr* c, const char* who, const float* xyzi, int n, int k, bool self) {
-    if (!c || (!self && (n < 0 || (n > 0 && !xyzi))) || k < 1 || k > SCAL_NBR_MAX_K) {
-        set_error("%s: bad argument (k is 1 .. %d)", who, SCAL_NBR_MAX_K);
-        return SCAL_E_ARG;
-    }
-    if (c->n < 0) {
-        set_error("%s: no index set", who);
-        return SCAL_E_STATE;
-    }
-    if (!self && n > c->cfg.max_query_points) {
-        set_error("%s: %d queries, max_query_points is %d", who, n, c->cfg.max_query_points);
-        return SCAL_E_CAPACITY;
-    }
-    return SCAL_OK;
-}
-
-// staging for n rows of k: a failed allocation leaves the buffer empty and the context as it was
-template <class T>
-static int nb_grow(DevBuf<T>& b, bool wanted, int n, int k) {
-    const size_t need = static_cast<size_t>(n) * static_cast<size_t>(k);
-    if (!wanted || need == 0 || (b.p && b.n >= need)) return SCAL_OK;
-    return b.alloc(need);
-}
-
-static int nb_download_knn(scal_nbr* c, int n, int k, int* idx, float* d2) {
-    if (n == 0) return SCAL_OK;
-    hipStream_t s = c->stream;
-    const size_t m = static_cast<size_t>(n) * static_cast<size_t>(k);
-    if (idx) SCAL_HIP(hipMemcpyAsync(idx, c->d_kidx.p, sizeof(int) * m, hipMemcpyDeviceToHost, s));
-    if (d2) SCAL_HIP(hipMemcpyAsync(d2, c->d_kd2.p, sizeof(float) * m, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipStreamSynchronize(s));
-    return SCAL_OK;
+    const size_t m = static_cast<size_t>(src == NB_SELF ? c->n : n) * static_cast<size_t>(k);
+    int* d_idx;
+    float* d_d2;
+    SCAL_TRY(nb_out(c->d_kidx, src, idx, m, &d_idx));
+    SCAL_TRY(nb_out(c->d_kd2, src, d2, m, &d_d2));
+    const float4* qs;
+    int nq;
+    SCAL_TRY(nb_queries(c, src, xyzi, n, &qs, &nq));
+    SCAL_TRY(nb_run(c, nq, [&](hipStream_t s) -> int {
+        nb_list_class(k, [&](auto kc) {
+            SCAL_LAUNCH_PROF("k_nb_knn", k_nb_knn<decltype(kc)::value>, dim3(div_up(nq, 64)), dim3(64), 0, s, qs, nq, k, c->inv, c->r2, c->hkeys.p,
+                             c->hrange.p, c->hmask, c->sorted.p, d_idx, d_d2, c->d_stats.p);
+        });
+        return SCAL_OK;
+    }));
+    return nb_download(c, src, m, idx, d_idx, d2, d_d2);
 }
 
 extern "C" int scal_nbr_knn(scal_nbr_t* c, const float* xyzi, int n, int k, int* idx, float* d2) {
-    SCAL_TRY(nb_check_knn(c, "scal_nbr_knn", xyzi, n, k, false));
-    SCAL_HIP(hipSetDevice(c->cfg.device));
-    SCAL_TRY(nb_grow(c->d_kidx, idx != nullptr, n, k));
-    SCAL_TRY(nb_grow(c->d_kd2, d2 != nullptr, n, k));
-    if (!c->stage.p) SCAL_TRY(c->stage.alloc(static_cast<size_t>(c->cap)));
-    if (n > 0) SCAL_HIP(hipMemcpyAsync(c->stage.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, c->stream));
-    SCAL_TRY(nb_sort_queries(c, c->stage.p, n));
-    SCAL_TRY(nb_run_knn(c, c->qsorted.p, n, k, idx ? c->d_kidx.p : nullptr, d2 ? c->d_kd2.p : nullptr));
-    return nb_download_knn(c, n, k, idx, d2);
+    return nb_knn(c, "scal_nbr_knn", NB_HOST, xyzi, n, k, idx, d2);
 }
 
 extern "C" int scal_nbr_knn_device(scal_nbr_t* c, const float* d_xyzi, int n, int k, int* d_idx, float* d_d2) {
-    SCAL_TRY(nb_check_knn(c, "scal_nbr_knn_device", d_xyzi, n, k, false));
-    SCAL_HIP(hipSetDevice(c->cfg.device));
-    SCAL_TRY(nb_sort_queries(c, reinterpret_cast<const float4*>(d_xyzi), n));
-    return nb_run_knn(c, c->qsorted.p, n, k, d_idx, d_d2);
+    return nb_knn(c, "scal_nbr_knn_device", NB_DEVICE, d_xyzi, n, k, d_idx, d_d2);
 }
 
 extern "C" int scal_nbr_knn_self(scal_nbr_t* c, int k, int* idx, float* d2) {
-    SCAL_TRY(nb_check_knn(c, "scal_nbr_knn_self", nullptr, 0, k, true));
+    return nb_knn(c, "scal_nbr_knn_self", NB_SELF, nullptr, 0, k, idx, d2);
+}
+
+// nc and dist are staged in cap entries each, allocated when first asked for.  The position table's allocation and fill are part of
+// the launcher, so a call without queries allocates nothing; they come after nb_run has queued the counters' memset, which is
+// harmless: the same stream, and a failed allocation leaves only zeroed counters behind.
+static int nb_normals(scal_nbr* c, const char* who, NbSource src, const float* xyzi, int n, int k, const double* vp, float* nc, float* dist) {
+    SCAL_TRY(nb_check(c, who, src, xyzi, n, 3, k));
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    SCAL_TRY(nb_grow(c->d_kidx, idx != nullptr, c->n, k));
-    SCAL_TRY(nb_grow(c->d_kd2, d2 != nullptr, c->n, k));
-    SCAL_TRY(nb_run_knn(c, c->sorted.p, c->n, k, idx ? c->d_kidx.p : nullptr, d2 ? c->d_kd2.p : nullptr));
-    return nb_download_knn(c, c->n, k, idx, d2);
-}
-
-// normal, curvature and plane distance of the nq queries at qs (cell order, output position in .w) -> d_nc [nq], d_dist [nq] (either may be null)
-static int nb_run_normals(scal_nbr* c, const float4* qs, int nq, int k, const double* vp, float4* d_nc, float* d_dist) {
-    hipStream_t s = c->stream;
-    c->pairs = 0, c->work_items = 0;
-    if (nq == 0) return SCAL_OK;
-    if (!c->slot_of.p) SCAL_TRY(c->slot_of.alloc(static_cast<size_t>(c->cfg.max_index_points)));
-    if (!c->slots_ok && c->n > 0) {  // from the index's own copy of the records: the caller's are not needed
-        SCAL_LAUNCH_PROF("k_nb_slots", k_nb_slots, dim3(div_up(c->n, 256)), dim3(256), 0, s, c->sorted.p, c->n, c->slot_of.p);
-        SCAL_HIP(hipGetLastError());
-    }
-    c->slots_ok = true;
-    SCAL_HIP(hipMemsetAsync(c->d_stats.p, 0, 2 * sizeof(unsigned long long), s));
-    const dim3 grid(div_up(nq, 64)), block(64);
-    const int use_vp = vp != nullptr;
-    const double vx = vp ? vp[0] : 0.0, vy = vp ? vp[1] : 0.0, vz = vp ? vp[2] : 0.0;
-#define NB_NORMALS(KC)                                                                                                                   \
-    SCAL_LAUNCH_PROF("k_nb_normals", k_nb_normals<KC>, grid, block, 0, s, qs, nq, k, c->inv, c->r2, c->hkeys.p, c->hrange.p, c->hmask, \
-                     c->sorted.p, c->slot_of.p, use_vp, vx, vy, vz, d_nc, d_dist, c->d_stats.p)
-    if (k <= 8) NB_NORMALS(8);
-    else if (k <= 16) NB_NORMALS(16);
-    else if (k <= 32) NB_NORMALS(32);
-    else NB_NORMALS(64);
-#undef NB_NORMALS
-    SCAL_HIP(hipGetLastError());
-    unsigned long long st[2] = {0, 0};
-    SCAL_HIP(hipMemcpyAsync(st, c->d_stats.p, sizeof st, hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipStreamSynchronize(s));
-    c->pairs = static_cast<long long>(st[0]), c->work_items = static_cast<int>(std::min<unsigned long long>(st[1], 0x7fffffffull));
-    return SCAL_OK;
-}
-
-static int nb_check_normals(scal_nbr* c, const char* who, const float* xyzi, int n, int k, bool self) {
-    if (!c || (!self && (n < 0 || (n > 0 && !xyzi))) || k < 3 || k > SCAL_NBR_MAX_K) {
-        set_error("%s: bad argument (k is 3 .. %d)", who, SCAL_NBR_MAX_K);
-        return SCAL_E_ARG;
-    }
-    if (c->n < 0) {
-        set_error("%s: no index set", who);
-        return SCAL_E_STATE;
-    }
-    if (!self && n > c->cfg.max_query_points) {
-        set_error("%s: %d queries, max_query_points is %d", who, n, c->cfg.max_query_points);
-        return SCAL_E_CAPACITY;
-    }
-    return SCAL_OK;
-}
-
-// the host outputs' staging, cap entries each, on first use
-static int nb_stage_normals(scal_nbr* c, bool nc, bool dist) {
-    if (nc && !c->d_nc.p) SCAL_TRY(c->d_nc.alloc(static_cast<size_t>(c->cap)));
-    if (dist && !c->d_dist.p) SCAL_TRY(c->d_dist.alloc(static_cast<size_t>(c->cap)));
-    return SCAL_OK;
-}
-
-static int nb_download_normals(scal_nbr* c, int n, float* nc, float* dist) {
-    if (n == 0) return SCAL_OK;
-    hipStream_t s = c->stream;
-    if (nc) SCAL_HIP(hipMemcpyAsync(nc, c->d_nc.p, sizeof(float4) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
-    if (dist) SCAL_HIP(hipMemcpyAsync(dist, c->d_dist.p, sizeof(float) * static_cast<size_t>(n), hipMemcpyDeviceToHost, s));
-    SCAL_HIP(hipStreamSynchronize(s));
-    return SCAL_OK;
+    float4* const nc4 = reinterpret_cast<float4*>(nc);
+    float4* d_nc;
+    float* d_dist;
+    SCAL_TRY(nb_out(c->d_nc, src, nc4, static_cast<size_t>(c->cap), &d_nc));
+    SCAL_TRY(nb_out(c->d_dist, src, dist, static_cast<size_t>(c->cap), &d_dist));
+    const float4* qs;
+    int nq;
+    SCAL_TRY(nb_queries(c, src, xyzi, n, &qs, &nq));
+    SCAL_TRY(nb_run(c, nq, [&](hipStream_t s) -> int {
+        if (!c->slot_of.p) SCAL_TRY(c->slot_of.alloc(static_cast<size_t>(c->cfg.max_index_points)));
+        if (!c->slots_ok && c->n > 0) {  // from the index's own copy of the records: the caller's are not needed
+            SCAL_LAUNCH_PROF("k_nb_slots", k_nb_slots, dim3(div_up(c->n, 256)), dim3(256), 0, s, c->sorted.p, c->n, c->slot_of.p);
+            SCAL_HIP(hipGetLastError());
+        }
+        c->slots_ok = true;
+        const int use_vp = vp != nullptr;
+        const double vx = vp ? vp[0] : 0.0, vy = vp ? vp[1] : 0.0, vz = vp ? vp[2] : 0.0;
+        nb_list_class(k, [&](auto kc) {
+            SCAL_LAUNCH_PROF("k_nb_normals", k_nb_normals<decltype(kc)::value>, dim3(div_up(nq, 64)), dim3(64), 0, s, qs, nq, k, c->inv, c->r2,
+                             c->hkeys.p, c->hrange.p, c->hmask, c->sorted.p, c->slot_of.p, use_vp, vx, vy, vz, d_nc, d_dist, c->d_stats.p);
+        });
+        return SCAL_OK;
+    }));
+    return nb_download(c, src, static_cast<size_t>(nq), nc4, d_nc, dist, d_dist);
 }
 
 extern "C" int scal_nbr_normals(scal_nbr_t* c, const float* xyzi, int n, int k, const double* viewpoint3, float* nc, float* dist) {
-    SCAL_TRY(nb_check_normals(c, "scal_nbr_normals", xyzi, n, k, false));
-    SCAL_HIP(hipSetDevice(c->cfg.device));
-    SCAL_TRY(nb_stage_normals(c, nc != nullptr, dist != nullptr));
-    if (!c->stage.p) SCAL_TRY(c->stage.alloc(static_cast<size_t>(c->cap)));
-    if (n > 0) SCAL_HIP(hipMemcpyAsync(c->stage.p, xyzi, sizeof(float4) * static_cast<size_t>(n), hipMemcpyHostToDevice, c->stream));
-    SCAL_TRY(nb_sort_queries(c, c->stage.p, n));
-    SCAL_TRY(nb_run_normals(c, c->qsorted.p, n, k, viewpoint3, nc ? c->d_nc.p : nullptr, dist ? c->d_dist.p : nullptr));
-    return nb_download_normals(c, n, nc, dist);
+    return nb_normals(c, "scal_nbr_normals", NB_HOST, xyzi, n, k, viewpoint3, nc, dist);
 }
 
 extern "C" int scal_nbr_normals_device(scal_nbr_t* c, const float* d_xyzi, int n, int k, const double* viewpoint3, float* d_nc, float* d_dist) {
-    SCAL_TRY(nb_check_normals(c, "scal_nbr_normals_device", d_xyzi, n, k, false));
-    SCAL_HIP(hipSetDevice(c->cfg.device));
-    SCAL_TRY(nb_sort_queries(c, reinterpret_cast<const float4*>(d_xyzi), n));
-    return nb_run_normals(c, c->qsorted.p, n, k, viewpoint3, reinterpret_cast<float4*>(d_nc), d_dist);
+    return nb_normals(c, "scal_nbr_normals_device", NB_DEVICE, d_xyzi, n, k, viewpoint3, d_nc, d_dist);
 }
 
 extern "C" int scal_nbr_normals_self(scal_nbr_t* c, int k, const double* viewpoint3, float* nc, float* dist) {
-    SCAL_TRY(nb_check_normals(c, "scal_nbr_normals_self", nullptr, 0, k, true));
-    SCAL_HIP(hipSetDevice(c->cfg.device));
-    SCAL_TRY(nb_stage_normals(c, nc != nullptr, dist != nullptr));
-    SCAL_TRY(nb_run_normals(c, c->sorted.p, c->n, k, viewpoint3, nc ? c->d_nc.p : nullptr, dist ? c->d_dist.p : nullptr));
-    return nb_download_normals(c, c->n, nc, dist);
+    return nb_normals(c, "scal_nbr_normals_self", NB_SELF, nullptr, 0, k, viewpoint3, nc, dist);
 }
 
 extern "C" int scal_nbr_stats(scal_nbr_t* c, long long* pairs, int* work_items) {

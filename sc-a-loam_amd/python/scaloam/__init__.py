@@ -1218,60 +1218,62 @@ class RadiusIndex:
         _check(lib().scal_nbr_set_index_device(self.h, mapmerge.device_points(), n, float(r)))
         self.n = n
 
+    def _chunked(self, n, call):
+        """call(i, m) for every chunk [i, i + m) of n queries, at most max_query_points each (one empty chunk when n is 0); stats()
+        afterwards covers all chunks"""
+        pairs, items = 0, 0
+        for i in range(0, max(n, 1), self.max_query_points):
+            m = min(self.max_query_points, n - i)
+            _check(call(i, m))
+            st = self._stats()
+            pairs, items = pairs + st[0], items + st[1]
+        self._sum = (pairs, items)
+
+    def _single(self, rc):
+        """after a call that is not chunked (self and device queries): stats() is that call's"""
+        _check(rc)
+        self._sum = self._stats()
+
     def query(self, xyzi):
         """(count uint16 [n], min_d2 float32 [n]); stats() afterwards covers all chunks"""
         q = _f32(xyzi).reshape(-1, 4)
         n = q.shape[0]
         count, d2 = np.zeros(max(n, 1), np.uint16), np.zeros(max(n, 1), np.float32)
-        pairs, items = 0, 0
-        for i in range(0, max(n, 1), self.max_query_points):
-            m = min(self.max_query_points, n - i)
-            _check(lib().scal_nbr_query(self.h, _p(q[i:i + m], _f32p), m, _p(count[i:], C.POINTER(C.c_ushort)), _p(d2[i:], _f32p)))
-            st = self._stats()
-            pairs, items = pairs + st[0], items + st[1]
-        self._sum = (pairs, items)
+        self._chunked(n, lambda i, m: lib().scal_nbr_query(self.h, _p(q[i:i + m], _f32p), m, _p(count[i:], C.POINTER(C.c_ushort)), _p(d2[i:], _f32p)))
         return count[:n], d2[:n]
 
     def query_self(self):
         count, d2 = np.zeros(max(self.n, 1), np.uint16), np.zeros(max(self.n, 1), np.float32)
-        _check(lib().scal_nbr_query_self(self.h, _p(count, C.POINTER(C.c_ushort)), _p(d2, _f32p)))
-        self._sum = self._stats()
+        self._single(lib().scal_nbr_query_self(self.h, _p(count, C.POINTER(C.c_ushort)), _p(d2, _f32p)))
         return count[:self.n], d2[:self.n]
 
     def query_device(self, d_xyzi_ptr, n, d_count_ptr, d_min_d2_ptr):
         """queries and outputs in device memory (either output may be None); at most max_query_points"""
-        _check(lib().scal_nbr_query_device(self.h, d_xyzi_ptr, int(n), d_count_ptr, d_min_d2_ptr))
-        self._sum = self._stats()
+        self._single(lib().scal_nbr_query_device(self.h, d_xyzi_ptr, int(n), d_count_ptr, d_min_d2_ptr))
+
+    @staticmethod
+    def _rows(n, k):
+        kk = min(max(k, 1), NBR_MAX_K)   # the buffers' width; a k out of range is the library's to refuse
+        return np.zeros((max(n, 1), kk), np.int32), np.zeros((max(n, 1), kk), np.float32)
 
     def knn(self, xyzi, k):
         """(idx int32 [n, k], d2 float32 [n, k]): per query its k nearest index records within r by (d2, input position), padded with
         -1 / +inf; chunked by max_query_points, and stats() afterwards covers all chunks"""
         q = _f32(xyzi).reshape(-1, 4)
         n, k = q.shape[0], int(k)
-        kk = min(max(k, 1), NBR_MAX_K)   # the buffers' width; a k out of range is the library's to refuse
-        idx, d2 = np.zeros((max(n, 1), kk), np.int32), np.zeros((max(n, 1), kk), np.float32)
-        pairs, items = 0, 0
-        for i in range(0, max(n, 1), self.max_query_points):
-            m = min(self.max_query_points, n - i)
-            _check(lib().scal_nbr_knn(self.h, _p(q[i:i + m], _f32p), m, k, _p(idx[i:], _i32p), _p(d2[i:], _f32p)))
-            st = self._stats()
-            pairs, items = pairs + st[0], items + st[1]
-        self._sum = (pairs, items)
+        idx, d2 = self._rows(n, k)
+        self._chunked(n, lambda i, m: lib().scal_nbr_knn(self.h, _p(q[i:i + m], _f32p), m, k, _p(idx[i:], _i32p), _p(d2[i:], _f32p)))
         return idx[:n], d2[:n]
 
     def knn_self(self, k):
         """the index records as the queries, rows in the order the index was given in"""
-        k = int(k)
-        kk = min(max(k, 1), NBR_MAX_K)
-        idx, d2 = np.zeros((max(self.n, 1), kk), np.int32), np.zeros((max(self.n, 1), kk), np.float32)
-        _check(lib().scal_nbr_knn_self(self.h, k, _p(idx, _i32p), _p(d2, _f32p)))
-        self._sum = self._stats()
+        idx, d2 = self._rows(self.n, int(k))
+        self._single(lib().scal_nbr_knn_self(self.h, int(k), _p(idx, _i32p), _p(d2, _f32p)))
         return idx[:self.n], d2[:self.n]
 
     def knn_device(self, d_xyzi_ptr, n, k, d_idx_ptr, d_d2_ptr):
         """queries and the [n, k] outputs in device memory (either output may be None); at most max_query_points"""
-        _check(lib().scal_nbr_knn_device(self.h, d_xyzi_ptr, int(n), int(k), d_idx_ptr, d_d2_ptr))
-        self._sum = self._stats()
+        self._single(lib().scal_nbr_knn_device(self.h, d_xyzi_ptr, int(n), int(k), d_idx_ptr, d_d2_ptr))
 
     @staticmethod
     def _viewpoint(viewpoint):
@@ -1289,28 +1291,20 @@ class RadiusIndex:
         n, k = q.shape[0], int(k)
         nc, dist = np.zeros((max(n, 1), 4), np.float32), np.zeros(max(n, 1), np.float32)
         v, vptr = self._viewpoint(viewpoint)
-        pairs, items = 0, 0
-        for i in range(0, max(n, 1), self.max_query_points):
-            m = min(self.max_query_points, n - i)
-            _check(lib().scal_nbr_normals(self.h, _p(q[i:i + m], _f32p), m, k, vptr, _p(nc[i:], _f32p), _p(dist[i:], _f32p)))
-            st = self._stats()
-            pairs, items = pairs + st[0], items + st[1]
-        self._sum = (pairs, items)
+        self._chunked(n, lambda i, m: lib().scal_nbr_normals(self.h, _p(q[i:i + m], _f32p), m, k, vptr, _p(nc[i:], _f32p), _p(dist[i:], _f32p)))
         return nc[:n], dist[:n]
 
     def normals_self(self, k, viewpoint=None):
         """the index records as the queries, outputs in the order the index was given in"""
         nc, dist = np.zeros((max(self.n, 1), 4), np.float32), np.zeros(max(self.n, 1), np.float32)
         v, vptr = self._viewpoint(viewpoint)
-        _check(lib().scal_nbr_normals_self(self.h, int(k), vptr, _p(nc, _f32p), _p(dist, _f32p)))
-        self._sum = self._stats()
+        self._single(lib().scal_nbr_normals_self(self.h, int(k), vptr, _p(nc, _f32p), _p(dist, _f32p)))
         return nc[:self.n], dist[:self.n]
 
     def normals_device(self, d_xyzi_ptr, n, k, d_nc_ptr, d_dist_ptr, viewpoint=None):
         """queries and the [n, 4] / [n] outputs in device memory (either output may be None); at most max_query_points"""
         v, vptr = self._viewpoint(viewpoint)
-        _check(lib().scal_nbr_normals_device(self.h, d_xyzi_ptr, int(n), int(k), vptr, d_nc_ptr, d_dist_ptr))
-        self._sum = self._stats()
+        self._single(lib().scal_nbr_normals_device(self.h, d_xyzi_ptr, int(n), int(k), vptr, d_nc_ptr, d_dist_ptr))
 
     def _stats(self):
         pairs, items = C.c_longlong(0), C.c_int(0)
