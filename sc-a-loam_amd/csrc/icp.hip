@@ -16,8 +16,11 @@
 // The reference pays a kd-tree query per point and iteration on the CPU.  Here the target is bucketed into a cell grid once per
 // alignment and a wave per query searches it ring by ring (k_icp_grid_nn, exact); queries the grid cannot settle within three
 // rings fall back to the dense sweep of k_icp_nn, which is also the whole search when scal_icp_set_search(ctx, 0) asks for it.
+// The ring search, the dense tile, the 17 sums and the point transform are icp_dev.hpp's, shared with the multiview refine
+// (refine.hip), which is held to this file bit for bit; the kernels here say where a cell's points are and which point a thread owns.
 #include "common.hpp"
 #include "device_utils.hpp"
+#include "icp_dev.hpp"
 #include "icp_host.hpp"
 #include <cmath>
 #include <cstring>
@@ -25,63 +28,26 @@
 
 namespace scal {
 
-constexpr int ICP_QPT = 4;     // queries per thread
-constexpr int ICP_QT = 256 * ICP_QPT;  // queries per workgroup
-constexpr int ICP_TC = 2048;   // targets per workgroup
-constexpr int ICP_NSUM = 17;   // n, sum p[3], sum q[3], sum q p^T[9], sum d^2
-
 // qlist == nullptr: queries are cur[0 .. n_src); else the *d_nq queries qlist[] (the cell grid's unresolved ones; surplus
 // workgroups leave at once)
 __global__ void __launch_bounds__(256) k_icp_nn(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt, int n_tgt,
                                                 unsigned long long* __restrict__ best, const int* __restrict__ qlist,
                                                 const int* __restrict__ d_nq) {
-    __shared__ float4 st[ICP_TC];
     if (qlist) {
         n_src = *d_nq;
         if (static_cast<int>(blockIdx.x) * ICP_QT >= n_src) return;
     }
-    const int t0 = blockIdx.y * ICP_TC;
-    const int tn = min(ICP_TC, n_tgt - t0);
-    for (int i = threadIdx.x; i < tn; i += 256) st[i] = tgt[t0 + i];
-    __syncthreads();
-    // every thread owns ICP_QPT queries and walks the whole chunk: one LDS broadcast read feeds ICP_QPT distance evaluations
-    float qx[ICP_QPT], qy[ICP_QPT], qz[ICP_QPT], bd[ICP_QPT];
-    int bi[ICP_QPT], qid[ICP_QPT];
-#pragma unroll
-    for (int u = 0; u < ICP_QPT; ++u) {
-        const int qi = blockIdx.x * ICP_QT + u * 256 + threadIdx.x;
-        qid[u] = qi < n_src ? (qlist ? qlist[qi] : qi) : -1;
-        const float4 q = qid[u] >= 0 ? cur[qid[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
-        qx[u] = q.x, qy[u] = q.y, qz[u] = q.z, bd[u] = 3.4e38f, bi[u] = -1;
-    }
-#pragma unroll 2
-    for (int t = 0; t < tn; ++t) {
-        const float4 p = st[t];
-#pragma unroll
-        for (int u = 0; u < ICP_QPT; ++u) {
-            const float dx = qx[u] - p.x, dy = qy[u] - p.y, dz = qz[u] - p.z;
-            float d = dx * dx;  // FLANN L2_Simple<float>, the metric of pcl::KdTreeFLANN
-            d += dy * dy;
-            d += dz * dz;
-            if (d < bd[u]) bd[u] = d, bi[u] = t;  // ascending t: the lowest index of equal distances is kept
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < ICP_QPT; ++u) {
-        if (qid[u] >= 0 && bi[u] >= 0)
-            atomicMin(&best[qid[u]], (static_cast<unsigned long long>(__float_as_uint(bd[u])) << 32) | static_cast<unsigned>(t0 + bi[u]));
-    }
+    icp_dense_tile<false>(
+        cur, tgt, n_tgt, blockIdx.y * ICP_TC, blockIdx.x * ICP_QT, [&](int qi) { return qi < n_src ? (qlist ? qlist[qi] : qi) : -1; }, nullptr, nullptr,
+        best);
 }
 
 // ---- cell grid over the target (built once per alignment) ---------------------------------------------------------------------
 // Exact nearest neighbour without the dense sweep: target points bucketed into <= 2^18 cubic cells (counting sort, original
-// index kept beside each point); a wave per query examines the cube of cells around the query ring by ring.  After ring k every
-// unexamined point lies more than k cell widths away, so the search stops as soon as the best squared distance is below
-// ((k - 0.05) c)^2 (the margin covers the f32 cell assignment); keys are (f32 squared distance, original index) exactly as in the dense
-// sweep, so equal distances still resolve to the lowest index.  Queries with nothing that close within ICP_RINGS rings (far
-// outliers, a poor initial guess) go to the dense sweep as a list - the result is the same either way.
+// index kept beside each point); a wave per query examines the cube of cells around the query ring by ring (icp_ring_search has the
+// stop rule and the keys).  Queries with nothing close enough within ICP_RINGS rings (far outliers, a poor initial guess) go to the
+// dense sweep as a list - the result is the same either way.
 constexpr int ICP_NCELL = 1 << 18;
-constexpr int ICP_RINGS = 3;
 struct IcpGrid {
     float ox, oy, oz, cell, inv;
     int dx, dy, dz;
@@ -202,61 +168,21 @@ __global__ void __launch_bounds__(256) k_icp_grid_nn(const float4* __restrict__ 
     const int qi = blockIdx.x * 4 + wave_id();
     if (qi >= n_src) return;
     const IcpGrid g = *gp;
-    const int lane = lane_id();
     const float4 q = cur[qi];
     const int cx = icp_cell_coord(q.x, g.ox, g.inv), cy = icp_cell_coord(q.y, g.oy, g.inv), cz = icp_cell_coord(q.z, g.oz, g.inv);
-    unsigned long long bk = ~0ull;
-    bool done = false;
-    for (int k = 1; k <= ICP_RINGS && !done; ++k) {
-        const int w = 2 * k + 1, ncube = w * w * w;
-        for (int j0 = 0; j0 < ncube; j0 += 64) {  // 64 cells at a time, one per lane
-            const int j = j0 + lane;
-            int s0 = 0, cnt = 0;
-            if (j < ncube) {
-                const int jz = j / (w * w), rem = j - jz * w * w, jy = rem / w, jx = rem - jy * w;
-                const int ax = jx - k, ay = jy - k, az = jz - k;
-                const int x = cx + ax, y = cy + ay, z = cz + az;
-                const bool fresh = k == 1 || max(max(abs(ax), abs(ay)), abs(az)) == k;  // inner cells were examined in an earlier ring
-                if (fresh && static_cast<unsigned>(x) < static_cast<unsigned>(g.dx) && static_cast<unsigned>(y) < static_cast<unsigned>(g.dy) &&
-                    static_cast<unsigned>(z) < static_cast<unsigned>(g.dz)) {
-                    const int cell = (z * g.dy + y) * g.dx + x;
-                    s0 = start[cell];
-                    cnt = start[cell + 1] - s0;
-                }
+    unsigned long long bk;
+    const bool done = icp_ring_search(
+        q, cx, cy, cz, g.cell, sorted,
+        [&](int x, int y, int z, int& s0, int& cnt) {
+            if (static_cast<unsigned>(x) < static_cast<unsigned>(g.dx) && static_cast<unsigned>(y) < static_cast<unsigned>(g.dy) &&
+                static_cast<unsigned>(z) < static_cast<unsigned>(g.dz)) {
+                const int cell = (z * g.dy + y) * g.dx + x;
+                s0 = start[cell];
+                cnt = start[cell + 1] - s0;
             }
-            // the points of these cells as one list spread over the lanes: candidate t belongs to the lane whose running count
-            // first exceeds t (six-step search over the inclusive scan), so a crowded cell costs no lane more than an empty one
-            const int incl = wave_inclusive_scan(cnt);
-            const int total = __shfl(incl, 63, 64);
-            const int excl = incl - cnt;
-            for (int base = 0; base < total; base += 64) {
-                const int t = base + lane;
-                int owner = 0;
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1) {
-                    const int v = __shfl(incl, owner + step - 1, 64);
-                    if (v <= t) owner += step;
-                }
-                owner = min(owner, 63);
-                const int idx = __shfl(s0, owner, 64) + (t - __shfl(excl, owner, 64));
-                if (t < total) {
-                    const float4 p = sorted[idx];
-                    const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-                    float d = dx * dx;  // the dense sweep's arithmetic
-                    d += dy * dy;
-                    d += dz * dz;
-                    if (d < 3.4e38f) {
-                        const unsigned long long key = (static_cast<unsigned long long>(__float_as_uint(d)) << 32) | static_cast<unsigned>(__float_as_int(p.w));
-                        bk = key < bk ? key : bk;
-                    }
-                }
-            }
-        }
-        bk = wave_min_u64(bk);
-        const float bound = (static_cast<float>(k) - 0.05f) * g.cell;  // 0.05 cells: the f32 cell assignment of either point
-        done = bk != ~0ull && __uint_as_float(static_cast<unsigned>(bk >> 32)) < bound * bound;
-    }
-    if (lane == 0) {
+        },
+        [](int) { return true; }, bk);
+    if (lane_id() == 0) {
         if (done)
             best[qi] = bk;
         else
@@ -268,37 +194,9 @@ __global__ void __launch_bounds__(256) k_icp_grid_nn(const float4* __restrict__ 
 __global__ void __launch_bounds__(256) k_icp_reduce(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
                                                     unsigned long long* __restrict__ best, float max2, double* __restrict__ partials,
                                                     int* __restrict__ d_nun) {
-    __shared__ double red[4][ICP_NSUM];
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i == 0) *d_nun = 0;  // the cell grid's unresolved-query list is consumed by now
-    double v[ICP_NSUM];
-#pragma unroll
-    for (int k = 0; k < ICP_NSUM; ++k) v[k] = 0.0;
-    if (i < n_src) {
-        const unsigned long long key = best[i];
-        best[i] = ~0ull;
-        const float d = __uint_as_float(static_cast<unsigned>(key >> 32));
-        if (key != ~0ull && !(d > max2)) {
-            const float4 p = cur[i];
-            const float4 q = tgt[static_cast<unsigned>(key & 0xffffffffu)];
-            v[0] = 1.0;
-            v[1] = p.x, v[2] = p.y, v[3] = p.z;
-            v[4] = q.x, v[5] = q.y, v[6] = q.z;
-            const double qq[3] = {q.x, q.y, q.z}, pp[3] = {p.x, p.y, p.z};
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[7 + 3 * r + c] = qq[r] * pp[c];
-            v[16] = d;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < ICP_NSUM; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane_id() == 0) red[wave_id()][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < ICP_NSUM) partials[blockIdx.x * ICP_NSUM + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    icp_corr_sums(cur, tgt, best, max2, i, i < n_src, partials + static_cast<size_t>(blockIdx.x) * ICP_NSUM);
 }
 
 // sums the workgroup partials in workgroup order and hands them to the host (pinned, device-visible memory)
@@ -313,16 +211,11 @@ __global__ void __launch_bounds__(64) k_icp_final(const double* __restrict__ par
 struct Mat34f {
     float m[12];
 };
-__global__ void __launch_bounds__(256) k_icp_apply(const float4* __restrict__ in, float4* __restrict__ out, int n, Mat34f T) {
+// in and out may be the same array (the working copy moved in place): neither is __restrict__
+__global__ void __launch_bounds__(256) k_icp_apply(const float4* in, float4* out, int n, Mat34f T) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float4 p = in[i];
-    float4 o;
-    o.x = ((T.m[0] * p.x + T.m[1] * p.y) + T.m[2] * p.z) + T.m[3];
-    o.y = ((T.m[4] * p.x + T.m[5] * p.y) + T.m[6] * p.z) + T.m[7];
-    o.z = ((T.m[8] * p.x + T.m[9] * p.y) + T.m[10] * p.z) + T.m[11];
-    o.w = p.w;
-    out[i] = o;
+    out[i] = icp_transform(T.m, in[i]);
 }
 
 __global__ void k_icp_fill(unsigned long long* __restrict__ best, int n) {

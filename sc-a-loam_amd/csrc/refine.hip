@@ -9,20 +9,21 @@
 //   k_rf_index                points stay in index order), the cells' [start, end) ranges behind an open-addressing hash table in
 //                             HBM.  The cell width does not depend on the map's extent, as icp.hip's dense 2^18-cell grid does.
 // Per iteration, ONE launch chain for all frames still iterating and one host synchronisation:
-//   k_rf_apply    last iteration's increments, one 3x4 matrix per frame
-//   k_rf_grid_nn  a wave per source point: the cube of cells around it ring by ring, candidates spread over the lanes, key
-//                 (f32 d^2 bits << 32) | index, stop rule best < ((k - 0.05) cell)^2 - k_icp_grid_nn's search; a candidate of the
-//                 query's own frame is dropped before the key is formed
+//   k_rf_apply    last iteration's increments, one 3x4 matrix per frame (icp_transform)
+//   k_rf_grid_nn  a wave per source point: icp_ring_search with the cells looked up through the hash table (ch_find); a candidate of
+//                 the query's own frame is dropped before the key is formed
 //   k_rf_dense    only when max_corr_dist reaches beyond the last ring: the unsettled queries as a list against all of G, a fixed
-//                 number of workgroups striding over (query tile, target chunk) pairs - none when the list is empty
-//   k_rf_reduce   the 17 correspondence sums per workgroup of 256 source points COUNTED FROM THE FRAME'S FIRST POINT, wave_sum, then
-//   k_rf_final    ((r0+r1)+r2)+r3, then the frame's workgroup partials in workgroup order -> pinned [K][17]: the additions of
-//                 k_icp_reduce / k_icp_final on that frame alone, in their order
+//                 number of workgroups striding over (query tile, target chunk) pairs (icp_dense_tile) - none when the list is empty
+//   k_rf_reduce   icp_corr_sums per workgroup of 256 source points COUNTED FROM THE FRAME'S FIRST POINT, then
+//   k_rf_final    the frame's workgroup partials in workgroup order -> pinned [K][17]: the additions of k_icp_reduce / k_icp_final on
+//                 that frame alone, in their order
 //   host          icp_host_step (icp_host.hpp, shared with icp.hip) per frame; K 3x4 increments and the active mask go back in one copy
-// Frames that have finished cost an early return per workgroup.
+// Frames that have finished cost an early return per workgroup.  The search, the sums and the transform are icp_dev.hpp's, the same
+// code icp.hip runs: what is written here is where a cell's points are, which candidates count and which point a thread owns.
 #include "common.hpp"
 #include "cellhash_dev.hpp"
 #include "device_utils.hpp"
+#include "icp_dev.hpp"
 #include "icp_host.hpp"
 #include "mapmerge_dev.hpp"
 #include "radix_sort.hpp"
@@ -34,10 +35,7 @@
 
 namespace scal {
 
-constexpr int RF_NSUM = 17;        // n, sum p[3], sum q[3], sum q p^T[9], sum d^2
-constexpr int RF_RINGS = 3;        // as ICP_RINGS
 constexpr float RF_CELL = 1.0f;    // cell width in metres; cell coordinate = floor(v), exact in f32
-constexpr int RF_QT = 1024, RF_TC = 2048, RF_QPT = 4;  // dense sweep: queries / targets per work item, queries per thread
 constexpr int RF_DENSE_WG = 2048;  // workgroups of the dense sweep
 // cell coordinates: 17 bits in x and y (+-65 km), 14 in z (+-8 km), clamped beyond.  Clamping is monotone, so a cell that the ring
 // search has not examined is still at least k cells away from the query along some axis and the stop rule holds out there too.
@@ -94,38 +92,17 @@ __global__ void __launch_bounds__(256) k_rf_index(const unsigned long long* __re
     ch_insert(hkeys, hrange, mask, key, i, head, tail);
 }
 
-__global__ void __launch_bounds__(256) k_rf_apply(float4* __restrict__ cur, const RfBlock* __restrict__ blocks, const RfCtrl* __restrict__ ctrl) {
+// a frame's 3x4 matrix applied to its points: last iteration's increment to the sources in place (in == out), or the whole
+// transformation to the moved frame itself for the fitness sweep (in = G); neither pointer is __restrict__
+__global__ void __launch_bounds__(256) k_rf_apply(const float4* in, float4* out, const RfBlock* __restrict__ blocks, const RfCtrl* __restrict__ ctrl) {
     const RfBlock b = blocks[blockIdx.x];
     if (!ctrl[b.frame].active) return;
     const int i = b.first + threadIdx.x;
     if (i >= b.end) return;
-    const float* m = ctrl[b.frame].m;
-    const float4 p = cur[i];
-    float4 o;  // k_icp_apply's order
-    o.x = ((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3];
-    o.y = ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7];
-    o.z = ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11];
-    o.w = p.w;
-    cur[i] = o;
-}
-// the fitness sweep's sources: the moved frame itself (g) by the whole transformation
-__global__ void __launch_bounds__(256) k_rf_apply_from(const float4* __restrict__ g, float4* __restrict__ cur, const RfBlock* __restrict__ blocks,
-                                                       const RfCtrl* __restrict__ ctrl) {
-    const RfBlock b = blocks[blockIdx.x];
-    if (!ctrl[b.frame].active) return;
-    const int i = b.first + threadIdx.x;
-    if (i >= b.end) return;
-    const float* m = ctrl[b.frame].m;
-    const float4 p = g[i];
-    float4 o;
-    o.x = ((m[0] * p.x + m[1] * p.y) + m[2] * p.z) + m[3];
-    o.y = ((m[4] * p.x + m[5] * p.y) + m[6] * p.z) + m[7];
-    o.z = ((m[8] * p.x + m[9] * p.y) + m[10] * p.z) + m[11];
-    o.w = p.w;
-    cur[i] = o;
+    out[i] = icp_transform(ctrl[b.frame].m, in[i]);
 }
 
-// one wave per query (k_icp_grid_nn with the cell looked up through the hash table and the query's own frame left out)
+// one wave per query: icp_dev.hpp's ring search with the cell looked up through the hash table and the query's own frame left out
 __global__ void __launch_bounds__(256) k_rf_grid_nn(const float4* __restrict__ cur, int n, const int* __restrict__ frame_of, const int* __restrict__ goff,
                                                     const RfCtrl* __restrict__ ctrl, const unsigned long long* __restrict__ hkeys,
                                                     const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
@@ -136,70 +113,17 @@ __global__ void __launch_bounds__(256) k_rf_grid_nn(const float4* __restrict__ c
     const int frame = frame_of[qi];
     if (!ctrl[frame].active) return;
     const int own0 = goff[frame], own_n = goff[frame + 1] - own0;  // the frame's points are one index range of G
-    const int lane = lane_id();
     const float4 q = cur[qi];
-    const int cx = rf_coord(q.x, RF_XB), cy = rf_coord(q.y, RF_XB), cz = rf_coord(q.z, RF_ZB);
-    unsigned long long bk = ~0ull;
-    bool done = false;
-    for (int k = 1; k <= RF_RINGS && !done; ++k) {
-        const int w = 2 * k + 1, ncube = w * w * w;
-        for (int j0 = 0; j0 < ncube; j0 += 64) {  // 64 cells at a time, one per lane
-            const int j = j0 + lane;
-            int s0 = 0, cnt = 0;
-            if (j < ncube) {
-                const int jz = j / (w * w), rem = j - jz * w * w, jy = rem / w, jx = rem - jy * w;
-                const int ax = jx - k, ay = jy - k, az = jz - k;
-                const bool fresh = k == 1 || max(max(abs(ax), abs(ay)), abs(az)) == k;  // inner cells were examined in an earlier ring
-                const unsigned long long key = fresh ? rf_key(cx + ax, cy + ay, cz + az) : RF_NO_CELL;
-                if (key != RF_NO_CELL) {
-                    unsigned slot = ch_slot(key, mask);
-                    for (;;) {
-                        const unsigned long long hk = hkeys[slot];
-                        if (hk == key) {
-                            const int2 r = hrange[slot];
-                            s0 = r.x, cnt = r.y - r.x;
-                            break;
-                        }
-                        if (hk == CH_EMPTY) break;
-                        slot = (slot + 1) & mask;
-                    }
-                }
-            }
-            // the points of these cells as one list spread over the lanes (k_icp_grid_nn)
-            const int incl = wave_inclusive_scan(cnt);
-            const int total = __shfl(incl, 63, 64);
-            const int excl = incl - cnt;
-            for (int base = 0; base < total; base += 64) {
-                const int t = base + lane;
-                int owner = 0;
-#pragma unroll
-                for (int step = 32; step > 0; step >>= 1) {
-                    const int v = __shfl(incl, owner + step - 1, 64);
-                    if (v <= t) owner += step;
-                }
-                owner = min(owner, 63);
-                const int idx = __shfl(s0, owner, 64) + (t - __shfl(excl, owner, 64));
-                if (t < total) {
-                    const float4 p = sorted[idx];
-                    const int ti = __float_as_int(p.w);
-                    if (static_cast<unsigned>(ti - own0) >= static_cast<unsigned>(own_n)) {  // not of the query's own frame
-                        const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-                        float d = dx * dx;  // the dense sweep's arithmetic
-                        d += dy * dy;
-                        d += dz * dz;
-                        if (d < 3.4e38f) {
-                            const unsigned long long key = (static_cast<unsigned long long>(__float_as_uint(d)) << 32) | static_cast<unsigned>(ti);
-                            bk = key < bk ? key : bk;
-                        }
-                    }
-                }
-            }
-        }
-        bk = wave_min_u64(bk);
-        const float bound = (static_cast<float>(k) - 0.05f) * RF_CELL;
-        done = bk != ~0ull && __uint_as_float(static_cast<unsigned>(bk >> 32)) < bound * bound;
-    }
-    if (lane == 0) {
+    unsigned long long bk;
+    const bool done = icp_ring_search(
+        q, rf_coord(q.x, RF_XB), rf_coord(q.y, RF_XB), rf_coord(q.z, RF_ZB), RF_CELL, sorted,
+        [&](int x, int y, int z, int& s0, int& cnt) {
+            const unsigned long long key = rf_key(x, y, z);
+            int2 r;
+            if (key != RF_NO_CELL && ch_find(hkeys, hrange, mask, key, r)) s0 = r.x, cnt = r.y - r.x;
+        },
+        [&](int ti) { return static_cast<unsigned>(ti - own0) >= static_cast<unsigned>(own_n); }, bk);
+    if (lane_id() == 0) {
         if (done)
             best[qi] = bk;
         else if (keep_unresolved)  // else: nothing within the last ring's bound, and max_corr_dist does not reach beyond it
@@ -207,90 +131,29 @@ __global__ void __launch_bounds__(256) k_rf_grid_nn(const float4* __restrict__ c
     }
 }
 
-// exact nearest neighbour of the *d_nq listed queries among all of G but their own frame (k_icp_nn's sweep and keys); the
-// workgroups stride over the (query tile, target chunk) pairs, so an empty list costs RF_DENSE_WG early returns
+// exact nearest neighbour of the *d_nq listed queries among all of G but their own frame; the workgroups stride over the
+// (query tile, target chunk) pairs, so an empty list costs RF_DENSE_WG early returns
 __global__ void __launch_bounds__(256) k_rf_dense(const float4* __restrict__ cur, const float4* __restrict__ tgt, int n_tgt, const int* __restrict__ frame_of,
                                                   const int* __restrict__ goff, unsigned long long* __restrict__ best, const int* __restrict__ qlist,
                                                   const int* __restrict__ d_nq) {
-    __shared__ float4 st[RF_TC];
     const int nq = *d_nq;
     if (nq == 0) return;
-    const long long n_qt = (nq + RF_QT - 1) / RF_QT, n_tc = (n_tgt + RF_TC - 1) / RF_TC;
+    const long long n_qt = (nq + ICP_QT - 1) / ICP_QT, n_tc = (n_tgt + ICP_TC - 1) / ICP_TC;
     for (long long w = blockIdx.x; w < n_qt * n_tc; w += gridDim.x) {
-        const int qt = static_cast<int>(w / n_tc), t0 = static_cast<int>(w % n_tc) * RF_TC;
-        const int tn = min(RF_TC, n_tgt - t0);
+        const int q0 = static_cast<int>(w / n_tc) * ICP_QT, t0 = static_cast<int>(w % n_tc) * ICP_TC;
         __syncthreads();  // the previous pair's chunk has been read
-        for (int i = threadIdx.x; i < tn; i += 256) st[i] = tgt[t0 + i];
-        __syncthreads();
-        float qx[RF_QPT], qy[RF_QPT], qz[RF_QPT], bd[RF_QPT];
-        int bi[RF_QPT], qid[RF_QPT], own0[RF_QPT];
-        unsigned own_n[RF_QPT];
-#pragma unroll
-        for (int u = 0; u < RF_QPT; ++u) {
-            const int qi = qt * RF_QT + u * 256 + threadIdx.x;
-            qid[u] = qi < nq ? qlist[qi] : -1;
-            const float4 q = qid[u] >= 0 ? cur[qid[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
-            const int f = qid[u] >= 0 ? frame_of[qid[u]] : 0;
-            own0[u] = goff[f] - t0, own_n[u] = qid[u] >= 0 ? static_cast<unsigned>(goff[f + 1] - goff[f]) : 0u;
-            qx[u] = q.x, qy[u] = q.y, qz[u] = q.z, bd[u] = 3.4e38f, bi[u] = -1;
-        }
-#pragma unroll 2
-        for (int t = 0; t < tn; ++t) {
-            const float4 p = st[t];
-#pragma unroll
-            for (int u = 0; u < RF_QPT; ++u) {
-                const float dx = qx[u] - p.x, dy = qy[u] - p.y, dz = qz[u] - p.z;
-                float d = dx * dx;  // FLANN L2_Simple<float>
-                d += dy * dy;
-                d += dz * dz;
-                // ascending t: the lowest index of equal distances is kept; own-frame points are no candidates
-                if (d < bd[u] && static_cast<unsigned>(t - own0[u]) >= own_n[u]) bd[u] = d, bi[u] = t;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < RF_QPT; ++u) {
-            if (qid[u] >= 0 && bi[u] >= 0)
-                atomicMin(&best[qid[u]], (static_cast<unsigned long long>(__float_as_uint(bd[u])) << 32) | static_cast<unsigned>(t0 + bi[u]));
-        }
+        icp_dense_tile<true>(cur, tgt, n_tgt, t0, q0, [&](int qi) { return qi < nq ? qlist[qi] : -1; }, frame_of, goff, best);
     }
 }
 
-// partial sums of one workgroup of 256 source points of one frame (k_icp_reduce's additions); resets the keys for the next sweep
+// partial sums of one workgroup of 256 source points of one frame; resets the keys for the next sweep
 __global__ void __launch_bounds__(256) k_rf_reduce(const float4* __restrict__ cur, const float4* __restrict__ tgt, const RfBlock* __restrict__ blocks,
                                                    const RfCtrl* __restrict__ ctrl, unsigned long long* __restrict__ best, float max2,
                                                    double* __restrict__ partials) {
-    __shared__ double red[4][RF_NSUM];
     const RfBlock b = blocks[blockIdx.x];
     if (!ctrl[b.frame].active) return;
     const int i = b.first + threadIdx.x;
-    double v[RF_NSUM];
-#pragma unroll
-    for (int k = 0; k < RF_NSUM; ++k) v[k] = 0.0;
-    if (i < b.end) {
-        const unsigned long long key = best[i];
-        best[i] = ~0ull;
-        const float d = __uint_as_float(static_cast<unsigned>(key >> 32));
-        if (key != ~0ull && !(d > max2)) {
-            const float4 p = cur[i];
-            const float4 q = tgt[static_cast<unsigned>(key & 0xffffffffu)];
-            v[0] = 1.0;
-            v[1] = p.x, v[2] = p.y, v[3] = p.z;
-            v[4] = q.x, v[5] = q.y, v[6] = q.z;
-            const double qq[3] = {q.x, q.y, q.z}, pp[3] = {p.x, p.y, p.z};
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[7 + 3 * r + c] = qq[r] * pp[c];
-            v[16] = d;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < RF_NSUM; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane_id() == 0) red[wave_id()][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < RF_NSUM) partials[static_cast<size_t>(blockIdx.x) * RF_NSUM + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    icp_corr_sums(cur, tgt, best, max2, i, i < b.end, partials + static_cast<size_t>(blockIdx.x) * ICP_NSUM);
 }
 
 // one workgroup per frame: its workgroup partials in workgroup order -> host_out[frame][17] (pinned, device-visible memory)
@@ -299,10 +162,10 @@ __global__ void __launch_bounds__(64) k_rf_final(const double* __restrict__ part
     if (blockIdx.x == 0 && threadIdx.x == 0) *d_nun = 0;  // the unresolved-query list is consumed by now
     const int f = blockIdx.x;
     if (!ctrl[f].active) return;
-    if (threadIdx.x < RF_NSUM) {
+    if (threadIdx.x < ICP_NSUM) {
         double s = 0.0;
-        for (int b = fb0[f]; b < fb0[f + 1]; ++b) s += partials[static_cast<size_t>(b) * RF_NSUM + threadIdx.x];
-        host_out[f * RF_NSUM + threadIdx.x] = s;
+        for (int b = fb0[f]; b < fb0[f + 1]; ++b) s += partials[static_cast<size_t>(b) * ICP_NSUM + threadIdx.x];
+        host_out[f * ICP_NSUM + threadIdx.x] = s;
     }
 }
 
@@ -358,10 +221,10 @@ int scal::refine_create_on_lane(const scal_refine_config* cfg, int lane, scal_re
     A(c->best.alloc(np)); A(c->keys.alloc(np)); A(c->vals.alloc(np)); A(c->hkeys.alloc(slots)); A(c->hrange.alloc(slots));
     A(c->sorter.init(cfg->max_points));
     A(c->mm_blocks.alloc(c->nb_mm_cap)); A(c->h_mm_blocks.alloc(c->nb_mm_cap)); A(c->blk.alloc(c->nb_mm_cap)); A(c->h_blk.alloc(c->nb_mm_cap));
-    A(c->poses.alloc(12 * nf)); A(c->h_poses.alloc(12 * nf)); A(c->partials.alloc(static_cast<size_t>(RF_NSUM) * c->nb_cap));
+    A(c->poses.alloc(12 * nf)); A(c->h_poses.alloc(12 * nf)); A(c->partials.alloc(static_cast<size_t>(ICP_NSUM) * c->nb_cap));
     A(c->blocks.alloc(c->nb_cap)); A(c->h_blocks.alloc(c->nb_cap));
     A(c->goff.alloc(nf + 1)); A(c->h_goff.alloc(nf + 1)); A(c->fb0.alloc(nf + 1)); A(c->h_fb0.alloc(nf + 1));
-    A(c->ctrl.alloc(nf)); A(c->h_ctrl.alloc(nf)); A(c->h_sums.alloc(RF_NSUM * nf));
+    A(c->ctrl.alloc(nf)); A(c->h_ctrl.alloc(nf)); A(c->h_sums.alloc(ICP_NSUM * nf));
     if (rc == SCAL_OK) rc = c->stream.acquire(cfg->device, lane);
     if (rc == SCAL_OK && (hipMemsetAsync(c->d_misc.p, 0, 2 * sizeof(int), c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = SCAL_E_HIP;
     if (rc != SCAL_OK) {
@@ -449,7 +312,7 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets
         for (int i = offsets[f]; i < offsets[f + 1]; i += MM_TILE) c->h_mm_blocks.p[nb_mm++] = MMBlock{i, offsets[f + 1], f};
     if (nb_mm) SCAL_HIP(hipMemcpyAsync(c->mm_blocks.p, c->h_mm_blocks.p, sizeof(MMBlock) * nb_mm, hipMemcpyHostToDevice, s));
     const float max2 = static_cast<float>(c->cfg.max_corr_dist * c->cfg.max_corr_dist);
-    const float last_bound = (static_cast<float>(RF_RINGS) - 0.05f) * RF_CELL;
+    const float last_bound = (static_cast<float>(ICP_RINGS) - 0.05f) * RF_CELL;
     // a query the rings leave unsettled has nothing nearer than last_bound: it only needs the dense sweep when the cap reaches further
     const bool dense = !(max2 < last_bound * last_bound);
     const double te = c->cfg.transformation_epsilon, fe = c->cfg.fitness_epsilon;
@@ -518,13 +381,13 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets
                 }
                 if (!go) break;
                 SCAL_HIP(hipMemcpyAsync(c->ctrl.p, c->h_ctrl.p, sizeof(RfCtrl) * K, hipMemcpyHostToDevice, s));
-                if (!first) hipLaunchKernelGGL(k_rf_apply, dim3(nb), dim3(256), 0, s, c->cur.p, c->blocks.p, c->ctrl.p);
+                if (!first) hipLaunchKernelGGL(k_rf_apply, dim3(nb), dim3(256), 0, s, c->cur.p, c->cur.p, c->blocks.p, c->ctrl.p);
                 first = false;
                 SCAL_TRY(refine_sweep(c, n, K, nb, max2, dense));
                 for (int f = 0; f < K; ++f) {
                     if (!fr[f].active) continue;
                     float T[16];
-                    const int step = icp_host_step(fr[f].is, c->h_sums.p + RF_NSUM * f, c->cfg.max_iterations, te, fe, T);
+                    const int step = icp_host_step(fr[f].is, c->h_sums.p + ICP_NSUM * f, c->cfg.max_iterations, te, fe, T);
                     if (step == ICP_STEP_CONTINUE)
                         std::memcpy(c->h_ctrl.p[f].m, T, sizeof(float) * 12);
                     else  // finished: the fitness sweep moves the frame by the whole transformation, the last increment need not be applied
@@ -537,7 +400,7 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets
                 std::memcpy(c->h_ctrl.p[f].m, fr[f].is.F, sizeof(float) * 12);
             }
             SCAL_HIP(hipMemcpyAsync(c->ctrl.p, c->h_ctrl.p, sizeof(RfCtrl) * K, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_rf_apply_from, dim3(nb), dim3(256), 0, s, c->g.p, c->cur.p, c->blocks.p, c->ctrl.p);
+            hipLaunchKernelGGL(k_rf_apply, dim3(nb), dim3(256), 0, s, c->g.p, c->cur.p, c->blocks.p, c->ctrl.p);
             SCAL_TRY(refine_sweep(c, n, K, nb, max2, dense));
         }
         // 5. results and poses
@@ -546,7 +409,7 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets
             scal_refine_frame_result& r = res[f];
             const IcpIterState& is = fr[f].is;
             r.converged = is.converged ? 1 : 0, r.iterations = is.it, r.state = is.st, r.n_correspondences = is.n_corr;
-            const double* sums = c->h_sums.p + RF_NSUM * f;
+            const double* sums = c->h_sums.p + ICP_NSUM * f;
             r.fitness = fr[f].runs && sums[0] > 0 ? sums[16] / sums[0] : dmax;
             for (int k = 0; k < 16; ++k) r.T[k] = is.F[k];
             r.accepted = fr[f].runs && is.converged && r.fitness <= c->cfg.fitness_gate ? 1 : 0;
