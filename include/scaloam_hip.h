@@ -466,6 +466,83 @@ int scal_icp_align_guess(scal_icp_t* ctx, const float* src_xyzi, int n_src, cons
 int scal_icp_align_guess_device(scal_icp_t* ctx, const float* d_src_xyzi, int n_src, const float* d_tgt_xyzi, int n_tgt, const float guess[16],
                                 scal_icp_result* res);
 
+/* ---- point-to-plane alignment on a scal_icp_t (an extension: the reference has no counterpart).
+ * The target carries one normal per point, tgt_nc [n_tgt][4] f32 in exactly the layout scal_nbr_normals* writes: normal, then
+ * curvature.  The curvature is ignored; the normal is used as stored, never re-normalised.  scal_icp_config, the search modes of
+ * scal_icp_set_search and the guess (its rules and error codes those of scal_icp_align_guess, NULL or the identity: none) are
+ * shared with the point-to-point calls, which are not changed by these.  The CPU restatement is scaloam/icp_plane.py; the device is
+ * held to it bit for bit, so THE ORDER OF THE OPERATIONS BELOW IS PART OF THE INTERFACE.
+ *
+ * Correspondences are exactly those of scal_icp_align: the nearest target point by the f32 key (d, index) - d the f32 squared
+ * distance dx dx + dy dy + dz dz summed left to right, the lowest index among equal d - within the cap `!(d > max2)`,
+ * max2 = (float)(max_corr_dist^2); a source or target point that is not finite takes no part.  A correspondence whose target normal
+ * has a component that is not finite (the NaN rows scal_nbr_normals writes for sparse neighbourhoods) is dropped: it still counts
+ * for `fitness` and for nothing else.
+ *
+ * One row per remaining correspondence, everything f64 promoted from the f32 values, one rounding per operation (no FMA).  p the
+ * moved source point, q the target point, n its normal:
+ *     c0 = p.y n.z - p.z n.y,  c1 = p.z n.x - p.x n.z,  c2 = p.x n.y - p.y n.x          (c = p x n)
+ *     a  = (c0, c1, c2, n.x, n.y, n.z)
+ *     r  = ((q.x - p.x) n.x + (q.y - p.y) n.y) + (q.z - p.z) n.z
+ * and the sweep minimises sum (a.x - r)^2 over x = (alpha, beta, gamma, tx, ty, tz).
+ *
+ * 32 sums per sweep (SCAL_ICP_PLANE_NSUM):
+ *     [0]       number of rows (within the cap, finite normal)
+ *     [1..21]   sum a_i a_j, i <= j, row-major: (0,0) (0,1) .. (0,5) (1,1) .. (5,5)
+ *     [22..27]  sum a_i r
+ *     [28]      sum r r
+ *     [29]      sum d over the rows (d the f32 squared distance)
+ *     [30]      number of source points with any nearest neighbour (no cap, no normal test)
+ *     [31]      sum d over those
+ * Source point i is lane i % 64 of wave (i / 64) % 4 of workgroup i / 256; a point without a term adds +0.  Every sum is reduced in
+ * the order of the point-to-point sums: the 64 lanes of a wave by the xor butterfly v += v[lane ^ o] for o = 32, 16, 8, 4, 2, 1;
+ * the four waves as ((r0 + r1) + r2) + r3; the workgroups sequentially, in workgroup order, from +0.
+ *
+ * Host step on the sums.  Fewer than 6 rows ([0] < 6): state 5, no increment.  Otherwise the 6x6 system A x = b (A from [1..21],
+ * b from [22..27]) is solved by LDL^T without pivoting, in this order:
+ *     for j = 0 .. 5:
+ *         v_k = L_jk D_k                                       for k < j
+ *         d   = A_jj;  d = d - L_jk v_k                        for k = 0 .. j-1 ascending
+ *         degenerate unless  d > SCAL_ICP_PLANE_PIVOT_MIN A_jj
+ *         D_j = d
+ *         s = A_ij;  s = s - L_ik v_k  (k ascending);  L_ij = s / d        for i = j+1 .. 5
+ *     y_i = b_i;  y_i = y_i - L_ik y_k  (k = 0 .. i-1 ascending)           for i = 0 .. 5
+ *     z_i = y_i / D_i
+ *     x_i = z_i;  x_i = x_i - L_ki x_k  (k = i+1 .. 5 ascending)           for i = 5 .. 0
+ * A degenerate system (one plane, two planes, a line: the data do not fix all six freedoms) is state 6: not converged, no
+ * increment, T keeps what has accumulated.  SCAL_ICP_PLANE_PIVOT_MIN is a setting, not a measurement: exactly singular systems
+ * show pivot ratios d / A_jj of 0, -1.6e-16 or an A_jj of 0, three orthogonal planes 0.25, a pair of thinned street keyframes 0.87.
+ *
+ * The increment, without trigonometric functions: h = (alpha / 2, beta / 2, gamma / 2), m = sqrt(((1 + hx hx) + hy hy) + hz hz),
+ * the unit quaternion (w, x, y, z) = (1 / m, hx / m, hy / m, hz / m), the rotation
+ *     1 - 2 (y y + z z)    2 (x y - z w)        2 (x z + y w)
+ *     2 (x y + z w)        1 - 2 (x x + z z)    2 (y z - x w)
+ *     2 (x z - y w)        2 (y z + x w)        1 - 2 (x x + y y)
+ * and the translation (tx, ty, tz), all stored as f32.  It is applied to the working cloud and taken up as F = T F in the f32
+ * arithmetic of scal_icp_align, and the convergence criteria and states 1 - 4 are scal_icp_align's with mse = [29] / [0].
+ *
+ * The final sweep moves the ORIGINAL source by the final T and sums with the same cap: fitness = [31] / [30] (uncapped, the value
+ * scal_icp_result::fitness has for this T, so the reference's 0.3 gate stays comparable), plane_fitness = [28] / [0],
+ * normal_eq = [1..27].  first_eq = [1..27] of the first sweep (the source as given, or moved by the guess). */
+#define SCAL_ICP_PLANE_NSUM 32
+#define SCAL_ICP_PLANE_PIVOT_MIN 1e-10
+typedef struct {
+    int converged, iterations, state, n_correspondences; /* as scal_icp_result; n_correspondences counts rows; state 6: degenerate normal equations */
+    double fitness;       /* as scal_icp_result: uncapped mean d of the ORIGINAL source moved by T; DBL_MAX without a neighbour */
+    double plane_fitness; /* mean r^2 over the final sweep's rows; DBL_MAX without one */
+    double T[16];         /* row-major, f32 values, guess included */
+    double normal_eq[27]; /* upper triangle of A^T A (21, row-major) and A^T b (6) of the FINAL sweep: the 6x6 information of the alignment */
+    double first_eq[27];  /* the same of the FIRST sweep */
+} scal_icp_plane_result;
+/* xyzi host records and host normals.  Empty clouds: state 5, T the identity.  SCAL_E_ARG / SCAL_E_TOO_MANY as scal_icp_align for
+ * the same arguments (tgt_nc == NULL with n_tgt > 0 is SCAL_E_ARG); the context stays usable.  The first plane call on a context
+ * allocates what only these calls need (normals staging, 32-wide partials, pinned sums); they are released with the context. */
+int scal_icp_align_plane(scal_icp_t* ctx, const float* src_xyzi, int n_src, const float* tgt_xyzi, const float* tgt_nc, int n_tgt,
+                         const float guess[16], scal_icp_plane_result* res);
+/* all three arrays already in HBM; target and normals are read in place and must stay valid until the call returns */
+int scal_icp_align_plane_device(scal_icp_t* ctx, const float* d_src_xyzi, int n_src, const float* d_tgt_xyzi, const float* d_tgt_nc, int n_tgt,
+                                const float guess[16], scal_icp_plane_result* res);
+
 /* ------------------------------------------------------------------ multiview refine (BASELINE.json config #5, "global ICP refine")
  * An extension: the reference has no counterpart.  All K keyframes of a session are aligned at once, in Jacobi rounds.  One round:
  *  1. every frame f is moved by its pose with the map merge's arithmetic and near-range rule (the bits of a one-frame

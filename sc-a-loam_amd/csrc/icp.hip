@@ -18,6 +18,10 @@
 // rings fall back to the dense sweep of k_icp_nn, which is also the whole search when scal_icp_set_search(ctx, 0) asks for it.
 // The ring search, the dense tile, the 17 sums and the point transform are icp_dev.hpp's, shared with the multiview refine
 // (refine.hip), which is held to this file bit for bit; the kernels here say where a cell's points are and which point a thread owns.
+//
+// scal_icp_align_plane* (an extension, include/scaloam_hip.h and DESIGN.md section 8.14) is the same alignment with a point-to-plane
+// metric on the target's normals: the search is untouched, k_icp_plane_reduce (icp_plane_sums: one f64 row per correspondence, 32
+// sums) stands in for k_icp_reduce and icp_plane_host_step (LDL^T of the 6x6 normal equations) for icp_host_step.
 #include "common.hpp"
 #include "device_utils.hpp"
 #include "icp_dev.hpp"
@@ -199,11 +203,21 @@ __global__ void __launch_bounds__(256) k_icp_reduce(const float4* __restrict__ c
     icp_corr_sums(cur, tgt, best, max2, i, i < n_src, partials + static_cast<size_t>(blockIdx.x) * ICP_NSUM);
 }
 
-// sums the workgroup partials in workgroup order and hands them to the host (pinned, device-visible memory)
+// the same for the 32 point-to-plane sums (scal_icp_align_plane); nc: the target's normals
+__global__ void __launch_bounds__(256) k_icp_plane_reduce(const float4* __restrict__ cur, int n_src, const float4* __restrict__ tgt,
+                                                          const float4* __restrict__ nc, unsigned long long* __restrict__ best, float max2,
+                                                          double* __restrict__ partials, int* __restrict__ d_nun) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *d_nun = 0;
+    icp_plane_sums(cur, tgt, nc, best, max2, i, i < n_src, partials + static_cast<size_t>(blockIdx.x) * ICP_PLANE_NSUM);
+}
+
+// sums the workgroup partials (NS to a workgroup) in workgroup order and hands them to the host (pinned, device-visible memory)
+template <int NS>
 __global__ void __launch_bounds__(64) k_icp_final(const double* __restrict__ partials, int nb, double* __restrict__ host_out) {
-    if (threadIdx.x < ICP_NSUM) {
+    if (threadIdx.x < NS) {
         double s = 0.0;
-        for (int b = 0; b < nb; ++b) s += partials[b * ICP_NSUM + threadIdx.x];
+        for (int b = 0; b < nb; ++b) s += partials[b * NS + threadIdx.x];
         host_out[threadIdx.x] = s;
     }
 }
@@ -242,6 +256,10 @@ struct scal_icp {
     DevBuf<unsigned> mm;
     DevBuf<int> count, start, bsum, cell_of, un_list, d_nun;
     DevBuf<float4> sorted;
+    // point-to-plane: allocated by the first scal_icp_align_plane* call (the normals staging by the first with host arrays)
+    DevBuf<float4> nc;
+    DevBuf<double> plane_partials;
+    PinBuf<double> h_plane;
 };
 
 extern "C" int scal_icp_create(const scal_icp_config* cfg, scal_icp_t** out) { return icp_create_on_lane(cfg, 0, out); }
@@ -294,8 +312,9 @@ extern "C" void scal_icp_destroy(scal_icp_t* c) {
     delete c;
 }
 
-// one correspondence sweep of `pts` against the target: sums -> c->h_sums (waits)
-static int icp_sweep(scal_icp* c, const float4* pts, int n_src, int n_tgt, float max2) {
+// one correspondence sweep of `pts` against the target: sums -> c->h_sums (waits); nc != nullptr: the target's normals, the 32
+// point-to-plane sums -> c->h_plane instead
+static int icp_sweep(scal_icp* c, const float4* pts, int n_src, int n_tgt, float max2, const float4* nc = nullptr) {
     hipStream_t s = c->stream;
     const int nb = div_up(n_src, 256);
     const int* no_list = nullptr;
@@ -308,44 +327,74 @@ static int icp_sweep(scal_icp* c, const float4* pts, int n_src, int n_tgt, float
         SCAL_LAUNCH_PROF("k_icp_nn", k_icp_nn, dim3(div_up(n_src, ICP_QT), div_up(n_tgt, ICP_TC)), dim3(256), 0, s, pts, n_src, c->tgt_cur, n_tgt,
                          c->best.p, no_list, no_list);
     }
-    hipLaunchKernelGGL(k_icp_reduce, dim3(nb), dim3(256), 0, s, pts, n_src, c->tgt_cur, c->best.p, max2, c->partials.p, c->d_nun.p);
-    hipLaunchKernelGGL(k_icp_final, dim3(1), dim3(64), 0, s, c->partials.p, nb, c->h_sums.p);
+    if (nc) {
+        SCAL_LAUNCH_PROF("k_icp_plane_reduce", k_icp_plane_reduce, dim3(nb), dim3(256), 0, s, pts, n_src, c->tgt_cur, nc, c->best.p, max2,
+                         c->plane_partials.p, c->d_nun.p);
+        hipLaunchKernelGGL(k_icp_final<ICP_PLANE_NSUM>, dim3(1), dim3(64), 0, s, c->plane_partials.p, nb, c->h_plane.p);
+    } else {
+        hipLaunchKernelGGL(k_icp_reduce, dim3(nb), dim3(256), 0, s, pts, n_src, c->tgt_cur, c->best.p, max2, c->partials.p, c->d_nun.p);
+        hipLaunchKernelGGL(k_icp_final<ICP_NSUM>, dim3(1), dim3(64), 0, s, c->partials.p, nb, c->h_sums.p);
+    }
     SCAL_HIP(hipGetLastError());
     SCAL_HIP(hipStreamSynchronize(s));
+    return SCAL_OK;
+}
+
+// what only the point-to-plane calls need, allocated by the first of them and released with the context
+static int icp_plane_prepare(scal_icp* c, bool staging) {
+    if (!c->plane_partials.p) SCAL_TRY(c->plane_partials.alloc(static_cast<size_t>(ICP_PLANE_NSUM) * (div_up(c->cfg.max_source, 256) + 1)));
+    if (!c->h_plane.p) SCAL_TRY(c->h_plane.alloc(ICP_PLANE_NSUM));
+    if (staging && !c->nc.p) SCAL_TRY(c->nc.alloc(c->cfg.max_target));
     return SCAL_OK;
 }
 
 // clouds in host memory (on_device = false: staged into the context) or already in HBM (the target is then used in place).
 // guess != nullptr: pcl::Registration::align(output, guess) - the working copy of the source is moved by the guess once and the
 // accumulated transformation starts from it; nullptr is align(output), today's path launch for launch.
+// pres != nullptr: point-to-plane on the target's normals tgt_nc (where the clouds are), the result in *pres and res unused; the
+// two metrics differ in the reduction of a sweep, in the host's increment and in the final sweep's cap, and in nothing else.
 static int icp_align(scal_icp* c, const float* src_xyzi, int n_src, const float* tgt_xyzi, int n_tgt, bool on_device, const float* guess,
-                     scal_icp_result* res) {
-    if (!c || !res || n_src < 0 || n_tgt < 0 || (n_src && !src_xyzi) || (n_tgt && !tgt_xyzi)) {
-        set_error("scal_icp_align: bad argument");
+                     scal_icp_result* res, const float* tgt_nc = nullptr, scal_icp_plane_result* pres = nullptr) {
+    const bool plane = pres != nullptr;
+    if (!c || !(res || pres) || n_src < 0 || n_tgt < 0 || (n_src && !src_xyzi) || (n_tgt && !tgt_xyzi) || (plane && n_tgt && !tgt_nc)) {
+        set_error("%s: bad argument", plane ? "scal_icp_align_plane" : "scal_icp_align");
         return SCAL_E_ARG;
     }
     if (n_src > c->cfg.max_source || n_tgt > c->cfg.max_target) {
-        set_error("scal_icp_align: cloud larger than the context capacity (source %d, target %d)", c->cfg.max_source, c->cfg.max_target);
+        set_error("%s: cloud larger than the context capacity (source %d, target %d)", plane ? "scal_icp_align_plane" : "scal_icp_align",
+                  c->cfg.max_source, c->cfg.max_target);
         return SCAL_E_TOO_MANY;
     }
-    std::memset(res, 0, sizeof *res);
     float F[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    for (int k = 0; k < 16; ++k) res->T[k] = F[k];
-    res->fitness = std::numeric_limits<double>::max();
+    if (plane) {
+        std::memset(pres, 0, sizeof *pres);
+        for (int k = 0; k < 16; ++k) pres->T[k] = F[k];
+        pres->fitness = pres->plane_fitness = std::numeric_limits<double>::max();
+    } else {
+        std::memset(res, 0, sizeof *res);
+        for (int k = 0; k < 16; ++k) res->T[k] = F[k];
+        res->fitness = std::numeric_limits<double>::max();
+    }
     if (n_src == 0 || n_tgt == 0) {  // pcl::Registration::align refuses empty clouds: not converged
-        res->state = 5;
+        (plane ? pres->state : res->state) = 5;
         return SCAL_OK;
     }
     SCAL_HIP(hipSetDevice(c->cfg.device));
+    if (plane) SCAL_TRY(icp_plane_prepare(c, !on_device));
     hipStream_t s = c->stream;
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     SCAL_HIP(hipMemcpyAsync(c->src.p, src_xyzi, sizeof(float) * 4 * n_src, kind, s));
     SCAL_HIP(hipMemcpyAsync(c->cur.p, src_xyzi, sizeof(float) * 4 * n_src, kind, s));
     const float4* tgt = c->tgt.p;
+    const float4* nc = nullptr;
     if (on_device)
         tgt = reinterpret_cast<const float4*>(tgt_xyzi);
     else
         SCAL_HIP(hipMemcpyAsync(c->tgt.p, tgt_xyzi, sizeof(float) * 4 * n_tgt, hipMemcpyHostToDevice, s));
+    if (plane) {
+        nc = on_device ? reinterpret_cast<const float4*>(tgt_nc) : c->nc.p;
+        if (!on_device) SCAL_HIP(hipMemcpyAsync(c->nc.p, tgt_nc, sizeof(float) * 4 * n_tgt, hipMemcpyHostToDevice, s));
+    }
     c->tgt_cur = tgt;
     if (guess) {
         Mat34f G;
@@ -371,10 +420,17 @@ static int icp_align(scal_icp* c, const float* src_xyzi, int n_src, const float*
     IcpIterState is;  // the iteration itself is icp_host.hpp's, shared with the multiview refine
     if (guess) std::memcpy(is.F, guess, sizeof is.F);
     for (;;) {
-        SCAL_TRY(icp_sweep(c, c->cur.p, n_src, n_tgt, max2));
+        SCAL_TRY(icp_sweep(c, c->cur.p, n_src, n_tgt, max2, nc));
         float T[16];
-        const int step = icp_host_step(is, c->h_sums.p, c->cfg.max_iterations, te, fe, T);
-        res->n_correspondences = is.n_corr;
+        int step;
+        if (plane) {
+            if (is.it == 0) std::memcpy(pres->first_eq, c->h_plane.p + 1, sizeof pres->first_eq);
+            step = icp_plane_host_step(is, c->h_plane.p, c->cfg.max_iterations, te, fe, T);
+            pres->n_correspondences = is.n_corr;
+        } else {
+            step = icp_host_step(is, c->h_sums.p, c->cfg.max_iterations, te, fe, T);
+            res->n_correspondences = is.n_corr;
+        }
         if (step == ICP_STEP_STOP) break;
         Mat34f M;
         std::memcpy(M.m, T, sizeof M.m);
@@ -384,11 +440,23 @@ static int icp_align(scal_icp* c, const float* src_xyzi, int n_src, const float*
     std::memcpy(F, is.F, sizeof F);
     const int it = is.it, st = is.st;
     const bool converged = is.converged;
-    // getFitnessScore(): the original source moved by the final transform, no distance cap
+    // getFitnessScore(): the original source moved by the final transform, no distance cap (point-to-plane: the cap stays for the
+    // rows, and the uncapped pair of sums rides along)
     Mat34f M;
     std::memcpy(M.m, F, sizeof M.m);
     hipLaunchKernelGGL(k_icp_apply, dim3(div_up(n_src, 256)), dim3(256), 0, s, c->src.p, c->cur.p, n_src, M);
-    SCAL_TRY(icp_sweep(c, c->cur.p, n_src, n_tgt, 3.4e38f));
+    SCAL_TRY(icp_sweep(c, c->cur.p, n_src, n_tgt, plane ? max2 : 3.4e38f, nc));
+    if (plane) {
+        const double* h = c->h_plane.p;
+        pres->converged = converged ? 1 : 0;
+        pres->iterations = it;
+        pres->state = st;
+        pres->fitness = h[30] > 0 ? h[31] / h[30] : std::numeric_limits<double>::max();
+        pres->plane_fitness = h[0] > 0 ? h[28] / h[0] : std::numeric_limits<double>::max();
+        std::memcpy(pres->normal_eq, h + 1, sizeof pres->normal_eq);
+        for (int k = 0; k < 16; ++k) pres->T[k] = F[k];
+        return SCAL_OK;
+    }
     res->converged = converged ? 1 : 0;
     res->iterations = it;
     res->state = st;
@@ -436,4 +504,26 @@ extern "C" int scal_icp_align_guess_device(scal_icp_t* c, const float* d_src_xyz
     const float* g;
     SCAL_TRY(icp_check_guess(guess, &g));
     return icp_align(c, d_src_xyzi, n_src, d_tgt_xyzi, n_tgt, true, g, res);
+}
+
+extern "C" int scal_icp_align_plane(scal_icp_t* c, const float* src_xyzi, int n_src, const float* tgt_xyzi, const float* tgt_nc, int n_tgt,
+                                    const float guess[16], scal_icp_plane_result* res) {
+    const float* g;
+    SCAL_TRY(icp_check_guess(guess, &g));
+    if (!res) {
+        set_error("scal_icp_align_plane: bad argument");
+        return SCAL_E_ARG;
+    }
+    return icp_align(c, src_xyzi, n_src, tgt_xyzi, n_tgt, false, g, nullptr, tgt_nc, res);
+}
+
+extern "C" int scal_icp_align_plane_device(scal_icp_t* c, const float* d_src_xyzi, int n_src, const float* d_tgt_xyzi, const float* d_tgt_nc,
+                                           int n_tgt, const float guess[16], scal_icp_plane_result* res) {
+    const float* g;
+    SCAL_TRY(icp_check_guess(guess, &g));
+    if (!res) {
+        set_error("scal_icp_align_plane: bad argument");
+        return SCAL_E_ARG;
+    }
+    return icp_align(c, d_src_xyzi, n_src, d_tgt_xyzi, n_tgt, true, g, nullptr, d_tgt_nc, res);
 }

@@ -8,7 +8,8 @@
 namespace scal {
 
 constexpr int ICP_NSUM = 17;           // n, sum p[3], sum q[3], sum q p^T[9], sum d^2
-constexpr int ICP_RINGS = 3;           // rings of cells the grid search examines before it gives a query up
+constexpr int ICP_PLANE_NSUM = 32;     // point-to-plane: n, 21 of a a^T, a r[6], r r, sum d, n any, sum d any (SCAL_ICP_PLANE_NSUM)
+constexpr int ICP_RINGS = 3;          // rings of cells the grid search examines before it gives a query up
 constexpr int ICP_QPT = 4;             // dense sweep: queries per thread
 constexpr int ICP_QT = 256 * ICP_QPT;  //              queries per workgroup
 constexpr int ICP_TC = 2048;           //              targets per workgroup
@@ -162,6 +163,55 @@ __device__ __forceinline__ void icp_corr_sums(const float4* __restrict__ cur, co
     }
     __syncthreads();
     if (threadIdx.x < ICP_NSUM) partials[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// ---- the 32 point-to-plane sums of one workgroup of 256 source points (scal_icp_align_plane; the header has the definition) -----------
+// The arguments of icp_corr_sums and the target's normals nc[] (normal, curvature; scal_nbr_normals' layout).  Reads the key and
+// resets it; gathers tgt[idx] and nc[idx]; a correspondence within the cap whose normal is finite makes the row a = (p x n, n),
+// r = (q - p).n in f64 and adds 1, a a^T's upper triangle, a r, r r and d; every query with a neighbour adds 1 and d to [30], [31]
+// whatever the cap and the normal.  Every sum: wave_sum, then the four waves as ((r0 + r1) + r2) + r3 -> partials[0 .. 32).
+__device__ __forceinline__ void icp_plane_sums(const float4* __restrict__ cur, const float4* __restrict__ tgt, const float4* __restrict__ nc,
+                                               unsigned long long* __restrict__ best, float max2, int i, bool has, double* __restrict__ partials) {
+    __shared__ double red[4][ICP_PLANE_NSUM];
+    double v[ICP_PLANE_NSUM];
+#pragma unroll
+    for (int k = 0; k < ICP_PLANE_NSUM; ++k) v[k] = 0.0;
+    if (has) {
+        const unsigned long long key = best[i];
+        best[i] = ~0ull;
+        if (key != ~0ull) {
+            const float d = __uint_as_float(static_cast<unsigned>(key >> 32));
+            v[30] = 1.0, v[31] = d;
+            if (!(d > max2)) {
+                const unsigned idx = static_cast<unsigned>(key & 0xffffffffu);
+                const float4 nf = nc[idx];
+                if (fabsf(nf.x) <= 3.4028235e38f && fabsf(nf.y) <= 3.4028235e38f && fabsf(nf.z) <= 3.4028235e38f) {  // finite: false for NaN
+                    const float4 pf = cur[i], qf = tgt[idx];
+                    const double px = pf.x, py = pf.y, pz = pf.z, nx = nf.x, ny = nf.y, nz = nf.z;
+                    const double a[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+                    const double ex = static_cast<double>(qf.x) - px, ey = static_cast<double>(qf.y) - py, ez = static_cast<double>(qf.z) - pz;
+                    const double r = (ex * nx + ey * ny) + ez * nz;
+                    v[0] = 1.0;
+                    int k = 1;
+#pragma unroll
+                    for (int r0 = 0; r0 < 6; ++r0)
+#pragma unroll
+                        for (int c0 = r0; c0 < 6; ++c0) v[k++] = a[r0] * a[c0];
+#pragma unroll
+                    for (int r0 = 0; r0 < 6; ++r0) v[22 + r0] = a[r0] * r;
+                    v[28] = r * r;
+                    v[29] = d;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < ICP_PLANE_NSUM; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane_id() == 0) red[wave_id()][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < ICP_PLANE_NSUM) partials[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
 // ---- the rigid increment applied to a point, f32 as PCL does: rows of the 3x4 matrix m, .w kept ---------------------------------------

@@ -75,6 +75,12 @@ class ICPResult(C.Structure):
                 ("fitness", C.c_double), ("T", C.c_double * 16)]
 
 
+class ICPPlaneResult(C.Structure):
+    _fields_ = [("converged", C.c_int), ("iterations", C.c_int), ("state", C.c_int), ("n_correspondences", C.c_int),
+                ("fitness", C.c_double), ("plane_fitness", C.c_double), ("T", C.c_double * 16), ("normal_eq", C.c_double * 27),
+                ("first_eq", C.c_double * 27)]
+
+
 class RefineConfig(C.Structure):
     _fields_ = [("max_corr_dist", C.c_double), ("transformation_epsilon", C.c_double), ("fitness_epsilon", C.c_double),
                 ("fitness_gate", C.c_double), ("max_iterations", C.c_int), ("max_frames", C.c_int), ("max_points", C.c_int),
@@ -201,6 +207,7 @@ EXPORTED_SYMBOLS = [
     "scal_nbr_create", "scal_nbr_destroy", "scal_nbr_set_index", "scal_nbr_set_index_device", "scal_nbr_query", "scal_nbr_query_device", "scal_nbr_query_self", "scal_nbr_stats",
     "scal_nbr_knn", "scal_nbr_knn_device", "scal_nbr_knn_self",
     "scal_nbr_normals", "scal_nbr_normals_device", "scal_nbr_normals_self",
+    "scal_icp_align_plane", "scal_icp_align_plane_device",
 ]
 
 _lib = None
@@ -407,7 +414,10 @@ def lib():
         L.scal_nbr_normals.argtypes = [vp, _f32p, C.c_int, C.c_int, _f64p, _f32p, _f32p]
         L.scal_nbr_normals_device.argtypes = [vp, vp, C.c_int, C.c_int, _f64p, vp, vp]
         L.scal_nbr_normals_self.argtypes = [vp, C.c_int, _f64p, _f32p, _f32p]
-    L.scal_keyframe_gate_init.argtypes = [C.POINTER(KeyframeGateState), C.c_double, C.c_double]
+    if hasattr(L, "scal_icp_align_plane"):  # absent from older builds compared through SCALOAM_LIB
+        L.scal_icp_align_plane.argtypes = [vp, _f32p, C.c_int, _f32p, _f32p, C.c_int, _f32p, C.POINTER(ICPPlaneResult)]
+        L.scal_icp_align_plane_device.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, _f32p, C.POINTER(ICPPlaneResult)]
+    L.scal_keyframe_gate_init.argtypes =[C.POINTER(KeyframeGateState), C.c_double, C.c_double]
     L.scal_keyframe_gate.argtypes = [C.POINTER(KeyframeGateState), _f64p, _f64p, _i32p]
     for fn in ("scal_pipeline_sc_of", "scal_pipeline_map_of"):
         getattr(L, fn).restype = C.c_void_p
@@ -965,6 +975,38 @@ class LoopICP:
             _check(lib().scal_icp_align_guess(self.h, _p(s, _f32p), s.shape[0], _p(t, _f32p), t.shape[0], _p(g, _f32p), C.byref(r)))
         return dict(converged=bool(r.converged), iterations=r.iterations, state=r.state, n_correspondences=r.n_correspondences,
                     fitness=r.fitness, T=np.array(r.T[:]).reshape(4, 4))
+
+    @staticmethod
+    def _plane_dict(r):
+        return dict(converged=bool(r.converged), iterations=r.iterations, state=r.state, n_correspondences=r.n_correspondences,
+                    fitness=r.fitness, plane_fitness=r.plane_fitness, T=np.array(r.T[:]).reshape(4, 4), normal_eq=np.array(r.normal_eq[:]),
+                    first_eq=np.array(r.first_eq[:]))
+
+    @staticmethod
+    def _guess(guess):
+        if guess is None:
+            return None
+        g = np.asarray(guess)
+        if g.size != 16:
+            raise ValueError("the guess is a 4x4 matrix")
+        return _f32(g.reshape(16))
+
+    def align_plane(self, src, tgt, tgt_nc, guess=None):
+        """Point-to-plane ICP (scal_icp_align_plane): tgt_nc [n_tgt, 4] is the target's normals and curvatures as
+        RadiusIndex.normals* returns them.  The CPU restatement is scaloam.icp_plane.align_plane."""
+        s, t, nc = _f32(src), _f32(tgt), _f32(tgt_nc)
+        if nc.shape != (t.shape[0], 4):
+            raise ValueError("tgt_nc is [n_tgt, 4]: one normal and curvature per target point")
+        g = self._guess(guess)
+        r = ICPPlaneResult()
+        _check(lib().scal_icp_align_plane(self.h, _p(s, _f32p), s.shape[0], _p(t, _f32p), _p(nc, _f32p), t.shape[0], _p(g, _f32p), C.byref(r)))
+        return self._plane_dict(r)
+
+    def align_plane_device(self, d_src_ptr, n_src, d_tgt_ptr, d_nc_ptr, n_tgt, guess=None):
+        g = self._guess(guess)
+        r = ICPPlaneResult()
+        _check(lib().scal_icp_align_plane_device(self.h, d_src_ptr, n_src, d_tgt_ptr, d_nc_ptr, n_tgt, _p(g, _f32p), C.byref(r)))
+        return self._plane_dict(r)
 
 
 class MultiviewRefine:
