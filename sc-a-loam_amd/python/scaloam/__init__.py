@@ -954,9 +954,14 @@ class LoopICP:
 
     __del__ = close
 
-    def align_device(self, d_src_ptr, n_src, d_tgt_ptr, n_tgt):
+    def align_device(self, d_src_ptr, n_src, d_tgt_ptr, n_tgt, guess=None):
+        """the clouds as 16-byte xyzi records in device memory; guess as in align (scal_icp_align_guess_device)"""
         r = ICPResult()
-        _check(lib().scal_icp_align_device(self.h, d_src_ptr, n_src, d_tgt_ptr, n_tgt, C.byref(r)))
+        if guess is None:
+            _check(lib().scal_icp_align_device(self.h, d_src_ptr, n_src, d_tgt_ptr, n_tgt, C.byref(r)))
+        else:
+            g = self._guess(guess)
+            _check(lib().scal_icp_align_guess_device(self.h, d_src_ptr, n_src, d_tgt_ptr, n_tgt, _p(g, _f32p), C.byref(r)))
         return dict(converged=bool(r.converged), iterations=r.iterations, state=r.state, n_correspondences=r.n_correspondences,
                     fitness=r.fitness, T=np.array(r.T[:]).reshape(4, 4))
 

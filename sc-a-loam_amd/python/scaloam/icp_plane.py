@@ -90,20 +90,21 @@ def point_terms(cur, tgt, tgt_nc, keys, max2):
 
 
 def reduce_terms(v):
-    """the device's reduction of the per-point terms v [n, 32] -> float64 [32]: source point i is lane i % 64 of wave (i / 64) % 4 of
-    workgroup i / 256; lanes by the xor butterfly 32, 16, .. 1, waves as ((r0 + r1) + r2) + r3, workgroups sequentially from +0"""
-    n = v.shape[0]
+    """the device's reduction of the per-point terms v [n, ns] -> float64 [ns] (32 sums here, 17 in icp_point): source point i is lane
+    i % 64 of wave (i / 64) % 4 of workgroup i / 256; lanes by the xor butterfly 32, 16, .. 1, waves as ((r0 + r1) + r2) + r3,
+    workgroups sequentially from +0"""
+    n, ns = v.shape
     nb = max((n + 255) // 256, 0)
-    pad = np.zeros((nb * 256, NSUM), np.float64)
+    pad = np.zeros((nb * 256, ns), np.float64)
     pad[:n] = v
-    w = pad.reshape(nb, 4, 64, NSUM)
+    w = pad.reshape(nb, 4, 64, ns)
     lane = np.arange(64)
     with np.errstate(all="ignore"):
         for o in (32, 16, 8, 4, 2, 1):
             w = w + w[:, :, lane ^ o, :]
         w = w[:, :, 0, :]
         part = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
-        s = np.zeros(NSUM, np.float64)
+        s = np.zeros(ns, np.float64)
         for b in range(nb):
             s = s + part[b]
     return s

@@ -289,3 +289,47 @@ def test_refine_errors_leave_the_context_usable(S, kf):
     assert call([0, 50, 100]) == S.OK and run.value == 1
     _case3(S, rf, a)
     rf.close()
+
+
+def small_frames():
+    """three pieces (500, 400 and 350 points) of one room corner of three 24 x 24 lattices at 0.25 m, each moved by a few centimetres
+    and a few milliradians and given 5 mm of noise"""
+    from test_icp_plane_cpu import corner_scene
+    from test_icp_point_cpu import rigid
+    rng = np.random.default_rng(71)
+    corner = corner_scene()[0][:, :3].astype(np.float64)
+    frames = []
+    for n, axis, th, t in ((500, [0.0, 0.2, 1.0], 0.004, [0.02, -0.01, 0.015]), (400, [1.0, 0.0, 0.3], -0.006, [-0.03, 0.02, 0.01]),
+                           (350, [0.3, 1.0, 0.0], 0.005, [0.01, 0.03, -0.02])):
+        M = rigid(axis, th, t)
+        xyz = corner[rng.permutation(corner.shape[0])[:n]] @ M[:3, :3].T + M[:3, 3] + rng.normal(0.0, 0.005, (n, 3))
+        f = np.zeros((n, 4), np.float32)
+        f[:, :3] = xyz
+        frames.append(f)
+    return frames
+
+
+@pytest.mark.parametrize("cap", [2.0, 150.0])
+def test_refine_at_small_shapes_equals_the_cpu_restatement(S, cap):
+    """Identity poses and near_thres = 0 leave the frames as they are, so every frame's result is scaloam.icp_point.align of the frame
+    against the concatenation of the others - the cell-hash lookup, the own-frame exclusion and frames of one to two workgroups
+    against a reference that is not the GPU.  cap 2.0: the rings alone; 150: with the dense list behind them.  The refine's
+    fitness keeps the cap, the restatement's does not: the scenes have every point's neighbour within it."""
+    from scaloam import icp_plane, icp_point
+    from test_icp_point_cpu import same_result
+    frames = small_frames()
+    assert [f.shape[0] for f in frames] == [500, 400, 350]
+    for fr in (frames, [frames[0], frames[0].copy(), frames[2]]):     # and two identical frames: ties resolve to the lower frame
+        want = [icp_point.align(fr[f], np.concatenate([fr[g] for g in range(3) if g != f]), max_corr_dist=cap, max_iterations=20)
+                for f in range(3)]
+        for f in range(3):
+            others = np.concatenate([fr[g] for g in range(3) if g != f])
+            moved = icp_plane.transform(want[f]["T"].astype(np.float32), fr[f])
+            assert icp_point.sweep_sums(moved, others, np.float32(cap * cap))[0] == fr[f].shape[0]
+            assert want[f]["converged"] and want[f]["iterations"] >= 1
+        rf = S.MultiviewRefine(3, sum(f.shape[0] for f in fr), max_corr_dist=cap, max_iterations=20)
+        P, res, run = rf.refine(fr, np.stack([IDENT12] * 3), rounds=1, near_thres=0.0)
+        rf.close()
+        assert run == 1
+        for f in range(3):
+            assert same_result(res[f], want[f]), (f, res[f], want[f])

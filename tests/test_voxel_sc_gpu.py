@@ -509,7 +509,8 @@ def test_loop_icp_matches_oracle(O, S, golden):
     on real keyframes downsampled at 0.4 m as doICPVirtualRelative prepares them.  Nearest neighbours are exact on both sides and
     the increment is stored as the f32 Matrix4f PCL keeps, which absorbs the different order of the f64 correspondence sums: on the
     real keyframe pair every one of the 99 iterates equals the oracle's bit for bit (tools/diag_icp_iterates.py), so the bar here
-    is 1e-9, not the 2e-3 an earlier version of this test allowed."""
+    is 1e-9, not the 2e-3 an earlier version of this test allowed.  Small shapes, the dense-only path, the cap, ties, the guess and
+    the convergence states are held bit for bit to the CPU restatement scaloam.icp_point in tests/test_icp_point_gpu.py."""
     vg = S.VoxelGrid()
     icp = S.LoopICP(max_source=100000, max_target=400000)
     a = vg.filter(golden("KAIST03_000000.npy"), 0.4)
