@@ -599,6 +599,64 @@ int scal_refine_run_device(scal_refine_t* ctx, const float* d_xyzi, const int* o
 int scal_refine_run(scal_refine_t* ctx, const float* xyzi, const int* offsets, int n_frames, double* poses12,
                     const unsigned char* fixed, double near_thres, int rounds, scal_refine_frame_result* res, int* rounds_run);
 
+/* ---- the multiview refine with the point-to-plane metric (an extension)
+ * The same context, the same scal_refine_config, the same rounds; what differs from scal_refine_run* is the metric of step 2, which
+ * is scal_icp_align_plane's, and what it needs.  The CPU restatement is scaloam/refine_plane.py; the device is held to it bit for
+ * bit, so THE ORDER OF THE OPERATIONS BELOW IS PART OF THE INTERFACE.
+ *
+ * Input normals.  nc [offsets[n_frames]][4] f32, one record per input record: the normal and the curvature of that point among the
+ * points of ITS OWN frame in the frame's LOCAL coordinates, in the layout scal_nbr_normals_self writes, NaN rows included.  Local
+ * normals do not depend on the poses being refined: the caller computes them once per frame and every round reuses them.  The sign
+ * of a normal does not matter (a row and its residual flip together); the curvature is carried along and otherwise ignored.
+ *
+ * One round is the point refine's round with three differences.
+ *  1. The move.  A kept point goes through exactly what step 1 above does (same bits, same near-range rule
+ *     sqrt((x x + y y) + z z) > near_thres, same stable compaction) and its normal is written to the same position of the union as
+ *         N.x = (float)((P[0] n.x + P[1] n.y) + P[2]  n.z)
+ *         N.y = (float)((P[4] n.x + P[5] n.y) + P[6]  n.z)
+ *         N.z = (float)((P[8] n.x + P[9] n.y) + P[10] n.z)        N.w = n.w
+ *     with P the frame's pose12, every operation in f64 on the promoted f32 components, one rounding each, no translation.  A NaN
+ *     component makes the moved normal non-finite, and the sums drop such a correspondence as scal_icp_align_plane does.
+ *  2. The sweep.  The neighbour search is the point refine's, untouched.  The sums are scal_icp_align_plane's 32, with the moved
+ *     normals of the whole union as the target's normals: source point i of frame f (counted from the frame's first kept point) is
+ *     lane i % 64 of wave (i / 64) % 4 of the frame's workgroup i / 256, the frame's workgroups are summed in workgroup order from
+ *     +0.  The host step is scal_icp_align_plane's: fewer than 6 rows is state 5, degenerate normal equations state 6; both end the
+ *     frame unconverged and not accepted, its pose kept.
+ *  3. The result, scal_refine_plane_frame_result: plane_fitness = [28] / [0] and normal_eq = [1..27] of the final sweep (the moved
+ *     frame by the whole T, same cap), first_eq = [1..27] of the first sweep.  fitness = [29] / [0] of the final sweep: the mean f32
+ *     d over the rows, that is within the cap AND with a finite normal.  This deviates from scal_icp_plane_result::fitness, which is
+ *     [31] / [30], uncapped: the refine does not settle far queries when the cap is below the last ring of the search, so [30] and
+ *     [31] are no defined quantity here - the reasoning of step 3 above.  Where every source point has its neighbour within the cap
+ *     and that neighbour's normal is finite, the two are the same number bit for bit.
+ * Acceptance (converged and fitness <= fitness_gate), pose <- T pose, Jacobi rounds, `fixed` and the early stop are the point
+ * refine's.
+ *
+ * The equality held: for every cap, sums [0..29] of every frame in every sweep are those of
+ * scal_icp_align_plane(G_f, concat(G_g, g != f), concat(N_g, g != f)), G and N the moved points and normals; therefore T,
+ * iterations, state, converged, n_correspondences, plane_fitness, normal_eq and first_eq equal it bit for bit.  Leaving the own
+ * frame out keeps the index order among the other frames, so equal distances resolve alike.
+ *
+ * The first plane call on a context allocates what only these calls need (the moved normals, the 32-wide partials, the pinned
+ * [max_frames][32] sums; the normals staging by the first call with host arrays); they are released with the context.  The point
+ * refine's results on the same context are not changed by these calls. */
+typedef struct {
+    int converged, iterations, state, n_correspondences;  /* as scal_refine_frame_result; n_correspondences counts rows; state 6: degenerate */
+    int accepted;
+    double fitness;         /* mean d over the final sweep's rows (see above); DBL_MAX without one */
+    double T[16];
+    double plane_fitness;   /* mean r^2 over the final sweep's rows; DBL_MAX without one */
+    double normal_eq[27];   /* upper triangle of A^T A (21, row-major) and A^T b (6) of the FINAL sweep: the frame's 6x6 information */
+    double first_eq[27];    /* the same of the FIRST sweep */
+} scal_refine_plane_frame_result;
+/* arguments, checks and error codes as scal_refine_run_device; d_nc == NULL with any point present is SCAL_E_ARG.  Everything is
+ * checked before the device is touched and the context stays usable after any error. */
+int scal_refine_run_plane_device(scal_refine_t* ctx, const float* d_xyzi, const float* d_nc, const int* offsets, int n_frames,
+                                 double* poses12, const unsigned char* fixed, double near_thres, int rounds,
+                                 scal_refine_plane_frame_result* res, int* rounds_run);
+/* the same with records and normals in host memory (staged into the context) */
+int scal_refine_run_plane(scal_refine_t* ctx, const float* xyzi, const float* nc, const int* offsets, int n_frames, double* poses12,
+                          const unsigned char* fixed, double near_thres, int rounds, scal_refine_plane_frame_result* res, int* rounds_run);
+
 /* ------------------------------------------------------------------ the four stages as ONE pipelined object
  * The reference runs scanRegistration, laserOdometry, laserMapping and laserPosegraphOptimization as four processes that work on
  * different scans at the same time (node main()s: scanRegistration.cpp:475-517, laserOdometry.cpp:186-600, laserMapping.cpp:909-952,

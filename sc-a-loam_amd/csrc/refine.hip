@@ -18,6 +18,10 @@
 //   k_rf_final    the frame's workgroup partials in workgroup order -> pinned [K][17]: the additions of k_icp_reduce / k_icp_final on
 //                 that frame alone, in their order
 //   host          icp_host_step (icp_host.hpp, shared with icp.hip) per frame; K 3x4 increments and the active mask go back in one copy
+// scal_refine_run_plane* (an extension) is the same round with the point-to-plane metric of
+// scal_icp_align_plane on the frames' own local normals: k_rf_write_nc writes the rotated normals beside the moved points, the search
+// is untouched, k_rf_plane_reduce (icp_plane_sums, 32 sums) stands in for k_rf_reduce, k_rf_final<32> for k_rf_final<17> and
+// icp_plane_host_step for icp_host_step.
 // Frames that have finished cost an early return per workgroup.  The search, the sums and the transform are icp_dev.hpp's, the same
 // code icp.hip runs: what is written here is where a cell's points are, which candidates count and which point a thread owns.
 #include "common.hpp"
@@ -31,6 +35,7 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 namespace scal {
@@ -58,6 +63,47 @@ __global__ void __launch_bounds__(256) k_rf_write(const float4* __restrict__ in,
                                                   double thres, const int* __restrict__ blkoff, long long cap, float4* __restrict__ out,
                                                   int* __restrict__ frame_of) {
     mm_write_body<true>(in, blocks, poses, thres, blkoff, 0, cap, out, frame_of);
+}
+
+// scal_refine_run_plane*: the normals of the points k_rf_write keeps, rotated by the frame's pose, to the positions k_rf_write gives
+// the points - the same keep rule on the same records, the same ballot ranks, so out[o] is the normal of g[o].  A kernel of its own:
+// mm_write_body stays what the map merge compiles.  Rows of the pose's rotation in f64, one rounding per operation, no translation.
+__global__ void __launch_bounds__(256) k_rf_write_nc(const float4* __restrict__ in, const float4* __restrict__ nc, const MMBlock* __restrict__ blocks,
+                                                     const double* __restrict__ poses, double thres, const int* __restrict__ blkoff, long long cap,
+                                                     float4* __restrict__ out) {
+    __shared__ int s_cnt[MM_ITEMS][4];
+    const MMBlock b = blocks[blockIdx.x];
+    const int w = wave_id();
+    bool keep[MM_ITEMS];
+    int rank[MM_ITEMS];
+#pragma unroll
+    for (int j = 0; j < MM_ITEMS; ++j) {
+        const int i = b.first + j * 256 + threadIdx.x;
+        keep[j] = i < b.end && mm_keep(in[i], thres);
+        const uint64_t m = __ballot(keep[j]);
+        rank[j] = __popcll(m & lanemask_lt());
+        if (lane_id() == 0) s_cnt[j][w] = __popcll(m);
+    }
+    __syncthreads();
+    const double* T = poses + 12 * b.frame;
+    int before = 0;  // kept points of the workgroup in front of (j, wave w)
+#pragma unroll
+    for (int j = 0; j < MM_ITEMS; ++j) {
+        int mine = before;
+        for (int q = 0; q < w; ++q) mine += s_cnt[j][q];
+        before += s_cnt[j][0] + s_cnt[j][1] + s_cnt[j][2] + s_cnt[j][3];
+        if (!keep[j]) continue;
+        const long long o = blkoff[blockIdx.x] + mine + rank[j];
+        if (o >= cap) continue;
+        const float4 n = nc[b.first + j * 256 + threadIdx.x];
+        const double x = n.x, y = n.y, z = n.z;
+        float4 g;
+        g.x = static_cast<float>((T[0] * x + T[1] * y) + T[2] * z);
+        g.y = static_cast<float>((T[4] * x + T[5] * y) + T[6] * z);
+        g.z = static_cast<float>((T[8] * x + T[9] * y) + T[10] * z);
+        g.w = n.w;
+        out[o] = g;
+    }
 }
 
 __device__ __forceinline__ int rf_coord(float v, int bits) { return ch_clamp_coord(v, bits); }  // NaN -> the lowest cell
@@ -156,16 +202,27 @@ __global__ void __launch_bounds__(256) k_rf_reduce(const float4* __restrict__ cu
     icp_corr_sums(cur, tgt, best, max2, i, i < b.end, partials + static_cast<size_t>(blockIdx.x) * ICP_NSUM);
 }
 
-// one workgroup per frame: its workgroup partials in workgroup order -> host_out[frame][17] (pinned, device-visible memory)
+// the same for the 32 point-to-plane sums (scal_refine_run_plane); nc: the moved normals of all of G
+__global__ void __launch_bounds__(256) k_rf_plane_reduce(const float4* __restrict__ cur, const float4* __restrict__ tgt, const float4* __restrict__ nc,
+                                                         const RfBlock* __restrict__ blocks, const RfCtrl* __restrict__ ctrl,
+                                                         unsigned long long* __restrict__ best, float max2, double* __restrict__ partials) {
+    const RfBlock b = blocks[blockIdx.x];
+    if (!ctrl[b.frame].active) return;
+    const int i = b.first + threadIdx.x;
+    icp_plane_sums(cur, tgt, nc, best, max2, i, i < b.end, partials + static_cast<size_t>(blockIdx.x) * ICP_PLANE_NSUM);
+}
+
+// one workgroup per frame: its workgroup partials (NS to a workgroup) in workgroup order -> host_out[frame][NS] (pinned, device-visible memory)
+template <int NS>
 __global__ void __launch_bounds__(64) k_rf_final(const double* __restrict__ partials, const int* __restrict__ fb0, const RfCtrl* __restrict__ ctrl,
                                                  double* __restrict__ host_out, int* __restrict__ d_nun) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *d_nun = 0;  // the unresolved-query list is consumed by now
     const int f = blockIdx.x;
     if (!ctrl[f].active) return;
-    if (threadIdx.x < ICP_NSUM) {
+    if (threadIdx.x < NS) {
         double s = 0.0;
-        for (int b = fb0[f]; b < fb0[f + 1]; ++b) s += partials[static_cast<size_t>(b) * ICP_NSUM + threadIdx.x];
-        host_out[f * ICP_NSUM + threadIdx.x] = s;
+        for (int b = fb0[f]; b < fb0[f + 1]; ++b) s += partials[static_cast<size_t>(b) * NS + threadIdx.x];
+        host_out[f * NS + threadIdx.x] = s;
     }
 }
 
@@ -195,6 +252,10 @@ struct scal_refine {
     PinBuf<double> h_poses, h_sums;
     PinBuf<RfBlock> h_blocks;
     PinBuf<RfCtrl> h_ctrl;
+    // point-to-plane: allocated by the first scal_refine_run_plane* call (the normals staging by the first with host arrays)
+    DevBuf<float4> nloc, gn;  // the input normals staged in; the moved normals of G
+    DevBuf<double> plane_partials;
+    PinBuf<double> h_plane;
 };
 
 extern "C" int scal_refine_create(const scal_refine_config* cfg, scal_refine_t** out) { return refine_create_on_lane(cfg, 0, out); }
@@ -243,7 +304,7 @@ extern "C" void scal_refine_destroy(scal_refine_t* c) {
 }
 
 static int refine_check_args(scal_refine* c, const float* xyzi, const int* offsets, int n_frames, double* poses12, double near_thres, int rounds,
-                             scal_refine_frame_result* res, int* rounds_run) {
+                             const void* res, int* rounds_run) {
     if (!c || !offsets || !poses12 || !res || !rounds_run || n_frames < 0 || rounds < 1 || !(near_thres == near_thres) || std::isinf(near_thres)) {
         set_error("scal_refine_run: bad argument");
         return SCAL_E_ARG;
@@ -281,22 +342,34 @@ struct RfFrame {
 }  // namespace
 
 // one sweep of the frames marked active in h_ctrl (already uploaded): sums -> c->h_sums (waits)
-static int refine_sweep(scal_refine* c, int n, int n_frames, int nb, float max2, bool dense) {
+// plane: the 32 point-to-plane sums on the moved normals c->gn -> c->h_plane instead
+static int refine_sweep(scal_refine* c, int n, int n_frames, int nb, float max2, bool dense, bool plane) {
     hipStream_t s = c->stream;
     SCAL_LAUNCH_PROF("k_rf_grid_nn", k_rf_grid_nn, dim3(div_up(n, 4)), dim3(256), 0, s, c->cur.p, n, c->frame_of.p, c->goff.p, c->ctrl.p, c->hkeys.p,
                      c->hrange.p, c->hmask, c->sorted.p, c->best.p, c->un_list.p, c->d_misc.p, dense ? 1 : 0);
     if (dense)
         SCAL_LAUNCH_PROF("k_rf_dense", k_rf_dense, dim3(RF_DENSE_WG), dim3(256), 0, s, c->cur.p, c->g.p, n, c->frame_of.p, c->goff.p, c->best.p,
                          c->un_list.p, c->d_misc.p);
-    SCAL_LAUNCH_PROF("k_rf_reduce", k_rf_reduce, dim3(nb), dim3(256), 0, s, c->cur.p, c->g.p, c->blocks.p, c->ctrl.p, c->best.p, max2, c->partials.p);
-    hipLaunchKernelGGL(k_rf_final, dim3(n_frames), dim3(64), 0, s, c->partials.p, c->fb0.p, c->ctrl.p, c->h_sums.p, c->d_misc.p);
+    if (plane) {
+        SCAL_LAUNCH_PROF("k_rf_plane_reduce", k_rf_plane_reduce, dim3(nb), dim3(256), 0, s, c->cur.p, c->g.p, c->gn.p, c->blocks.p, c->ctrl.p, c->best.p,
+                         max2, c->plane_partials.p);
+        hipLaunchKernelGGL(k_rf_final<ICP_PLANE_NSUM>, dim3(n_frames), dim3(64), 0, s, c->plane_partials.p, c->fb0.p, c->ctrl.p, c->h_plane.p, c->d_misc.p);
+    } else {
+        SCAL_LAUNCH_PROF("k_rf_reduce", k_rf_reduce, dim3(nb), dim3(256), 0, s, c->cur.p, c->g.p, c->blocks.p, c->ctrl.p, c->best.p, max2, c->partials.p);
+        hipLaunchKernelGGL(k_rf_final<ICP_NSUM>, dim3(n_frames), dim3(64), 0, s, c->partials.p, c->fb0.p, c->ctrl.p, c->h_sums.p, c->d_misc.p);
+    }
     SCAL_HIP(hipGetLastError());
     SCAL_HIP(hipStreamSynchronize(s));
     return SCAL_OK;
 }
 
-static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets, int K, double* poses12, const unsigned char* fixed, double near_thres,
-                         int rounds, scal_refine_frame_result* res, int* rounds_run) {
+// Res = scal_refine_plane_frame_result: the point-to-plane metric on the frames' local normals d_nc (scal_refine_run_plane*)
+template <class Res>
+static int refine_rounds(scal_refine* c, const float4* d_loc, const float4* d_nc, const int* offsets, int K, double* poses12, const unsigned char* fixed,
+                         double near_thres, int rounds, Res* res, int* rounds_run) {
+    constexpr bool plane = std::is_same<Res, scal_refine_plane_frame_result>::value;
+    constexpr int NS = plane ? ICP_PLANE_NSUM : ICP_NSUM;
+    const double* const h_sums = plane ? c->h_plane.p : c->h_sums.p;
     hipStream_t s = c->stream;
     *rounds_run = 0;
     const double dmax = std::numeric_limits<double>::max();
@@ -304,6 +377,7 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets
         std::memset(&res[f], 0, sizeof res[f]);
         for (int k = 0; k < 4; ++k) res[f].T[5 * k] = 1.0;
         res[f].fitness = dmax;
+        if constexpr (plane) res[f].plane_fitness = dmax;
     }
     if (K == 0) return SCAL_OK;
     // the move's workgroups: the same for every round
@@ -361,6 +435,9 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets
             SCAL_HIP(hipMemcpyAsync(c->d_misc.p + 1, &c->h_goff.p[K], sizeof(int), hipMemcpyHostToDevice, s));
             SCAL_LAUNCH_PROF("k_rf_write", k_rf_write, dim3(nb_mm), dim3(256), 0, s, d_loc, c->mm_blocks.p, c->poses.p, near_thres, c->blk.p,
                              static_cast<long long>(n), c->g.p, c->frame_of.p);
+            if constexpr (plane)
+                SCAL_LAUNCH_PROF("k_rf_write_nc", k_rf_write_nc, dim3(nb_mm), dim3(256), 0, s, d_loc, d_nc, c->mm_blocks.p, c->poses.p, near_thres, c->blk.p,
+                                 static_cast<long long>(n), c->gn.p);
             SCAL_HIP(hipMemcpyAsync(c->cur.p, c->g.p, sizeof(float4) * n, hipMemcpyDeviceToDevice, s));
             // 2. the neighbour index over G
             SCAL_HIP(hipMemsetAsync(c->hkeys.p, 0xff, sizeof(unsigned long long) * (static_cast<size_t>(c->hmask) + 1), s));
@@ -383,11 +460,17 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets
                 SCAL_HIP(hipMemcpyAsync(c->ctrl.p, c->h_ctrl.p, sizeof(RfCtrl) * K, hipMemcpyHostToDevice, s));
                 if (!first) hipLaunchKernelGGL(k_rf_apply, dim3(nb), dim3(256), 0, s, c->cur.p, c->cur.p, c->blocks.p, c->ctrl.p);
                 first = false;
-                SCAL_TRY(refine_sweep(c, n, K, nb, max2, dense));
+                SCAL_TRY(refine_sweep(c, n, K, nb, max2, dense, plane));
                 for (int f = 0; f < K; ++f) {
                     if (!fr[f].active) continue;
                     float T[16];
-                    const int step = icp_host_step(fr[f].is, c->h_sums.p + ICP_NSUM * f, c->cfg.max_iterations, te, fe, T);
+                    int step;
+                    if constexpr (plane) {
+                        if (fr[f].is.it == 0) std::memcpy(res[f].first_eq, h_sums + NS * f + 1, sizeof res[f].first_eq);
+                        step = icp_plane_host_step(fr[f].is, h_sums + NS * f, c->cfg.max_iterations, te, fe, T);
+                    } else {
+                        step = icp_host_step(fr[f].is, h_sums + NS * f, c->cfg.max_iterations, te, fe, T);
+                    }
                     if (step == ICP_STEP_CONTINUE)
                         std::memcpy(c->h_ctrl.p[f].m, T, sizeof(float) * 12);
                     else  // finished: the fitness sweep moves the frame by the whole transformation, the last increment need not be applied
@@ -401,16 +484,23 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const int* offsets
             }
             SCAL_HIP(hipMemcpyAsync(c->ctrl.p, c->h_ctrl.p, sizeof(RfCtrl) * K, hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(k_rf_apply, dim3(nb), dim3(256), 0, s, c->g.p, c->cur.p, c->blocks.p, c->ctrl.p);
-            SCAL_TRY(refine_sweep(c, n, K, nb, max2, dense));
+            SCAL_TRY(refine_sweep(c, n, K, nb, max2, dense, plane));
         }
         // 5. results and poses
         bool moved = false;
         for (int f = 0; f < K; ++f) {
-            scal_refine_frame_result& r = res[f];
+            Res& r = res[f];
             const IcpIterState& is = fr[f].is;
             r.converged = is.converged ? 1 : 0, r.iterations = is.it, r.state = is.st, r.n_correspondences = is.n_corr;
-            const double* sums = c->h_sums.p + ICP_NSUM * f;
-            r.fitness = fr[f].runs && sums[0] > 0 ? sums[16] / sums[0] : dmax;
+            const double* sums = h_sums + NS * f;
+            r.fitness = fr[f].runs && sums[0] > 0 ? sums[plane ? 29 : 16] / sums[0] : dmax;
+            if constexpr (plane) {
+                r.plane_fitness = fr[f].runs && sums[0] > 0 ? sums[28] / sums[0] : dmax;
+                if (fr[f].runs)
+                    std::memcpy(r.normal_eq, sums + 1, sizeof r.normal_eq);
+                else  // a frame that does not run has no sweep, in this round or (its first_eq) in an earlier one
+                    std::memset(r.normal_eq, 0, sizeof r.normal_eq), std::memset(r.first_eq, 0, sizeof r.first_eq);
+            }
             for (int k = 0; k < 16; ++k) r.T[k] = is.F[k];
             r.accepted = fr[f].runs && is.converged && r.fitness <= c->cfg.fitness_gate ? 1 : 0;
             if (!r.accepted) continue;
@@ -437,7 +527,7 @@ extern "C" int scal_refine_run_device(scal_refine_t* c, const float* d_xyzi, con
                                       double near_thres, int rounds, scal_refine_frame_result* res, int* rounds_run) {
     SCAL_TRY(refine_check_args(c, d_xyzi, offsets, n_frames, poses12, near_thres, rounds, res, rounds_run));
     SCAL_HIP(hipSetDevice(c->cfg.device));
-    return refine_rounds(c, reinterpret_cast<const float4*>(d_xyzi), offsets, n_frames, poses12, fixed, near_thres, rounds, res, rounds_run);
+    return refine_rounds(c, reinterpret_cast<const float4*>(d_xyzi), nullptr, offsets, n_frames, poses12, fixed, near_thres, rounds, res, rounds_run);
 }
 
 extern "C" int scal_refine_run(scal_refine_t* c, const float* xyzi, const int* offsets, int n_frames, double* poses12, const unsigned char* fixed,
@@ -447,5 +537,49 @@ extern "C" int scal_refine_run(scal_refine_t* c, const float* xyzi, const int* o
     const int n = offsets[n_frames];
     if (!c->loc.p) SCAL_TRY(c->loc.alloc(static_cast<size_t>(c->cfg.max_points)));
     if (n) SCAL_HIP(hipMemcpyAsync(c->loc.p, xyzi, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream));
-    return refine_rounds(c, c->loc.p, offsets, n_frames, poses12, fixed, near_thres, rounds, res, rounds_run);
+    return refine_rounds(c, c->loc.p, nullptr, offsets, n_frames, poses12, fixed, near_thres, rounds, res, rounds_run);
+}
+
+// what only the point-to-plane calls need, allocated by the first of them and released with the context
+static int refine_plane_prepare(scal_refine* c, bool staging) {
+    const size_t np = static_cast<size_t>(c->cfg.max_points);
+    if (!c->gn.p) SCAL_TRY(c->gn.alloc(np));
+    if (!c->plane_partials.p) SCAL_TRY(c->plane_partials.alloc(static_cast<size_t>(ICP_PLANE_NSUM) * c->nb_cap));
+    if (!c->h_plane.p) SCAL_TRY(c->h_plane.alloc(static_cast<size_t>(ICP_PLANE_NSUM) * c->cfg.max_frames));
+    if (staging && !c->nloc.p) SCAL_TRY(c->nloc.alloc(np));
+    return SCAL_OK;
+}
+
+static int refine_plane_check_args(scal_refine* c, const float* xyzi, const float* nc, const int* offsets, int n_frames, double* poses12, double near_thres,
+                                   int rounds, const void* res, int* rounds_run) {
+    SCAL_TRY(refine_check_args(c, xyzi, offsets, n_frames, poses12, near_thres, rounds, res, rounds_run));
+    if (offsets[n_frames] > 0 && !nc) {
+        set_error("scal_refine_run_plane: bad argument (no normals)");
+        return SCAL_E_ARG;
+    }
+    return SCAL_OK;
+}
+
+extern "C" int scal_refine_run_plane_device(scal_refine_t* c, const float* d_xyzi, const float* d_nc, const int* offsets, int n_frames, double* poses12,
+                                            const unsigned char* fixed, double near_thres, int rounds, scal_refine_plane_frame_result* res,
+                                            int* rounds_run) {
+    SCAL_TRY(refine_plane_check_args(c, d_xyzi, d_nc, offsets, n_frames, poses12, near_thres, rounds, res, rounds_run));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(refine_plane_prepare(c, false));
+    return refine_rounds(c, reinterpret_cast<const float4*>(d_xyzi), reinterpret_cast<const float4*>(d_nc), offsets, n_frames, poses12, fixed, near_thres,
+                         rounds, res, rounds_run);
+}
+
+extern "C" int scal_refine_run_plane(scal_refine_t* c, const float* xyzi, const float* nc, const int* offsets, int n_frames, double* poses12,
+                                     const unsigned char* fixed, double near_thres, int rounds, scal_refine_plane_frame_result* res, int* rounds_run) {
+    SCAL_TRY(refine_plane_check_args(c, xyzi, nc, offsets, n_frames, poses12, near_thres, rounds, res, rounds_run));
+    SCAL_HIP(hipSetDevice(c->cfg.device));
+    SCAL_TRY(refine_plane_prepare(c, true));
+    const int n = offsets[n_frames];
+    if (!c->loc.p) SCAL_TRY(c->loc.alloc(static_cast<size_t>(c->cfg.max_points)));
+    if (n) {
+        SCAL_HIP(hipMemcpyAsync(c->loc.p, xyzi, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream));
+        SCAL_HIP(hipMemcpyAsync(c->nloc.p, nc, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream));
+    }
+    return refine_rounds(c, c->loc.p, c->nloc.p, offsets, n_frames, poses12, fixed, near_thres, rounds, res, rounds_run);
 }

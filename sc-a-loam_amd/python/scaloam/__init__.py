@@ -92,6 +92,12 @@ class RefineFrameResult(C.Structure):
                 ("accepted", C.c_int), ("fitness", C.c_double), ("T", C.c_double * 16)]
 
 
+class RefinePlaneFrameResult(C.Structure):
+    _fields_ = [("converged", C.c_int), ("iterations", C.c_int), ("state", C.c_int), ("n_correspondences", C.c_int),
+                ("accepted", C.c_int), ("fitness", C.c_double), ("T", C.c_double * 16), ("plane_fitness", C.c_double),
+                ("normal_eq", C.c_double * 27), ("first_eq", C.c_double * 27)]
+
+
 class RelocConfig(C.Structure):
     _fields_ = [("max_keyframes", C.c_int), ("max_points", C.c_int), ("max_query_points", C.c_int), ("sc_max_radius", C.c_double),
                 ("sc_dist_thres", C.c_double), ("float_math", C.c_int), ("leaf", C.c_float), ("submap_half", C.c_int),
@@ -208,6 +214,7 @@ EXPORTED_SYMBOLS = [
     "scal_nbr_knn", "scal_nbr_knn_device", "scal_nbr_knn_self",
     "scal_nbr_normals", "scal_nbr_normals_device", "scal_nbr_normals_self",
     "scal_icp_align_plane", "scal_icp_align_plane_device",
+    "scal_refine_run_plane", "scal_refine_run_plane_device",
 ]
 
 _lib = None
@@ -313,6 +320,9 @@ def lib():
         L.scal_refine_destroy.restype = None
         for fn in (L.scal_refine_run_device, L.scal_refine_run):
             fn.argtypes = [vp, vp, _i32p, C.c_int, _f64p, C.c_char_p, C.c_double, C.c_int, C.POINTER(RefineFrameResult), _i32p]
+    if hasattr(L, "scal_refine_run_plane"):  # absent from older builds compared through SCALOAM_LIB
+        for fn in (L.scal_refine_run_plane_device, L.scal_refine_run_plane):
+            fn.argtypes = [vp, vp, vp, _i32p, C.c_int, _f64p, C.c_char_p, C.c_double, C.c_int, C.POINTER(RefinePlaneFrameResult), _i32p]
     L.scal_mapmerge_create.argtypes = [C.POINTER(MapMergeConfig), C.POINTER(vp)]
     L.scal_mapmerge_destroy.argtypes = [vp]
     L.scal_mapmerge_destroy.restype = None
@@ -1034,7 +1044,9 @@ class MultiviewRefine:
 
     __del__ = close
 
-    def _run(self, fn, ptr, offsets, poses12, fixed, rounds, near_thres):
+    def _run(self, fn, ptr, offsets, poses12, fixed, rounds, near_thres, nc_ptr=None):
+        """nc_ptr: the normals beside the records - fn is one of the scal_refine_run_plane* calls"""
+        plane = nc_ptr is not None
         off = np.ascontiguousarray(offsets, np.int32)
         k = off.shape[0] - 1
         P = np.array(poses12, np.float64).reshape(-1, 12).copy()
@@ -1045,12 +1057,16 @@ class MultiviewRefine:
             fx = np.ascontiguousarray(np.asarray(fixed) != 0, np.uint8)
             if fx.shape[0] != k:
                 raise ValueError("one fixed flag per frame is needed")
-        res = (RefineFrameResult * max(k, 1))()
+        res = ((RefinePlaneFrameResult if plane else RefineFrameResult) * max(k, 1))()
         run = C.c_int(0)
-        _check(fn(self.h, ptr, _p(off, _i32p), k, _p(P, _f64p), fx.ctypes.data_as(C.c_char_p) if fx is not None else None,
-                  float(near_thres), int(rounds), res, C.byref(run)))
+        tail = (_p(off, _i32p), k, _p(P, _f64p), fx.ctypes.data_as(C.c_char_p) if fx is not None else None, float(near_thres), int(rounds),
+                res, C.byref(run))
+        _check(fn(self.h, ptr, nc_ptr, *tail) if plane else fn(self.h, ptr, *tail))
         out = [dict(converged=bool(r.converged), iterations=r.iterations, state=r.state, n_correspondences=r.n_correspondences,
                     accepted=bool(r.accepted), fitness=r.fitness, T=np.array(r.T[:]).reshape(4, 4)) for r in res[:k]]
+        if plane:
+            for d, r in zip(out, res[:k]):
+                d.update(plane_fitness=r.plane_fitness, normal_eq=np.array(r.normal_eq[:]), first_eq=np.array(r.first_eq[:]))
         return P, out, run.value
 
     def refine(self, frames, poses12, fixed=None, rounds=1, near_thres=2.0):
@@ -1066,6 +1082,27 @@ class MultiviewRefine:
     def refine_device(self, d_xyzi_ptr, offsets, poses12, fixed=None, rounds=1, near_thres=2.0):
         """the frames as 16-byte xyzi records back to back in device memory, frame f = records [offsets[f], offsets[f+1])"""
         return self._run(lib().scal_refine_run_device, d_xyzi_ptr, offsets, poses12, fixed, rounds, near_thres)
+
+    def refine_plane(self, frames, normals, poses12, fixed=None, rounds=1, near_thres=2.0):
+        """The refine with the point-to-plane metric (scal_refine_run_plane).  normals: per frame the [n, 4] normals and curvatures of
+        its points among themselves, in the frame's local coordinates, as RadiusIndex.normals_self or
+        scaloam.refine_plane.frame_normals give them; computed once, they serve every round and every pose.  The dicts carry
+        plane_fitness, normal_eq and first_eq besides refine's fields.  The CPU restatement is scaloam.refine_plane.refine_plane."""
+        fs, ns = [_f32(f).reshape(-1, 4) for f in frames], [_f32(a).reshape(-1, 4) for a in normals]
+        if len(ns) != len(fs) or any(a.shape[0] != f.shape[0] for a, f in zip(ns, fs)):
+            raise ValueError("one [n, 4] array of normals per frame, one row per point, is needed")
+        off = np.zeros(len(fs) + 1, np.int64)
+        off[1:] = np.cumsum([f.shape[0] for f in fs])
+        if off[-1] > 2**31 - 1:
+            raise ValueError("more points than 32-bit offsets hold")
+        cat = np.ascontiguousarray(np.concatenate(fs, 0)) if fs else np.zeros((0, 4), np.float32)
+        ncat = np.ascontiguousarray(np.concatenate(ns, 0)) if ns else np.zeros((0, 4), np.float32)
+        return self._run(lib().scal_refine_run_plane, cat.ctypes.data_as(C.c_void_p), off, poses12, fixed, rounds, near_thres,
+                         ncat.ctypes.data_as(C.c_void_p))
+
+    def refine_plane_device(self, d_xyzi_ptr, d_nc_ptr, offsets, poses12, fixed=None, rounds=1, near_thres=2.0):
+        """records and normals back to back in device memory, frame f = rows [offsets[f], offsets[f+1]) of both"""
+        return self._run(lib().scal_refine_run_plane_device, d_xyzi_ptr, offsets, poses12, fixed, rounds, near_thres, C.c_void_p(d_nc_ptr))
 
 
 def yaw_guess(yaw_rad):

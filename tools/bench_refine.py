@@ -7,7 +7,8 @@ perturbed by a seeded few decimetres, cap 2 m.
       the others) - what the library could do before.  Where the whole loop is projected to take more than --loop-budget seconds it
       is run on the first --loop-sample frames only and the total is extrapolated (flagged in the output).
 Wall times are the median of 5 after one warm-up.  Writes one JSON document (default profiles/refine.json) and prints it.
-`--only-refine` runs (a) alone, for a separate run under rocprofv3 --kernel-trace --stats (the program goes after `--`)."""
+`--only-refine` runs (a) alone, for a separate run under rocprofv3 --kernel-trace --stats (the program goes after `--`).
+`--plane` measures scal_refine_run_plane_device beside (a) on the smallest set of --ks instead and writes profiles/refine_plane.json."""
 import argparse
 import json
 import os
@@ -68,14 +69,71 @@ def nn_bytes_per_query(G, goff, sample=4000, seed=3):
             "ring1_candidates_per_query": float(cand.mean()), "ring1_bytes_per_query": float(27 * 16 + 16 * cand.mean() + 16)}
 
 
+def plane_set(S, torch, frames, clean, poses, K, out_path, gen_s):
+    """--plane: the point-to-plane refine (scal_refine_run_plane_device) beside the point refine on the same K frames in the same
+    process - sweeps per round, wall median of 5, the library's per-kernel times (a separate, profiled call each), the one-off cost
+    of the K per-frame normals, the median translation error before and after one round"""
+    fr = frames[:K]
+    off = np.concatenate([[0], np.cumsum([f.shape[0] for f in fr])]).astype(np.int64)
+    n = int(off[-1])
+    d_loc = torch.from_numpy(np.ascontiguousarray(np.concatenate(fr), np.float32)).cuda()
+    m = max(f.shape[0] for f in fr)
+    idx = S.RadiusIndex(m, m)
+
+    def all_normals():
+        ncs = []
+        for f in fr:
+            idx.set_index(f, 0.8)
+            ncs.append(idx.normals_self(10)[0].copy())
+        return ncs
+    ms_n, ncs = median_ms(all_normals)
+    idx.close()
+    d_nc = torch.from_numpy(np.ascontiguousarray(np.concatenate(ncs), np.float32)).cuda()
+    rf = S.MultiviewRefine(K, n, max_corr_dist=2.0)
+    runs = {"point": lambda: rf.refine_device(d_loc.data_ptr(), off, poses[:K], rounds=1),
+            "plane": lambda: rf.refine_plane_device(d_loc.data_ptr(), d_nc.data_ptr(), off, poses[:K], rounds=1)}
+    before = np.linalg.norm(poses[:K, [3, 7, 11]] - clean[:K, [3, 7, 11]], axis=1)
+    out = {"metric": "multiview refine, point-to-plane beside point-to-point, ms per round", "unit": "ms", "sensor": "HDL-64 synthetic", "leaf_m": 0.4,
+           "max_corr_dist_m": 2.0, "rounds": 1, "keyframes": K, "points": n, "generation_s": gen_s,
+           "normals": {"k": 10, "r_m": 0.8, "ms_all_frames": ms_n, "ms_per_frame": ms_n / K,
+                       "finite": int(sum(int(np.isfinite(c[:, :3]).all(1).sum()) for c in ncs))},
+           "translation_error_m": {"before_median": float(np.median(before))}}
+    for name, fn in runs.items():
+        ms, (P, res, _) = median_ms(fn)
+        its = np.array([r["iterations"] for r in res])
+        after = np.linalg.norm(P[:, [3, 7, 11]] - clean[:K, [3, 7, 11]], axis=1)
+        S.prof_reset()
+        S.prof_enable(True)
+        fn()
+        S.prof_enable(False)
+        kern = {k: {"ms": v[0], "launches": v[1]} for k, v in S.prof_read_all().items() if v[1]}
+        S.prof_reset()
+        out[name] = {"refine_ms": ms, "sweeps_per_round": int(its.max()) + 1, "iterations_max": int(its.max()), "iterations_sum": int(its.sum()),
+                     "ms_per_sweep": ms / (int(its.max()) + 1), "accepted": int(sum(r["accepted"] for r in res)),
+                     "converged": int(sum(r["converged"] for r in res)), "states": {str(s): int(c) for s, c in zip(*np.unique([r["state"] for r in res], return_counts=True))},
+                     "translation_error_after_median_m": float(np.median(after)), "kernels": kern}
+    rf.close()
+    out["value"] = out["plane"]["refine_ms"]
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", type=int, nargs="+", default=[64, 512, 2000])
     ap.add_argument("--only-refine", action="store_true")
     ap.add_argument("--loop-budget", type=float, default=60.0)
     ap.add_argument("--loop-sample", type=int, default=16)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refine.json"))
+    ap.add_argument("--plane", action="store_true", help="the point-to-plane refine beside the point refine on the smallest set of --ks")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "refine_plane.json" if a.plane else "refine.json")
+    if a.plane:
+        a.ks = [min(a.ks)]
     import torch
     torch.cuda.set_device(0)  # torch's HIP context first, as in bench.py
     torch.zeros(1, device="cuda")
@@ -98,6 +156,9 @@ def main():
     vg.close()
     clean, poses = np.array(clean), np.array(poses)
     gen_s = time.perf_counter() - t0
+    if a.plane:
+        plane_set(S, torch, frames, clean, poses, kmax, a.out, gen_s)
+        return
     out = {"metric": "multiview refine, keyframes/s", "unit": "keyframes/s", "sensor": "HDL-64 synthetic", "leaf_m": 0.4, "max_corr_dist_m": 2.0,
            "rounds": 1, "generation_s": gen_s, "sets": {}}
     for K in a.ks:

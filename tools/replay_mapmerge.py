@@ -3,7 +3,9 @@
 optimized_poses.txt), merges the keyframes into the global frame (near-range removal 2 m) with scal_mapmerge_*, writes the map as
 a binary PCD.  `--check` also runs the CPU oracle and compares bit for bit.  `--refine ROUNDS` first refines the poses with
 scal_refine_* (every keyframe thinned at --refine-leaf and aligned against all the others, keyframe 0 held), writes them to
-refined_poses.txt beside the session's optimized_poses.txt and merges with them.  `--remove-dynamic` runs scal_removert_* on the merged map
+refined_poses.txt beside the session's optimized_poses.txt and merges with them; with `--refine-plane K[,R]` the refine uses the
+point-to-plane metric (scal_refine_run_plane) on each thinned keyframe's own normals, the plane through a point's K nearest
+neighbours within R (default 0.8 m) of its keyframe (scal_nbr_normals_self).  `--remove-dynamic` runs scal_removert_* on the merged map
 where it lies in device memory, with the poses the merge used (the refined ones after --refine), reports the counts and writes the
 static points beside the map as *_static.pcd - after VoxelGrid(--leaf) if a leaf is given.  `--radius-filter R,MIN` drops the isolated
 returns before either map is written: a point stays iff more than MIN points of the merged map, itself included, lie within R
@@ -44,7 +46,21 @@ def main():
     ap.add_argument("--sor-filter", default=None, metavar="MEAN_K,STD_MUL[,R0]",
                     help="keep a point iff its mean distance to its MEAN_K nearest neighbours is within STD_MUL standard deviations of the map's mean")
     ap.add_argument("--normals", default=None, metavar="K[,R]", help="write *_normals.pcd: normals and curvature from the K nearest neighbours within R")
+    ap.add_argument("--refine-plane", default=None, metavar="K[,R]",
+                    help="with --refine: the point-to-plane metric on each thinned keyframe's own normals, K nearest neighbours within R")
     a = ap.parse_args()
+    refine_plane = None
+    if a.refine_plane:
+        try:
+            f = a.refine_plane.split(",")
+            refine_plane = (int(f[0]), float(f[1]) if len(f) > 1 else 0.8)
+            ok = len(f) in (1, 2) and 3 <= refine_plane[0] <= 64 and np.isfinite(refine_plane[1]) and refine_plane[1] > 0
+        except (ValueError, IndexError):
+            ok = False
+        if not ok:
+            ap.error("--refine-plane takes K[,R]: K in 3 .. 64, R > 0")
+        if a.refine <= 0:
+            ap.error("--refine-plane needs --refine ROUNDS")
     normals = None
     if a.normals:
         try:
@@ -78,7 +94,18 @@ def main():
         rf = S.MultiviewRefine(len(thin), sum(t.shape[0] for t in thin) + 1, max_corr_dist=a.max_corr)
         fixed = np.zeros(len(thin), np.uint8)
         fixed[0] = 1
-        poses, res, run = rf.refine(thin, poses, fixed=fixed, rounds=a.refine, near_thres=a.near)
+        if refine_plane:
+            idx = S.RadiusIndex(max(t.shape[0] for t in thin), max(t.shape[0] for t in thin))
+            ncs = []
+            for t in thin:
+                idx.set_index(t, refine_plane[1])
+                ncs.append(idx.normals_self(refine_plane[0])[0].copy())
+            idx.close()
+            print(f"refine-plane: {sum(int(np.isfinite(n[:, 0]).sum()) for n in ncs)} of {sum(t.shape[0] for t in thin)} thinned points have a "
+                  f"normal ({refine_plane[0]} nearest within {refine_plane[1]} m of their own keyframe)")
+            poses, res, run = rf.refine_plane(thin, ncs, poses, fixed=fixed, rounds=a.refine, near_thres=a.near)
+        else:
+            poses, res, run = rf.refine(thin, poses, fixed=fixed, rounds=a.refine, near_thres=a.near)
         print(f"refine: {run} round(s), {sum(r['accepted'] for r in res)} of {len(res)} keyframes accepted in the last one")
         path = os.path.join(a.data_dir, "refined_poses.txt")
         F.write_poses(path, poses)
