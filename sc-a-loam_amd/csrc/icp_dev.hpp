@@ -129,12 +129,26 @@ __device__ __forceinline__ void icp_dense_tile(const float4* __restrict__ cur, c
     }
 }
 
+// ---- the tail of both sums below: a workgroup of 256 threads, NS f64 terms a thread ----------------------------------------------------
+// Every sum: wave_sum, then the four waves as ((r0 + r1) + r2) + r3 -> partials[0 .. NS).  The kernels and their CPU restatements
+// are held to this order of additions bit for bit.
+template <int NS>
+__device__ __forceinline__ void icp_block_sums(const double (&v)[NS], double* __restrict__ partials) {
+    __shared__ double red[4][NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane_id() == 0) red[wave_id()][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) partials[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
 // ---- the 17 correspondence sums of one workgroup of 256 source points ----------------------------------------------------------------
 // Thread t owns source point i (has == false: none).  Reads its key and resets it for the next sweep; a correspondence within the
-// cap (max2, squared) adds 1, p, q, q p^T and d^2 in f64; wave_sum, then the four waves as ((r0 + r1) + r2) + r3 -> partials[0 .. 17).
+// cap (max2, squared) adds 1, p, q, q p^T and d^2 in f64; icp_block_sums -> partials[0 .. 17).
 __device__ __forceinline__ void icp_corr_sums(const float4* __restrict__ cur, const float4* __restrict__ tgt, unsigned long long* __restrict__ best,
                                               float max2, int i, bool has, double* __restrict__ partials) {
-    __shared__ double red[4][ICP_NSUM];
     double v[ICP_NSUM];
 #pragma unroll
     for (int k = 0; k < ICP_NSUM; ++k) v[k] = 0.0;
@@ -156,23 +170,16 @@ __device__ __forceinline__ void icp_corr_sums(const float4* __restrict__ cur, co
             v[16] = d;
         }
     }
-#pragma unroll
-    for (int k = 0; k < ICP_NSUM; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane_id() == 0) red[wave_id()][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < ICP_NSUM) partials[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    icp_block_sums(v, partials);
 }
 
 // ---- the 32 point-to-plane sums of one workgroup of 256 source points (scal_icp_align_plane; the header has the definition) -----------
 // The arguments of icp_corr_sums and the target's normals nc[] (normal, curvature; scal_nbr_normals' layout).  Reads the key and
 // resets it; gathers tgt[idx] and nc[idx]; a correspondence within the cap whose normal is finite makes the row a = (p x n, n),
 // r = (q - p).n in f64 and adds 1, a a^T's upper triangle, a r, r r and d; every query with a neighbour adds 1 and d to [30], [31]
-// whatever the cap and the normal.  Every sum: wave_sum, then the four waves as ((r0 + r1) + r2) + r3 -> partials[0 .. 32).
+// whatever the cap and the normal.  icp_block_sums -> partials[0 .. 32).
 __device__ __forceinline__ void icp_plane_sums(const float4* __restrict__ cur, const float4* __restrict__ tgt, const float4* __restrict__ nc,
                                                unsigned long long* __restrict__ best, float max2, int i, bool has, double* __restrict__ partials) {
-    __shared__ double red[4][ICP_PLANE_NSUM];
     double v[ICP_PLANE_NSUM];
 #pragma unroll
     for (int k = 0; k < ICP_PLANE_NSUM; ++k) v[k] = 0.0;
@@ -205,13 +212,7 @@ __device__ __forceinline__ void icp_plane_sums(const float4* __restrict__ cur, c
             }
         }
     }
-#pragma unroll
-    for (int k = 0; k < ICP_PLANE_NSUM; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane_id() == 0) red[wave_id()][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < ICP_PLANE_NSUM) partials[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    icp_block_sums(v, partials);
 }
 
 // ---- the rigid increment applied to a point, f32 as PCL does: rows of the 3x4 matrix m, .w kept ---------------------------------------

@@ -3,10 +3,9 @@
 // primitive behind the session map diff and the radius outlier filter.
 //
 // One context, one stream (lane 0).  set_index:
-//   k_nb_keys -> RadixSort (stable, 48-bit keys) -> k_nb_index (records in cell order with their input position in .w, the cells'
-//   [start, end) ranges behind an open-addressing hash table) - the shape of refine.hip's k_rf_keys / k_rf_index, with the key, the
-//   clamp, the slot function and the table's insert shared with it through cellhash_dev.hpp (which holds the lookup as well).
-// query: the queries are sorted by the same key (k_nb_keys, RadixSort, k_nb_gather; a self query reuses the index's own order), then
+//   SparseCells::build (cell_index.hpp, the index refine.hip uses as well): records in cell order with their input position in .w,
+//   the cells' [start, end) ranges behind an open-addressing hash table; its two launches are timed as k_nb_keys and k_nb_index.
+// query: the queries are sorted by the same key (SparseCells::sort, k_nb_gather; a self query reuses the index's own order), then
 //   k_nb_query: one wave per 64 consecutive sorted queries, a query per lane.  The wave takes the runs of equal cells among its 64
 //   queries one after the other (a run that crosses a multiple of 64 is cut there): such a piece is a work item - up to 64 queries of
 //   ONE cell, so the 27 cell ranges around it are wave-uniform.  Lanes 0 .. 26 look one range up each; the wave then streams the
@@ -38,32 +37,17 @@
 // the difference <= 1.  So the 27 cells around a query's cell hold every record within r: an argument, no slack factor; the cost is
 // a cell up to twice r wide.
 #include "common.hpp"
-#include "cellhash_dev.hpp"
-#include "radix_sort.hpp"
+#include "cell_index.hpp"
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <type_traits>
 
 namespace scal {
 
-// cell coordinates: 17 bits in x and y, 14 in z, clamped beyond (refine.hip's layout)
-constexpr int NB_XB = 17, NB_ZB = 14, NB_KEY_BITS = 2 * NB_XB + NB_ZB;
-constexpr unsigned long long NB_NO_CELL = (1ull << NB_KEY_BITS) - 1;  // records that are not finite: sorted behind every cell, in no cell
 constexpr unsigned NB_INF = 0x7f800000u;
 
 __device__ __forceinline__ bool nb_finite(const float4 p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
-__device__ __forceinline__ int nb_coord(float v, float inv, int bits) { return ch_clamp_coord(v * inv, bits); }
-// key of cell (x, y, z), NB_NO_CELL outside the coordinate range (nothing is stored there)
-__device__ __forceinline__ unsigned long long nb_key(int x, int y, int z) { return ch_key<NB_XB, NB_ZB>(x, y, z); }
-
-__global__ void __launch_bounds__(256) k_nb_keys(const float4* __restrict__ pts, int n, float inv, unsigned long long* __restrict__ keys,
-                                                 int* __restrict__ vals) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = pts[i];
-    keys[i] = nb_finite(p) ? nb_key(nb_coord(p.x, inv, NB_XB), nb_coord(p.y, inv, NB_XB), nb_coord(p.z, inv, NB_ZB)) : NB_NO_CELL;
-    vals[i] = i;
-}
 
 // sorted position i: the record with its input position in .w (the queries of a set, in cell order)
 __global__ void __launch_bounds__(256) k_nb_gather(const int* __restrict__ vals, int n, const float4* __restrict__ pts, float4* __restrict__ sorted) {
@@ -73,23 +57,6 @@ __global__ void __launch_bounds__(256) k_nb_gather(const int* __restrict__ vals,
     float4 p = pts[idx];
     p.w = __int_as_float(idx);
     sorted[i] = p;
-}
-
-// the same for the index, and the first and the last position of a cell enter the cell's range into the hash table
-__global__ void __launch_bounds__(256) k_nb_index(const unsigned long long* __restrict__ keys, const int* __restrict__ vals, int n,
-                                                  const float4* __restrict__ pts, float4* __restrict__ sorted, unsigned long long* __restrict__ hkeys,
-                                                  int2* __restrict__ hrange, unsigned mask) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long key = keys[i];
-    const int idx = vals[i];
-    float4 p = pts[idx];
-    p.w = __int_as_float(idx);
-    sorted[i] = p;
-    if (key == NB_NO_CELL) return;
-    const bool head = i == 0 || keys[i - 1] != key, tail = i == n - 1 || keys[i + 1] != key;
-    if (!head && !tail) return;
-    ch_insert(hkeys, hrange, mask, key, i, head, tail);
 }
 
 __device__ __forceinline__ float nb_lane_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
@@ -104,10 +71,9 @@ __device__ __forceinline__ float nb_lane_f(float v, int lane) { return __int_as_
 //   end(mine)              at the end of a work item.
 // stats: [0] (query, record) pairs tested, [1] work items - the same for every kernel, since they depend on nothing a callable does.
 template <class Begin, class Visit, class End>
-__device__ __forceinline__ void nb_visit(const float4 q, const bool fin, const int lane, const float inv, const unsigned long long* __restrict__ hkeys,
-                                         const int2* __restrict__ hrange, const unsigned mask, const float4* __restrict__ sorted,
+__device__ __forceinline__ void nb_visit(const float4 q, const bool fin, const int lane, const CellView ix,
                                          unsigned long long* __restrict__ stats, Begin begin, Visit visit, End end) {
-    const int cx = nb_coord(q.x, inv, NB_XB), cy = nb_coord(q.y, inv, NB_XB), cz = nb_coord(q.z, inv, NB_ZB);
+    const int cx = ix.cx(q.x), cy = ix.cx(q.y), cz = ix.cz(q.z);
     unsigned long long waiting = __ballot(fin), pairs = 0;
     int items = 0;
     while (waiting) {
@@ -118,9 +84,8 @@ __device__ __forceinline__ void nb_visit(const float4 q, const bool fin, const i
         int s0 = 0, e0 = 0;
         if (lane < 27) {
             const int az = lane / 9, ay = (lane - 9 * az) / 3, ax = lane - 9 * az - 3 * ay;
-            const unsigned long long key = nb_key(lx + ax - 1, ly + ay - 1, lz + az - 1);
             int2 r;
-            if (key != NB_NO_CELL && ch_find(hkeys, hrange, mask, key, r)) s0 = r.x, e0 = r.y;
+            if (ix.find(lx + ax - 1, ly + ay - 1, lz + az - 1, r)) s0 = r.x, e0 = r.y;
         }
         begin();
         int seen = 0;
@@ -129,7 +94,7 @@ __device__ __forceinline__ void nb_visit(const float4 q, const bool fin, const i
             seen += e - s;
             for (int b = s; b < e; b += 64) {
                 const int m = __builtin_amdgcn_readfirstlane(min(64, e - b));  // keeps the loop counter on the scalar side
-                const float4 p = lane < m ? sorted[b + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 p = lane < m ? ix.sorted[b + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
                 for (int j = 0; j < m; ++j) {
                     const float dx = q.x - nb_lane_f(p.x, j), dy = q.y - nb_lane_f(p.y, j), dz = q.z - nb_lane_f(p.z, j);
                     visit(mine, (dx * dx + dy * dy) + dz * dz, p, j);
@@ -149,8 +114,7 @@ __device__ __forceinline__ void nb_visit(const float4 q, const bool fin, const i
 
 // qs: nq queries in cell order with their output position in .w; a wave per 64 of them (four waves per block, independent).
 // cnt_out / d2_out may be null.
-__global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs, int nq, float inv, float r2, const unsigned long long* __restrict__ hkeys,
-                                                  const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
+__global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs, int nq, float r2, const CellView ix,
                                                   unsigned short* __restrict__ cnt_out, float* __restrict__ d2_out, unsigned long long* __restrict__ stats) {
     const int lane = threadIdx.x & 63;
     const int i = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 64 + lane;
@@ -165,7 +129,7 @@ __global__ void __launch_bounds__(256) k_nb_query(const float4* __restrict__ qs,
     int count = 0;
     float best = __uint_as_float(NB_INF);
     nb_visit(
-        q, fin, lane, inv, hkeys, hrange, mask, sorted, stats, [&] { count = 0, best = __uint_as_float(NB_INF); },
+        q, fin, lane, ix, stats, [&] { count = 0, best = __uint_as_float(NB_INF); },
         [&](bool, float d2, const float4&, int) {  // every lane counts, its own work item or not: a predicate here is an issue per record
             if (d2 <= r2) {
                 ++count;
@@ -195,10 +159,9 @@ constexpr unsigned long long NB_NO_KEY = ~0ull;  // above every key: d2 bits are
 // nb_visit by hand (the tests pin equal statistics across the calls).  With the insertion passed to nb_visit as a callable - or
 // to any other function - the record and insertion loops compile to the same instructions in other registers, and k_nb_knn and
 // k_nb_normals then run between 4 % faster and 2 % slower, which is outside what identical builds show.
-__device__ __forceinline__ int nb_knn_lists(const float4 q, const bool fin, const int lane, const int k, const float inv, const float r2,
-                                            const unsigned long long* __restrict__ hkeys, const int2* __restrict__ hrange, const unsigned mask,
-                                            const float4* __restrict__ sorted, unsigned long long* const mylist, unsigned long long* __restrict__ stats) {
-    const int cx = nb_coord(q.x, inv, NB_XB), cy = nb_coord(q.y, inv, NB_XB), cz = nb_coord(q.z, inv, NB_ZB);
+__device__ __forceinline__ int nb_knn_lists(const float4 q, const bool fin, const int lane, const int k, const float r2, const CellView ix,
+                                            unsigned long long* const mylist, unsigned long long* __restrict__ stats) {
+    const int cx = ix.cx(q.x), cy = ix.cx(q.y), cz = ix.cz(q.z);
     int len = 0;
     unsigned long long kth = NB_NO_KEY;
     unsigned long long waiting = __ballot(fin), pairs = 0;
@@ -211,9 +174,8 @@ __device__ __forceinline__ int nb_knn_lists(const float4 q, const bool fin, cons
         int s0 = 0, e0 = 0;
         if (lane < 27) {
             const int az = lane / 9, ay = (lane - 9 * az) / 3, ax = lane - 9 * az - 3 * ay;
-            const unsigned long long key = nb_key(lx + ax - 1, ly + ay - 1, lz + az - 1);
             int2 r;
-            if (key != NB_NO_CELL && ch_find(hkeys, hrange, mask, key, r)) s0 = r.x, e0 = r.y;
+            if (ix.find(lx + ax - 1, ly + ay - 1, lz + az - 1, r)) s0 = r.x, e0 = r.y;
         }
         int seen = 0;
         for (int c = 0; c < 27; ++c) {
@@ -221,7 +183,7 @@ __device__ __forceinline__ int nb_knn_lists(const float4 q, const bool fin, cons
             seen += e - s;
             for (int b = s; b < e; b += 64) {
                 const int m = __builtin_amdgcn_readfirstlane(min(64, e - b));
-                const float4 p = lane < m ? sorted[b + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 p = lane < m ? ix.sorted[b + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
                 for (int j = 0; j < m; ++j) {
                     const float dx = q.x - nb_lane_f(p.x, j), dy = q.y - nb_lane_f(p.y, j), dz = q.z - nb_lane_f(p.z, j);
                     const float d2 = (dx * dx + dy * dy) + dz * dz;
@@ -256,8 +218,7 @@ __device__ __forceinline__ int nb_knn_lists(const float4 q, const bool fin, cons
 
 // idx_out / d2_out [nq][k] may be null.
 template <int KC>
-__global__ void __launch_bounds__(64) k_nb_knn(const float4* __restrict__ qs, int nq, int k, float inv, float r2, const unsigned long long* __restrict__ hkeys,
-                                               const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
+__global__ void __launch_bounds__(64) k_nb_knn(const float4* __restrict__ qs, int nq, int k, float r2, const CellView ix,
                                                int* __restrict__ idx_out, float* __restrict__ d2_out, unsigned long long* __restrict__ stats) {
     __shared__ unsigned long long list[KC * 64];
     const int lane = threadIdx.x;
@@ -267,7 +228,7 @@ __global__ void __launch_bounds__(64) k_nb_knn(const float4* __restrict__ qs, in
     const bool fin = have && nb_finite(q);
     const size_t row = static_cast<size_t>(__float_as_int(q.w)) * static_cast<size_t>(k);
     unsigned long long* const mylist = list + lane;  // slot s at mylist[64 * s]
-    const int len = nb_knn_lists(q, fin, lane, k, inv, r2, hkeys, hrange, mask, sorted, mylist, stats);
+    const int len = nb_knn_lists(q, fin, lane, k, r2, ix, mylist, stats);
     if (have) {  // a query that is not finite has len 0: a fully padded row
         for (int s = 0; s < k; ++s) {
             const bool in = s < len;
@@ -311,6 +272,8 @@ __device__ __forceinline__ void nb_rotate(double& app, double& aqq, double& apq,
 // of the header in f64 on 15 named scalars and writes one float4 and one float through .w: no [n][k] buffer exists on this path.
 // Lanes without a fit (fewer than 3 neighbours, no query) carry A = 0 through the sweeps, which is a no-op, so the wave leaves the
 // sweep loop together on a ballot once every lane's off-diagonals are exactly 0.  nc_out / dist_out may be null.
+// The index comes as loose arguments, not as a CellView like k_nb_query's and k_nb_knn's: with the view as the argument this kernel
+// ran 9 % slower at k = 21 (profiles/cell_index_ab.txt), with the view put together in here it runs as before.
 template <int KC>
 __global__ void __launch_bounds__(64) k_nb_normals(const float4* __restrict__ qs, int nq, int k, float inv, float r2, const unsigned long long* __restrict__ hkeys,
                                                    const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
@@ -324,7 +287,8 @@ __global__ void __launch_bounds__(64) k_nb_normals(const float4* __restrict__ qs
     const bool fin = have && nb_finite(q);
     const int out = __float_as_int(q.w);
     unsigned long long* const mylist = list + lane;
-    const int len = nb_knn_lists(q, fin, lane, k, inv, r2, hkeys, hrange, mask, sorted, mylist, stats);
+    const CellView ix{hkeys, hrange, sorted, mask, inv};
+    const int len = nb_knn_lists(q, fin, lane, k, r2, ix, mylist, stats);
     const int m = len >= 3 ? len : 0;
     const double dm = static_cast<double>(m);
     double sx = 0.0, sy = 0.0, sz = 0.0;
@@ -382,11 +346,9 @@ struct scal_nbr {
     scal_nbr_config cfg;
     LaneStream stream;
     int cap = 0;  // max(max_index_points, max_query_points): a self query has as many queries as the index has records
-    unsigned hmask = 0;
-    DevBuf<float4> stage, sorted, qsorted;  // stage: host records staged in (index or queries), allocated on first use
-    DevBuf<unsigned long long> keys, hkeys, d_stats;
-    DevBuf<int> vals, d_n;
-    DevBuf<int2> hrange;
+    SparseCells ix;  // the index; its sort takes the query sets as well
+    DevBuf<float4> stage, qsorted;  // stage: host records staged in (index or queries), allocated on first use
+    DevBuf<unsigned long long> d_stats;
     DevBuf<unsigned short> d_cnt;
     DevBuf<float> d_d2;
     DevBuf<int> d_kidx;   // k-NN rows staged for the host: allocated at the first k-NN call, grown to the largest n * k so far
@@ -395,9 +357,8 @@ struct scal_nbr {
     bool slots_ok = false;
     DevBuf<float4> d_nc;  // normals staged for the host, cap entries each, allocated when first asked for
     DevBuf<float> d_dist;
-    RadixSort sorter;
     int n = -1;  // -1: no index set
-    float inv = 0.f, r2 = 0.f;
+    float r2 = 0.f;
     long long pairs = 0;
     int work_items = 0;
 };
@@ -412,16 +373,13 @@ extern "C" int scal_nbr_create(const scal_nbr_config* cfg, scal_nbr_t** out) {
     auto* c = new scal_nbr();
     c->cfg = *cfg;
     c->cap = std::max(cfg->max_index_points, cfg->max_query_points);
-    const size_t ni = static_cast<size_t>(cfg->max_index_points), nq = static_cast<size_t>(cfg->max_query_points), nc = static_cast<size_t>(c->cap);
-    size_t slots = 1024;
-    while (slots < 2 * ni) slots <<= 1;
-    c->hmask = static_cast<unsigned>(slots - 1);
+    const size_t nq = static_cast<size_t>(cfg->max_query_points), nc = static_cast<size_t>(c->cap);
+    c->ix.set_names("k_nb_keys", "k_nb_index");
     int rc = SCAL_OK;
     auto A = [&](int r) { if (rc == SCAL_OK) rc = r; };
     A(c->stream.acquire(cfg->device, 0));
-    A(c->sorted.alloc(ni)); A(c->qsorted.alloc(nq)); A(c->keys.alloc(nc)); A(c->vals.alloc(nc)); A(c->d_n.alloc(1));
-    A(c->hkeys.alloc(slots)); A(c->hrange.alloc(slots)); A(c->d_stats.alloc(2)); A(c->d_cnt.alloc(nc)); A(c->d_d2.alloc(nc));
-    A(c->sorter.init(c->cap));
+    A(c->ix.init(cfg->max_index_points, cfg->max_query_points)); A(c->qsorted.alloc(nq));
+    A(c->d_stats.alloc(2)); A(c->d_cnt.alloc(nc)); A(c->d_d2.alloc(nc));
     if (rc != SCAL_OK) {
         scal_nbr_destroy(c);
         return rc;
@@ -435,16 +393,6 @@ extern "C" void scal_nbr_destroy(scal_nbr_t* c) {
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     delete c;
-}
-
-// keys of the n records at pts, sorted: the pairs are in *sp afterwards
-static int nb_sort(scal_nbr* c, const float4* pts, int n, SortedPairs* sp) {
-    hipStream_t s = c->stream;
-    SCAL_HIP(hipMemcpyAsync(c->d_n.p, &n, sizeof(int), hipMemcpyHostToDevice, s));
-    SCAL_LAUNCH_PROF("k_nb_keys", k_nb_keys, dim3(div_up(n, 256)), dim3(256), 0, s, pts, n, c->inv, c->keys.p, c->vals.p);
-    SCAL_HIP(hipGetLastError());
-    SCAL_TRY(c->sorter.sort(s, c->keys.p, c->vals.p, c->d_n.p, n, NB_KEY_BITS, nullptr, sp));
-    return SCAL_OK;
 }
 
 static int nb_check_index(scal_nbr* c, const char* who, const float* xyzi, int n, double radius) {
@@ -468,15 +416,8 @@ static int nb_build(scal_nbr* c, const float4* pts, int n, double radius) {
     // 1 / w for w = the smallest power of two > r: r = mant 2^e with mant in [0.5, 1), so w = 2^e
     int e = 0;
     (void)std::frexp(r, &e);
-    c->inv = std::isinf(c->r2) ? 0.f : std::ldexp(1.f, -std::max(e, -62));
-    SCAL_HIP(hipMemsetAsync(c->hkeys.p, 0xff, sizeof(unsigned long long) * (static_cast<size_t>(c->hmask) + 1), s));
-    if (n > 0) {
-        SortedPairs sp;
-        SCAL_TRY(nb_sort(c, pts, n, &sp));
-        SCAL_LAUNCH_PROF("k_nb_index", k_nb_index, dim3(div_up(n, 256)), dim3(256), 0, s, sp.keys[sp.fixed_sel], sp.vals[sp.fixed_sel], n, pts,
-                         c->sorted.p, c->hkeys.p, c->hrange.p, c->hmask);
-        SCAL_HIP(hipGetLastError());
-    }
+    const float inv = std::isinf(c->r2) ? 0.f : std::ldexp(1.f, -std::max(e, -62));
+    SCAL_TRY(c->ix.build(s, pts, n, inv, std::numeric_limits<float>::infinity()));  // every finite record is in a cell
     SCAL_HIP(hipStreamSynchronize(s));  // the caller's records have been read
     c->n = n;
     return SCAL_OK;
@@ -522,7 +463,7 @@ static int nb_check(scal_nbr* c, const char* who, NbSource src, const float* xyz
 static int nb_sort_queries(scal_nbr* c, const float4* pts, int n) {
     if (n == 0) return SCAL_OK;
     SortedPairs sp;
-    SCAL_TRY(nb_sort(c, pts, n, &sp));
+    SCAL_TRY(c->ix.sort(c->stream, pts, n, &sp));
     SCAL_LAUNCH_PROF("k_nb_gather", k_nb_gather, dim3(div_up(n, 256)), dim3(256), 0, c->stream, sp.vals[sp.fixed_sel], n, pts, c->qsorted.p);
     SCAL_HIP(hipGetLastError());
     return SCAL_OK;
@@ -531,7 +472,7 @@ static int nb_sort_queries(scal_nbr* c, const float4* pts, int n) {
 // a checked call's queries in cell order, output position in .w: *qs, *nq.  A self query runs on the index's own order.
 static int nb_queries(scal_nbr* c, NbSource src, const float* xyzi, int n, const float4** qs, int* nq) {
     if (src == NB_SELF) {
-        *qs = c->sorted.p, *nq = c->n;
+        *qs = c->ix.sorted.p, *nq = c->n;
         return SCAL_OK;
     }
     const float4* pts = reinterpret_cast<const float4*>(xyzi);
@@ -606,8 +547,7 @@ static int nb_query(scal_nbr* c, const char* who, NbSource src, const float* xyz
     int nq;
     SCAL_TRY(nb_queries(c, src, xyzi, n, &qs, &nq));
     SCAL_TRY(nb_run(c, nq, [&](hipStream_t s) -> int {
-        SCAL_LAUNCH_PROF("k_nb_query", k_nb_query, dim3(div_up(nq, 256)), dim3(256), 0, s, qs, nq, c->inv, c->r2, c->hkeys.p, c->hrange.p, c->hmask,
-                         c->sorted.p, d_cnt, d_d2, c->d_stats.p);
+        SCAL_LAUNCH_PROF("k_nb_query", k_nb_query, dim3(div_up(nq, 256)), dim3(256), 0, s, qs, nq, c->r2, c->ix.view(), d_cnt, d_d2, c->d_stats.p);
         return SCAL_OK;
     }));
     return nb_download(c, src, m, cnt, d_cnt, d2, d_d2);
@@ -639,8 +579,8 @@ static int nb_knn(scal_nbr* c, const char* who, NbSource src, const float* xyzi,
     SCAL_TRY(nb_queries(c, src, xyzi, n, &qs, &nq));
     SCAL_TRY(nb_run(c, nq, [&](hipStream_t s) -> int {
         nb_list_class(k, [&](auto kc) {
-            SCAL_LAUNCH_PROF("k_nb_knn", k_nb_knn<decltype(kc)::value>, dim3(div_up(nq, 64)), dim3(64), 0, s, qs, nq, k, c->inv, c->r2, c->hkeys.p,
-                             c->hrange.p, c->hmask, c->sorted.p, d_idx, d_d2, c->d_stats.p);
+            SCAL_LAUNCH_PROF("k_nb_knn", k_nb_knn<decltype(kc)::value>, dim3(div_up(nq, 64)), dim3(64), 0, s, qs, nq, k, c->r2, c->ix.view(),
+                             d_idx, d_d2, c->d_stats.p);
         });
         return SCAL_OK;
     }));
@@ -676,15 +616,15 @@ static int nb_normals(scal_nbr* c, const char* who, NbSource src, const float* x
     SCAL_TRY(nb_run(c, nq, [&](hipStream_t s) -> int {
         if (!c->slot_of.p) SCAL_TRY(c->slot_of.alloc(static_cast<size_t>(c->cfg.max_index_points)));
         if (!c->slots_ok && c->n > 0) {  // from the index's own copy of the records: the caller's are not needed
-            SCAL_LAUNCH_PROF("k_nb_slots", k_nb_slots, dim3(div_up(c->n, 256)), dim3(256), 0, s, c->sorted.p, c->n, c->slot_of.p);
+            SCAL_LAUNCH_PROF("k_nb_slots", k_nb_slots, dim3(div_up(c->n, 256)), dim3(256), 0, s, c->ix.sorted.p, c->n, c->slot_of.p);
             SCAL_HIP(hipGetLastError());
         }
         c->slots_ok = true;
         const int use_vp = vp != nullptr;
         const double vx = vp ? vp[0] : 0.0, vy = vp ? vp[1] : 0.0, vz = vp ? vp[2] : 0.0;
         nb_list_class(k, [&](auto kc) {
-            SCAL_LAUNCH_PROF("k_nb_normals", k_nb_normals<decltype(kc)::value>, dim3(div_up(nq, 64)), dim3(64), 0, s, qs, nq, k, c->inv, c->r2,
-                             c->hkeys.p, c->hrange.p, c->hmask, c->sorted.p, c->slot_of.p, use_vp, vx, vy, vz, d_nc, d_dist, c->d_stats.p);
+            SCAL_LAUNCH_PROF("k_nb_normals", k_nb_normals<decltype(kc)::value>, dim3(div_up(nq, 64)), dim3(64), 0, s, qs, nq, k, c->ix.inv, c->r2,
+                             c->ix.hkeys.p, c->ix.hrange.p, c->ix.mask, c->ix.sorted.p, c->slot_of.p, use_vp, vx, vy, vz, d_nc, d_dist, c->d_stats.p);
         });
         return SCAL_OK;
     }));

@@ -5,12 +5,13 @@
 // Per round:
 //   k_rf_count / k_rf_write   every frame moved by its pose with the map merge's own passes (mapmerge_dev.hpp) -> G, the round's
 //                             target, frames in order, every point with its frame beside it; the sources start as a copy of G
-//   k_rf_keys, RadixSort,     sparse neighbour index over G: 48-bit key of the 1 m cell coordinates, sorted (stable, so a cell's
-//   k_rf_index                points stay in index order), the cells' [start, end) ranges behind an open-addressing hash table in
-//                             HBM.  The cell width does not depend on the map's extent, as icp.hip's dense 2^18-cell grid does.
+//   SparseCells::build        sparse neighbour index over G (cell_index.hpp, the index nbr.hip uses as well) with a 1 m cell: sorted
+//                             by cell (stable, so a cell's points stay in index order), the cells' [start, end) ranges behind a hash
+//                             table in HBM; the index launch is timed as k_rf_index.  The cell width does not depend on the map's
+//                             extent, as icp.hip's dense 2^18-cell grid does.
 // Per iteration, ONE launch chain for all frames still iterating and one host synchronisation:
 //   k_rf_apply    last iteration's increments, one 3x4 matrix per frame (icp_transform)
-//   k_rf_grid_nn  a wave per source point: icp_ring_search with the cells looked up through the hash table (ch_find); a candidate of
+//   k_rf_grid_nn  a wave per source point: icp_ring_search with the cells looked up through the index (CellView::find); a candidate of
 //                 the query's own frame is dropped before the key is formed
 //   k_rf_dense    only when max_corr_dist reaches beyond the last ring: the unsettled queries as a list against all of G, a fixed
 //                 number of workgroups striding over (query tile, target chunk) pairs (icp_dense_tile) - none when the list is empty
@@ -25,12 +26,11 @@
 // Frames that have finished cost an early return per workgroup.  The search, the sums and the transform are icp_dev.hpp's, the same
 // code icp.hip runs: what is written here is where a cell's points are, which candidates count and which point a thread owns.
 #include "common.hpp"
-#include "cellhash_dev.hpp"
+#include "cell_index.hpp"
 #include "device_utils.hpp"
 #include "icp_dev.hpp"
 #include "icp_host.hpp"
 #include "mapmerge_dev.hpp"
-#include "radix_sort.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -42,10 +42,10 @@ namespace scal {
 
 constexpr float RF_CELL = 1.0f;    // cell width in metres; cell coordinate = floor(v), exact in f32
 constexpr int RF_DENSE_WG = 2048;  // workgroups of the dense sweep
-// cell coordinates: 17 bits in x and y (+-65 km), 14 in z (+-8 km), clamped beyond.  Clamping is monotone, so a cell that the ring
+// The index clamps cell coordinates beyond +-65 km in x and y and +-8 km in z.  Clamping is monotone, so a cell that the ring
 // search has not examined is still at least k cells away from the query along some axis and the stop rule holds out there too.
-constexpr int RF_XB = 17, RF_ZB = 14, RF_KEY_BITS = 2 * RF_XB + RF_ZB;
-constexpr unsigned long long RF_NO_CELL = (1ull << RF_KEY_BITS) - 1;  // non-finite points: sorted behind every cell, in no cell
+// A point is in a cell when |v| < 3.4e38 on every axis: any other can never be a nearest neighbour (d < 3.4e38 fails).
+constexpr float RF_FINITE = 3.4e38f;
 
 struct RfBlock {
     int first, end, frame;  // 256 source points of one frame: [first, min(first + 256, end)) of G
@@ -106,38 +106,6 @@ __global__ void __launch_bounds__(256) k_rf_write_nc(const float4* __restrict__ 
     }
 }
 
-__device__ __forceinline__ int rf_coord(float v, int bits) { return ch_clamp_coord(v, bits); }  // NaN -> the lowest cell
-// key of cell (x, y, z), RF_NO_CELL outside the coordinate range (nothing is stored there)
-__device__ __forceinline__ unsigned long long rf_key(int x, int y, int z) { return ch_key<RF_XB, RF_ZB>(x, y, z); }
-
-__global__ void __launch_bounds__(256) k_rf_keys(const float4* __restrict__ g, int n, unsigned long long* __restrict__ keys, int* __restrict__ vals) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = g[i];
-    unsigned long long key = RF_NO_CELL;  // non-finite points can never be a nearest neighbour (d < 3.4e38 fails)
-    if (fabsf(p.x) < 3.4e38f && fabsf(p.y) < 3.4e38f && fabsf(p.z) < 3.4e38f) key = rf_key(rf_coord(p.x, RF_XB), rf_coord(p.y, RF_XB), rf_coord(p.z, RF_ZB));
-    keys[i] = key;
-    vals[i] = i;
-}
-
-// sorted position i: the point itself with its index in G beside it; the first and the last position of a cell enter the cell's
-// range into the hash table (find-or-insert by compare-and-swap; which of the two arrives first does not matter)
-__global__ void __launch_bounds__(256) k_rf_index(const unsigned long long* __restrict__ keys, const int* __restrict__ vals, int n,
-                                                  const float4* __restrict__ g, float4* __restrict__ sorted, unsigned long long* __restrict__ hkeys,
-                                                  int2* __restrict__ hrange, unsigned mask) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long key = keys[i];
-    const int idx = vals[i];
-    float4 p = g[idx];
-    p.w = __int_as_float(idx);
-    sorted[i] = p;
-    if (key == RF_NO_CELL) return;
-    const bool head = i == 0 || keys[i - 1] != key, tail = i == n - 1 || keys[i + 1] != key;
-    if (!head && !tail) return;
-    ch_insert(hkeys, hrange, mask, key, i, head, tail);
-}
-
 // a frame's 3x4 matrix applied to its points: last iteration's increment to the sources in place (in == out), or the whole
 // transformation to the moved frame itself for the fitness sweep (in = G); neither pointer is __restrict__
 __global__ void __launch_bounds__(256) k_rf_apply(const float4* in, float4* out, const RfBlock* __restrict__ blocks, const RfCtrl* __restrict__ ctrl) {
@@ -148,7 +116,9 @@ __global__ void __launch_bounds__(256) k_rf_apply(const float4* in, float4* out,
     out[i] = icp_transform(ctrl[b.frame].m, in[i]);
 }
 
-// one wave per query: icp_dev.hpp's ring search with the cell looked up through the hash table and the query's own frame left out
+// one wave per query: icp_dev.hpp's ring search with the cell looked up through the index and the query's own frame left out.
+// The index comes as loose arguments and the view is put together in here: with a CellView as the argument the kernel ran 1.2 %
+// slower, outside what two identical builds show (profiles/cell_index_ab.txt); this way its code is the one from before.
 __global__ void __launch_bounds__(256) k_rf_grid_nn(const float4* __restrict__ cur, int n, const int* __restrict__ frame_of, const int* __restrict__ goff,
                                                     const RfCtrl* __restrict__ ctrl, const unsigned long long* __restrict__ hkeys,
                                                     const int2* __restrict__ hrange, unsigned mask, const float4* __restrict__ sorted,
@@ -160,13 +130,13 @@ __global__ void __launch_bounds__(256) k_rf_grid_nn(const float4* __restrict__ c
     if (!ctrl[frame].active) return;
     const int own0 = goff[frame], own_n = goff[frame + 1] - own0;  // the frame's points are one index range of G
     const float4 q = cur[qi];
+    const CellView ix{hkeys, hrange, sorted, mask, 1.0f / RF_CELL};
     unsigned long long bk;
     const bool done = icp_ring_search(
-        q, rf_coord(q.x, RF_XB), rf_coord(q.y, RF_XB), rf_coord(q.z, RF_ZB), RF_CELL, sorted,
+        q, ix.cx(q.x), ix.cx(q.y), ix.cz(q.z), RF_CELL, ix.sorted,
         [&](int x, int y, int z, int& s0, int& cnt) {
-            const unsigned long long key = rf_key(x, y, z);
             int2 r;
-            if (key != RF_NO_CELL && ch_find(hkeys, hrange, mask, key, r)) s0 = r.x, cnt = r.y - r.x;
+            if (ix.find(x, y, z, r)) s0 = r.x, cnt = r.y - r.x;
         },
         [&](int ti) { return static_cast<unsigned>(ti - own0) >= static_cast<unsigned>(own_n); }, bk);
     if (lane_id() == 0) {
@@ -234,13 +204,10 @@ struct scal_refine {
     scal_refine_config cfg;
     LaneStream stream;  // released by `delete c`, after scal_refine_destroy has synchronised it
     int nb_mm_cap = 0, nb_cap = 0;  // workgroups of the move (<= max_points / 1024 + max_frames) and of a sweep (<= max_points / 256 + max_frames)
-    unsigned hmask = 0;
-    DevBuf<float4> loc, g, cur, sorted;  // loc: host records staged in (scal_refine_run), allocated on first use
-    DevBuf<int> frame_of, un_list, d_misc;  // d_misc: [0] unresolved count, [1] n (the sort's device count)
-    DevBuf<unsigned long long> best, keys, hkeys;
-    DevBuf<int> vals;
-    DevBuf<int2> hrange;
-    RadixSort sorter;
+    SparseCells ix;  // the round's neighbour index over G
+    DevBuf<float4> loc, g, cur;  // loc: host records staged in (scal_refine_run), allocated on first use
+    DevBuf<int> frame_of, un_list, d_nun;  // d_nun: the unresolved count
+    DevBuf<unsigned long long> best;
     DevBuf<MMBlock> mm_blocks;
     DevBuf<int> blk;       // kept points per move workgroup, then their exclusive prefix
     DevBuf<double> poses, partials;
@@ -273,21 +240,18 @@ int scal::refine_create_on_lane(const scal_refine_config* cfg, int lane, scal_re
     const size_t np = static_cast<size_t>(cfg->max_points), nf = static_cast<size_t>(cfg->max_frames);
     c->nb_mm_cap = static_cast<int>(np / MM_TILE + nf);
     c->nb_cap = static_cast<int>(np / 256 + nf);
-    size_t slots = 1024;
-    while (slots < 2 * np) slots <<= 1;
-    c->hmask = static_cast<unsigned>(slots - 1);
+    c->ix.set_names(nullptr, "k_rf_index");
     int rc = SCAL_OK;
     auto A = [&](int r) { if (rc == SCAL_OK) rc = r; };
-    A(c->g.alloc(np)); A(c->cur.alloc(np)); A(c->sorted.alloc(np)); A(c->frame_of.alloc(np)); A(c->un_list.alloc(np)); A(c->d_misc.alloc(2));
-    A(c->best.alloc(np)); A(c->keys.alloc(np)); A(c->vals.alloc(np)); A(c->hkeys.alloc(slots)); A(c->hrange.alloc(slots));
-    A(c->sorter.init(cfg->max_points));
+    A(c->g.alloc(np)); A(c->cur.alloc(np)); A(c->frame_of.alloc(np)); A(c->un_list.alloc(np)); A(c->d_nun.alloc(1));
+    A(c->best.alloc(np)); A(c->ix.init(cfg->max_points, cfg->max_points));
     A(c->mm_blocks.alloc(c->nb_mm_cap)); A(c->h_mm_blocks.alloc(c->nb_mm_cap)); A(c->blk.alloc(c->nb_mm_cap)); A(c->h_blk.alloc(c->nb_mm_cap));
     A(c->poses.alloc(12 * nf)); A(c->h_poses.alloc(12 * nf)); A(c->partials.alloc(static_cast<size_t>(ICP_NSUM) * c->nb_cap));
     A(c->blocks.alloc(c->nb_cap)); A(c->h_blocks.alloc(c->nb_cap));
     A(c->goff.alloc(nf + 1)); A(c->h_goff.alloc(nf + 1)); A(c->fb0.alloc(nf + 1)); A(c->h_fb0.alloc(nf + 1));
     A(c->ctrl.alloc(nf)); A(c->h_ctrl.alloc(nf)); A(c->h_sums.alloc(ICP_NSUM * nf));
     if (rc == SCAL_OK) rc = c->stream.acquire(cfg->device, lane);
-    if (rc == SCAL_OK && (hipMemsetAsync(c->d_misc.p, 0, 2 * sizeof(int), c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = SCAL_E_HIP;
+    if (rc == SCAL_OK && (hipMemsetAsync(c->d_nun.p, 0, sizeof(int), c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) rc = SCAL_E_HIP;
     if (rc != SCAL_OK) {
         delete c;
         return rc;
@@ -345,18 +309,18 @@ struct RfFrame {
 // plane: the 32 point-to-plane sums on the moved normals c->gn -> c->h_plane instead
 static int refine_sweep(scal_refine* c, int n, int n_frames, int nb, float max2, bool dense, bool plane) {
     hipStream_t s = c->stream;
-    SCAL_LAUNCH_PROF("k_rf_grid_nn", k_rf_grid_nn, dim3(div_up(n, 4)), dim3(256), 0, s, c->cur.p, n, c->frame_of.p, c->goff.p, c->ctrl.p, c->hkeys.p,
-                     c->hrange.p, c->hmask, c->sorted.p, c->best.p, c->un_list.p, c->d_misc.p, dense ? 1 : 0);
+    SCAL_LAUNCH_PROF("k_rf_grid_nn", k_rf_grid_nn, dim3(div_up(n, 4)), dim3(256), 0, s, c->cur.p, n, c->frame_of.p, c->goff.p, c->ctrl.p, c->ix.hkeys.p,
+                     c->ix.hrange.p, c->ix.mask, c->ix.sorted.p, c->best.p, c->un_list.p, c->d_nun.p, dense ? 1 : 0);
     if (dense)
         SCAL_LAUNCH_PROF("k_rf_dense", k_rf_dense, dim3(RF_DENSE_WG), dim3(256), 0, s, c->cur.p, c->g.p, n, c->frame_of.p, c->goff.p, c->best.p,
-                         c->un_list.p, c->d_misc.p);
+                         c->un_list.p, c->d_nun.p);
     if (plane) {
         SCAL_LAUNCH_PROF("k_rf_plane_reduce", k_rf_plane_reduce, dim3(nb), dim3(256), 0, s, c->cur.p, c->g.p, c->gn.p, c->blocks.p, c->ctrl.p, c->best.p,
                          max2, c->plane_partials.p);
-        hipLaunchKernelGGL(k_rf_final<ICP_PLANE_NSUM>, dim3(n_frames), dim3(64), 0, s, c->plane_partials.p, c->fb0.p, c->ctrl.p, c->h_plane.p, c->d_misc.p);
+        hipLaunchKernelGGL(k_rf_final<ICP_PLANE_NSUM>, dim3(n_frames), dim3(64), 0, s, c->plane_partials.p, c->fb0.p, c->ctrl.p, c->h_plane.p, c->d_nun.p);
     } else {
         SCAL_LAUNCH_PROF("k_rf_reduce", k_rf_reduce, dim3(nb), dim3(256), 0, s, c->cur.p, c->g.p, c->blocks.p, c->ctrl.p, c->best.p, max2, c->partials.p);
-        hipLaunchKernelGGL(k_rf_final<ICP_NSUM>, dim3(n_frames), dim3(64), 0, s, c->partials.p, c->fb0.p, c->ctrl.p, c->h_sums.p, c->d_misc.p);
+        hipLaunchKernelGGL(k_rf_final<ICP_NSUM>, dim3(n_frames), dim3(64), 0, s, c->partials.p, c->fb0.p, c->ctrl.p, c->h_sums.p, c->d_nun.p);
     }
     SCAL_HIP(hipGetLastError());
     SCAL_HIP(hipStreamSynchronize(s));
@@ -432,7 +396,6 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const float4* d_nc
             SCAL_HIP(hipMemcpyAsync(c->goff.p, c->h_goff.p, sizeof(int) * (K + 1), hipMemcpyHostToDevice, s));
             SCAL_HIP(hipMemcpyAsync(c->fb0.p, c->h_fb0.p, sizeof(int) * (K + 1), hipMemcpyHostToDevice, s));
             SCAL_HIP(hipMemcpyAsync(c->blocks.p, c->h_blocks.p, sizeof(RfBlock) * nb, hipMemcpyHostToDevice, s));
-            SCAL_HIP(hipMemcpyAsync(c->d_misc.p + 1, &c->h_goff.p[K], sizeof(int), hipMemcpyHostToDevice, s));
             SCAL_LAUNCH_PROF("k_rf_write", k_rf_write, dim3(nb_mm), dim3(256), 0, s, d_loc, c->mm_blocks.p, c->poses.p, near_thres, c->blk.p,
                              static_cast<long long>(n), c->g.p, c->frame_of.p);
             if constexpr (plane)
@@ -440,14 +403,8 @@ static int refine_rounds(scal_refine* c, const float4* d_loc, const float4* d_nc
                                  static_cast<long long>(n), c->gn.p);
             SCAL_HIP(hipMemcpyAsync(c->cur.p, c->g.p, sizeof(float4) * n, hipMemcpyDeviceToDevice, s));
             // 2. the neighbour index over G
-            SCAL_HIP(hipMemsetAsync(c->hkeys.p, 0xff, sizeof(unsigned long long) * (static_cast<size_t>(c->hmask) + 1), s));
             SCAL_HIP(hipMemsetAsync(c->best.p, 0xff, sizeof(unsigned long long) * n, s));
-            hipLaunchKernelGGL(k_rf_keys, dim3(div_up(n, 256)), dim3(256), 0, s, c->g.p, n, c->keys.p, c->vals.p);
-            SortedPairs sp;
-            SCAL_TRY(c->sorter.sort(s, c->keys.p, c->vals.p, c->d_misc.p + 1, n, RF_KEY_BITS, nullptr, &sp));
-            SCAL_LAUNCH_PROF("k_rf_index", k_rf_index, dim3(div_up(n, 256)), dim3(256), 0, s, sp.keys[sp.fixed_sel], sp.vals[sp.fixed_sel], n, c->g.p,
-                             c->sorted.p, c->hkeys.p, c->hrange.p, c->hmask);
-            SCAL_HIP(hipGetLastError());
+            SCAL_TRY(c->ix.build(s, c->g.p, n, 1.0f / RF_CELL, RF_FINITE));
             // 3. the iterations: one launch chain and one synchronisation each, for all frames still iterating
             bool first = true;
             for (;;) {
