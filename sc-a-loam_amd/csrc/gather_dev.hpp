@@ -1,5 +1,5 @@
 // Moving stored keyframe clouds: the f32 rigid transform of a point and the gather table of the kernels that concatenate several
-// keyframes (k_rl_submap, k_pgo_gather; k_kf_submap moves one range by one transform).
+// keyframes: k_submap_gather (submap.hip, every loop check's submap) and k_pgo_gather (keyframes.hip, the pose-graph map).
 #pragma once
 
 namespace scal {

@@ -3,8 +3,9 @@
 //  - the keyframe store (keyframeLaserClouds / keyframePoses, :629-637): stage D appends each keyframe's 0.4 m cloud - the output of
 //    ScanContext's keyframe filter, still in HBM - to an xyzi arena on the ScanContext stream (k_kf_append), nothing is read back;
 //  - the loop verification (loopFindNearKeyframesCloud / doICPVirtualRelative, :472-548) on a stream of its own: the source and the
-//    target submap are moved by the loop keyframe's pose (k_kf_submap: local2global, :338-359), filtered at 0.4 m by the device voxel
-//    filter and aligned by the exact-NN ICP; the acceptance test (:531) and the relative pose (:536-547) are computed on the host;
+//    target submap are moved by the loop keyframe's pose (local2global, :338-359: a one-entry gather table each for the shared
+//    SubmapVerifier of submap.hip), filtered at 0.4 m by the device voxel filter and aligned by the exact-NN ICP; the acceptance test
+//    (:531) and the relative pose (:536-547) are computed on the host;
 //  - the caller's optimized poses (updatePoses, :408-431 -> keyframePosesUpdated), versioned by the push counter so that each
 //    verification sees the poses that held when its query scan was pushed;
 //  - the pose-graph map (pubMap, :810-834) on a stream of its own: every skip-th keyframe moved by its current pose (k_pgo_gather: one
@@ -18,7 +19,7 @@
 namespace scal {
 
 // pubMap's local2global + concatenation (:815-822) of n_sel keyframes into map positions [0, n): position i lies in table entry s with
-// xf[s].dst <= i < xf[s + 1].dst and is arena record xf[s].src + (i - xf[s].dst), moved by xf[s].m exactly as k_kf_submap moves it.
+// xf[s].dst <= i < xf[s + 1].dst and is arena record xf[s].src + (i - xf[s].dst), moved by xf[s].m exactly as k_submap_gather moves it.
 // A fixed grid (<= 256 workgroups: the filter's key kernel reduces one bounding box per workgroup in every workgroup) of contiguous
 // chunks; each thread carries its table entry forward (positions only grow), so the table is searched once per workgroup.  Per point
 // one 16-byte load (PGO_ITEMS of them in flight per thread) and four coalesced 4-byte stores into the planes the filter reads.
@@ -86,15 +87,6 @@ __global__ void k_kf_append(const float* __restrict__ x, const float* __restrict
     }
     if (!fits) return;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) arena[base + i] = make_float4(x[i], y[i], z[i], w[i]);
-}
-
-// local2global (:338-359, xf_point) of keyframes j0 .. j1 (contiguous in the arena, in keyframe order) with ONE transform, into
-// out[0 .. n).  Streaming: one 16-byte load and one 16-byte store per point.
-__global__ void k_kf_submap(const float4* __restrict__ arena, const int* __restrict__ off, int j0, int j1, Aff34 T, float4* __restrict__ out,
-                            int* __restrict__ d_n_out) {
-    const int base = off[j0], n = off[j1 + 1] - base;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *d_n_out = n;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = xf_point(T.m, arena[base + i]);
 }
 
 // pcl::getTransformation (f32 Affine3f, R = Rz(yaw) Ry(pitch) Rx(roll)), as scaloam.pgo._affine_f32 states it: the sines and cosines
@@ -187,7 +179,6 @@ KeyframeStore::~KeyframeStore() {
     (void)hipSetDevice(device);
     if (vstream) (void)hipStreamSynchronize(vstream);
     if (mstream) (void)hipStreamSynchronize(mstream);
-    if (icp) scal_icp_destroy(icp);
 }
 
 int KeyframeStore::init(int dev, int points, int keyframes, int map_points) {
@@ -205,13 +196,10 @@ int KeyframeStore::init(int dev, int points, int keyframes, int map_points) {
     h_off.p[0] = 0, h_overflow.p[0] = 0;
     // verification: lane 5 (scal_pipeline's busy chains are on lanes 0, 1, 3 and 4)
     SCAL_TRY(vstream.acquire(dev, 5));
-    SCAL_TRY(vcf.init(points));
-    vcf.set_tag(".V");
-    for (DevBuf<float4>* b : {&raw_src, &raw_tgt, &ds_src, &ds_tgt}) SCAL_TRY(b->alloc(static_cast<size_t>(points)));
     scal_icp_config ic{};
-    ic.max_corr_dist = 150, ic.max_iterations = 100, ic.transformation_epsilon = 1e-6, ic.fitness_epsilon = 1e-6;  // :519-523
-    ic.max_source = points, ic.max_target = points, ic.device = dev;
-    SCAL_TRY(icp_create_on_lane(&ic, 5, &icp));
+    ic.max_corr_dist = LOOP_ICP_MAX_CORR_DIST, ic.max_iterations = LOOP_ICP_MAX_ITERATIONS;
+    ic.transformation_epsilon = LOOP_ICP_TRANSFORMATION_EPS, ic.fitness_epsilon = LOOP_ICP_FITNESS_EPS;
+    SCAL_TRY(v.init(dev, 5, points, 2, LOOP_LEAF, ic, ".V", "scal_pipeline: loop verification"));
     SCAL_HIP(hipMemsetAsync(d_off.p, 0, sizeof(int), vstream));
     SCAL_HIP(hipMemsetAsync(d_overflow.p, 0, sizeof(int), vstream));
     SCAL_HIP(hipStreamSynchronize(vstream));
@@ -309,35 +297,31 @@ int KeyframeStore::verify(const KfLoopJob& job, double fitness_thres, scal_pipel
         jc = own(job.curr_kf), jl = own(job.loop_kf);
         if (jc < 0 || jl < 0 || jc >= checked) return SCAL_OK;
         // loopFindNearKeyframesCloud(target, loop, 25, loop): keyframes loop-25 .. loop+25 that have a cloud, in keyframe order
-        const int submap = 25;  // historyKeyframeSearchNum (:502)
+        const int submap = LOOP_SUBMAP_HALF;
         j0 = static_cast<int>(std::lower_bound(db_of_own.begin(), db_of_own.end(), job.loop_kf - submap) - db_of_own.begin());
         j1 = static_cast<int>(std::upper_bound(db_of_own.begin(), db_of_own.end(), job.loop_kf + submap) - db_of_own.begin()) - 1;
         j1 = std::min(j1, checked - 1);
         // every keyframe is moved by the ROOT (loop) keyframe's pose (:506-507): keyframePosesUpdated's, as it was when scan seq was pushed
         T = affine_f32(pose_at(jl, job.seq).data());
     }
-    const int n_src = h_off.p[jc + 1] - h_off.p[jc], n_tgt = h_off.p[j1 + 1] - h_off.p[j0];
     SCAL_HIP(hipSetDevice(device));
     hipStream_t s = vstream;
     SCAL_HIP(hipStreamWaitEvent(s, ev_append, 0));  // behind the current keyframe's append (and every earlier one)
-    int n_ds[2] = {0, 0};
-    float4* raw[2] = {raw_src.p, raw_tgt.p};
-    float4* ds[2] = {ds_src.p, ds_tgt.p};
-    const int jr0[2] = {jc, j0}, jr1[2] = {jc, j1}, nr[2] = {n_src, n_tgt};
+    // the source [jc, jc], then the target [j0, j1]: a one-entry table with T and the sentinel over an arena range whose offsets the
+    // host has confirmed (jc < checked, j1 <= checked - 1); downSizeFilterICP (:491-492) behind the gather
+    float4* ds[2] = {v.ds_src.p, v.ds_tgt.p};
+    const int a[2] = {h_off.p[jc], h_off.p[j0]}, b[2] = {h_off.p[jc + 1], h_off.p[j1 + 1]};
+    int n_ds[2];
     for (int c = 0; c < 2; ++c) {
-        if (nr[c] <= 0) continue;
-        const int grid = std::min(div_up(nr[c], 256), 1024);
-        hipLaunchKernelGGL(k_kf_submap, dim3(grid), dim3(256), 0, s, arena.p, d_off.p, jr0[c], jr1[c], T, raw[c], vcf.d_n_in());
-        SCAL_HIP(hipGetLastError());
-        // downSizeFilterICP (:491-492): leaf 0.4, the voxel filter of scal_voxel_downsample_device (45 key bits)
-        vcf.load_counted(s, reinterpret_cast<const float*>(raw[c]), nr[c]);
-        SCAL_TRY(vcf.filter(s, nr[c], 0.4f));
-        vcf.store(s, nr[c], reinterpret_cast<float*>(ds[c]));
-        if ((n_ds[c] = vcf.wait(s, "scal_pipeline: loop verification")) < 0) return n_ds[c];
+        GatherXf* t = v.h_xf.p;  // free again: the source's run has waited
+        std::memset(t, 0, 2 * sizeof *t);
+        std::memcpy(t[0].m, T.m, sizeof T.m);
+        t[0].src = a[c], t[1].dst = b[c] - a[c];
+        if ((n_ds[c] = v.gather_filter(s, arena.p, 1, ds[c])) < 0) return n_ds[c];
     }
     out->n_src = n_ds[0], out->n_tgt = n_ds[1];
     scal_icp_result r;
-    SCAL_TRY(scal_icp_align_device(icp, reinterpret_cast<const float*>(ds_src.p), n_ds[0], reinterpret_cast<const float*>(ds_tgt.p), n_ds[1], &r));
+    SCAL_TRY(v.align(v.ds_src.p, n_ds[0], n_ds[1], nullptr, &r));
     out->converged = r.converged, out->iterations = r.iterations, out->state = r.state, out->fitness = r.fitness;
     std::memcpy(out->T, r.T, sizeof out->T);
     out->verified = (r.converged && r.fitness <= fitness_thres) ? 1 : 0;  // :531

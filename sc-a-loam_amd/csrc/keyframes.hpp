@@ -1,8 +1,7 @@
-// scal_pipeline's keyframe store and loop verification (sc_mode 3).  See keyframes.hip.
+// scal_pipeline's keyframe store and loop verification (sc_mode 3); the gather, filter and ICP of a verification are submap.hpp's
+// SubmapVerifier, shared with scal_reloc.  See keyframes.hip.
 #pragma once
-#include "common.hpp"
-#include "voxel_dev.hpp"
-#include "gather_dev.hpp"
+#include "submap.hpp"
 #include <array>
 #include <vector>
 
@@ -31,7 +30,7 @@ struct PoseVersion {
 struct KeyframeStore {
     int device = 0, max_points = 0, max_keyframes = 0;
     DevBuf<float4> arena;
-    DevBuf<int> d_off;       // [max_keyframes + 1], d_off[0] = 0
+    DevBuf<int> d_off;       // [max_keyframes + 1], d_off[0] = 0; read by k_kf_append only (every other reader takes h_off)
     DevBuf<int> d_overflow;  // set by k_kf_append when a keyframe does not fit (nothing is written then)
     PinBuf<int> h_off;       // host mirror of d_off, copied behind every append
     PinBuf<int> h_overflow;
@@ -41,11 +40,10 @@ struct KeyframeStore {
     std::vector<std::array<double, 6>> pose6;  // its Pose6D (getOdom)
     int checked = 0;                           // keyframes whose append has been confirmed on the host
     std::vector<std::vector<PoseVersion>> upd; // keyframe j's updated poses, oldest first (none: its gated pose holds)
-    // verification (own stream, lane 5): submaps, their 0.4 m filter, ICP
+    // verification (own stream, lane 5): the source's submap (one keyframe), then the target's, through one SubmapVerifier - its
+    // filter, its single raw buffer and its two-entry gather table are free again behind each cloud's wait
     LaneStream vstream;
-    CloudFilter vcf;          // the source's run, then the target's
-    DevBuf<float4> raw_src, raw_tgt, ds_src, ds_tgt;
-    scal_icp_t* icp = nullptr;
+    SubmapVerifier v;
     // pose-graph map (pubMap, :810-834; pgo_map_max_points > 0): its own stream (lane 2, which scal_pipeline's layout leaves empty),
     // filter and buffers; one map at a time (map_mu)
     int map_cap = 0;

@@ -105,7 +105,7 @@ struct scal_pipeline {
     // sc_mode 3: keyframe gate and store (stage D's thread), loops waiting for verification / to be popped
     KeyframeStore* kf = nullptr;
     scal_keyframe_gate_state gate{};
-    double fitness_thres = 0.3;
+    double fitness_thres = LOOP_FITNESS_THRES;
     std::deque<KfLoopJob> jobs;
     std::deque<scal_pipeline_loop> loops;
     bool verifying = false;
@@ -577,7 +577,7 @@ int create(const scal_pipeline_config* cfg, int n_seqs, scal_pipeline_t** out) {
     auto* p = new scal_pipeline();
     p->cfg = *cfg, p->ring = ring, p->depth = depth, p->S = n_seqs;
     p->gate = gate;
-    p->fitness_thres = cfg->loop_fitness_thres == 0 ? 0.3 : cfg->loop_fitness_thres;
+    p->fitness_thres = cfg->loop_fitness_thres == 0 ? LOOP_FITNESS_THRES : cfg->loop_fitness_thres;
     int rc = SCAL_OK;
     if (p->kf_mode()) {
         p->kf = new KeyframeStore();

@@ -44,7 +44,7 @@ def test_prefilled_entries_shift_kf_end():
 
 
 def test_f32_operation_order():
-    """each coordinate is ((T0 x + T1 y) + T2 z) + T3 with every product and sum rounded to f32 (k_kf_submap's order, no contraction)"""
+    """each coordinate is ((T0 x + T1 y) + T2 z) + T3 with every product and sum rounded to f32 (xf_point's order, no contraction)"""
     clouds, poses = _clouds(5), _poses(5)
     got = pgo_map_cloud(clouds, poses, 5, 1)
     rows, other = [], []

@@ -481,6 +481,32 @@ def test_reloc_other_place_and_candidate_alone(S, clouds, queries):
     icp.close(), rl.close()
 
 
+@pytest.mark.parametrize("empty_at", (0, 2), ids=("first_of_the_window", "behind_the_candidate"))
+def test_reloc_submap_entries_that_share_a_dst(S, clouds, queries, empty_at):
+    """A stored keyframe without points gives the submap's gather table an entry that shares its dst with the next one (or with the
+    sentinel): gather_find has to take the LAST entry with dst <= i.  Keyframes 0 / 7 / 20 with one of the candidate's neighbours empty,
+    submap_half = 1, the 90 degree query: n_tgt and the whole ICP record against the chain rebuilt outside from the non-empty parts."""
+    vg, poses, stored = clouds["vg"], clouds["poses"], clouds["stored"]
+    gm = S.SCManager()
+    far = gm.makeScancontext(stored[3])  # the empty keyframe is stored with another place's descriptor: the search is left alone
+    rl = S.Relocalizer(max_keyframes=4, max_points=100000, max_query_points=70000, submap_half=1)
+    for j in range(3):
+        if j == empty_at:
+            assert rl.add_keyframe(np.zeros((0, 4), np.float32), poses[j], desc=far) == j
+        else:
+            assert rl.add_keyframe(clouds["raw"][j], poses[j]) == j
+    r = rl.query(queries[1])
+    assert r["sc"]["loop_id"] == 1 and r["sc"]["nn_idx"] == 1
+    parts = [stored[j] if j == 1 else _apply34(S.relative_transform(poses[1], poses[j]), stored[j]) for j in range(3) if j != empty_at]
+    src, tgt = vg.filter(queries[1], 0.4), vg.filter(np.concatenate(parts), 0.4)
+    icp = S.LoopICP(max_source=70000, max_target=70000)
+    ref = icp.align(src, tgt, guess=S.yaw_guess(r["sc"]["yaw"]))
+    print(empty_at, r["status"], r["n_tgt"], tgt.shape[0], r["icp"]["fitness"], ref["fitness"], r["icp"]["iterations"], ref["iterations"])
+    assert r["n_src"] == src.shape[0] and r["n_tgt"] == tgt.shape[0]
+    assert _icp_same(ref, r["icp"])  # fitness and T depend on every bit of both clouds
+    icp.close(), gm.close(), rl.close()
+
+
 def test_reloc_batch_equals_single_calls_and_repeats(clouds, session, queries, singles):
     extra = [clouds["raw"][4], np.zeros((0, 4), np.float32), clouds["raw"][0][:5000]]
     every = list(queries) + extra

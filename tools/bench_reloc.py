@@ -61,7 +61,7 @@ def same_record(a, b):
 
 
 STAGES = (("filter", ("k_vox", "k_deinterleave", "k_interleave4", "k_radix", "k_sort")), ("descriptor", ("k_sc_bin", "k_sc_finish")),
-          ("search", ("k_sc_keys", "k_sc_topk", "k_sc_detect")), ("submap", ("k_rl_submap",)), ("icp_neighbours", ("k_icp",)))
+          ("search", ("k_sc_keys", "k_sc_topk", "k_sc_detect")), ("submap", ("k_submap_gather",)), ("icp_neighbours", ("k_icp",)))
 
 
 def stage_ms(prof, n):
