@@ -185,7 +185,8 @@ def relative_pose_from_icp(T):
 # Parity with GTSAM is unpinned: which Pose3 chart the reference's build used cannot be found out.
 SERIES_THETA = 0.1     # below: the coefficient functions of Exp / Log / Jr^-1 by their series (4 terms, error < 1e-15 relative)
 SERIES_SINE = 1e-4     # below (|vector part| of the quaternion): atan by its series in the rotation logarithm
-PG_DEFAULTS = dict(max_iterations=50, step_tol=1e-8, lambda_first=1e-4, lambda_factor=10.0, lambda_max=1e8)
+PG_DEFAULTS = dict(max_iterations=50, step_tol=1e-8, lambda_first=1e-4, lambda_factor=10.0, lambda_max=1e8,
+                   linear="splu", linear_rtol=1e-12, max_linear_iterations=2000)
 PRIOR_VARIANCES = (1e-12,) * 6                              # :286-288
 ODOM_VARIANCES = (1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4)       # :292
 LOOP_VARIANCES = (0.5,) * 6                                 # :295
@@ -405,21 +406,169 @@ def whitened_residuals(poses, prior, edges, jacobians=False):
     return ep, e, w, cost, Jp * sp[:, None], Ji * se[:, :, None], Jj * se[:, :, None]
 
 
+# ---- the device's linear solver restated (csrc/posegraph.hip: k_pg_assemble, k_pg_offdiag, k_pg_pcr_*, solve()): numpy only.
+# H is kept the way the device keeps it: the diagonal blocks D[n] and one block O[e] = A_i^T A_j per between edge, H[i, j] += O[e],
+# H[j, i] += O[e]^T.  The same algorithm in the same order of steps, not the same bits: sums run in numpy's order.
+def _blocks(n, prior, edges, w, ep, e, Jp, Ji, Jj):
+    sw = np.sqrt(w)
+    Ai, Aj, b = Ji * sw[:, None, None], Jj * sw[:, None, None], e * sw[:, None]
+    ei, ej = edges["i"].astype(np.int64), edges["j"].astype(np.int64)
+    D, g = np.zeros((n, 6, 6)), np.zeros((n, 6))
+    pn = int(prior["node"])
+    D[pn] += Jp.T @ Jp
+    g[pn] += Jp.T @ ep
+    np.add.at(D, ei, np.einsum("eki,ekj->eij", Ai, Ai))
+    np.add.at(D, ej, np.einsum("eki,ekj->eij", Aj, Aj))
+    np.add.at(g, ei, np.einsum("eki,ek->ei", Ai, b))
+    np.add.at(g, ej, np.einsum("eki,ek->ei", Aj, b))
+    return dict(D=D, i=ei, j=ej, O=np.einsum("eki,ekj->eij", Ai, Aj)), g
+
+
+def normal_blocks(poses, prior, edges, lam=0.0):
+    """H = J^T J in 6x6 blocks (dict: D[n, 6, 6] the diagonal blocks, i, j, O[m, 6, 6] with H[i, j] += O, H[j, i] += O^T per edge) and
+    g = J^T b as [n, 6], robust rows scaled by sqrt(w) as optimize_pose_graph does; damping lam * diag(H) on the diagonal"""
+    poses = np.asarray(poses, np.float64).reshape(-1, 7)
+    ep, e, w, _, Jp, Ji, Jj = whitened_residuals(poses, prior, edges, True)
+    H, g = _blocks(len(poses), prior, edges, w, ep, e, Jp, Ji, Jj)
+    return damped_blocks(H, lam), g
+
+
+def damped_blocks(H, lam):
+    """H + lam diag(H) (k_pg_assemble: d += lambda * d on the diagonal)"""
+    if lam == 0:
+        return H
+    D = H["D"].copy()
+    k = np.arange(6)
+    D[:, k, k] += lam * D[:, k, k]
+    return dict(H, D=D)
+
+
+def blocks_matvec(H, p):
+    """H p for p [n, 6] (k_pg_hp)"""
+    q = np.einsum("nij,nj->ni", H["D"], p)
+    np.add.at(q, H["i"], np.einsum("eij,ej->ei", H["O"], p[H["j"]]))
+    np.add.at(q, H["j"], np.einsum("eji,ej->ei", H["O"], p[H["i"]]))
+    return q
+
+
+def blocks_dense(H, tridiagonal=False):
+    """H as a dense [6 n, 6 n] matrix; tridiagonal: only M, the diagonal blocks and the blocks between neighbouring nodes"""
+    n = len(H["D"])
+    A = np.zeros((n, 6, n, 6))
+    k = np.arange(n)
+    A[k, :, k, :] = H["D"]
+    for a, b, O in zip(H["i"], H["j"], H["O"]):
+        if tridiagonal and abs(int(a) - int(b)) != 1:
+            continue
+        A[a, :, b, :] += O
+        A[b, :, a, :] += O.T
+    return A.reshape(6 * n, 6 * n)
+
+
+def _upper_blocks(H):
+    """U[k] = H[k, k + 1] (k_pg_assemble's block towards node + 1; zero for the last node, k_pg_pcr_init)"""
+    n = len(H["D"])
+    U = np.zeros((n, 6, 6))
+    fwd, bwd = H["j"] == H["i"] + 1, H["i"] == H["j"] + 1
+    np.add.at(U, H["i"][fwd], H["O"][fwd])
+    np.add.at(U, H["j"][bwd], np.swapaxes(H["O"][bwd], 1, 2))
+    return U
+
+
+def pcr_factor(H):
+    """Parallel cyclic reduction of M, the block-tridiagonal part of H (rows L_i, D_i, U_i, L_i = U_{i-1}^T), as k_pg_pcr_init and
+    k_pg_pcr_level do it: levels s = 1, 2, 4, ... while s < n, every row in each: alpha = L_i Dinv_{i-s}, gamma = U_i Dinv_{i+s},
+    D' = D - alpha U_{i-s} - gamma L_{i+s}, L' = -alpha L_{i-s}, U' = -gamma U_{i+s} (terms whose row does not exist are left out).
+    Returns the multipliers of every level and the last level's Dinv."""
+    D = H["D"].copy()
+    n = len(D)
+    U = _upper_blocks(H)
+    L = np.zeros_like(U)
+    L[1:] = np.swapaxes(U[:-1], 1, 2)
+    Di = np.linalg.inv(D)
+    levels, s = [], 1
+    while s < n:
+        al, ga = np.zeros_like(D), np.zeros_like(D)
+        al[s:] = L[s:] @ Di[:-s]
+        ga[:-s] = U[:-s] @ Di[s:]
+        Dn, Ln, Un = D.copy(), np.zeros_like(D), np.zeros_like(D)
+        Dn[s:] -= al[s:] @ U[:-s]
+        Ln[s:] = -(al[s:] @ L[:-s])
+        Dn[:-s] -= ga[:-s] @ L[s:]
+        Un[:-s] = -(ga[:-s] @ U[s:])
+        D, L, U = Dn, Ln, Un
+        Di = np.linalg.inv(D)
+        levels.append((s, al, ga))
+        s *= 2
+    return dict(levels=levels, Dinv=Di)
+
+
+def pcr_solve(factor, r):
+    """M^-1 r for r [n, 6]: per level out_i = in_i - alpha_i in_{i-s} - gamma_i in_{i+s} (k_pg_pcr_apply), then Dinv_i in_i
+    (k_pg_pcr_final)"""
+    v = np.array(r, np.float64).reshape(-1, 6)
+    for s, al, ga in factor["levels"]:
+        out = v.copy()
+        out[s:] -= np.einsum("nij,nj->ni", al[s:], v[:-s])
+        out[:-s] -= np.einsum("nij,nj->ni", ga[:-s], v[s:])
+        v = out
+    return np.einsum("nij,nj->ni", factor["Dinv"], v)
+
+
+def pcg_solve(H, g, rtol=1e-12, max_iterations=2000):
+    """H d = -g by conjugate gradients preconditioned with pcr_solve, the loop of solve() in csrc/posegraph.hip: stop when
+    r . M^-1 r <= rtol^2 times its first value.  Returns d [n, 6], the iterations and the status (0 met the tolerance, 1 the bound
+    hit, 2 breakdown: a curvature or r . M^-1 r that is not positive and finite)."""
+    g = np.asarray(g, np.float64).reshape(-1, 6)
+    F = pcr_factor(H)
+    d, r = np.zeros_like(g), -g
+    z = pcr_solve(F, r)
+    rz = rz0 = float(np.sum(r * z))
+    if not rz > 0:
+        return d, 0, (0 if rz == 0 else 2)
+    p, it = z, 0
+    while True:
+        q = blocks_matvec(H, p)
+        pq = float(np.sum(p * q))
+        if not (pq > 0 and np.isfinite(pq)):
+            return d, it, 2
+        a = rz / pq
+        d = d + a * p
+        r = r - a * q
+        z = pcr_solve(F, r)
+        rzn = float(np.sum(r * z))
+        it += 1
+        if not np.isfinite(rzn) or rzn < 0:
+            return d, it, 2
+        beta, rz = rzn / rz, rzn
+        if rz <= rtol * rtol * rz0:
+            return d, it, 0
+        if it >= max_iterations:
+            return d, it, 1
+        p = z + beta * p
+
+
 def optimize_pose_graph(poses, prior, edges, params=None):
     """Batch Gauss-Newton over the graph, robust rows reweighted as gtsam's noiseModel::Robust does (row block and right-hand side
     times sqrt(w), no second-order term); exact sparse solve of the normal equations.  A step that raises the cost is rejected and
     solved again with Levenberg damping lambda diag(H) (lambda_first, then times lambda_factor); damping is dropped after an accepted
     step.  Stops (converged) when a step's max-norm is below step_tol.  Returns poses, stats(costs per iteration starting with the
-    initial one, step_norms, weights at the returned estimate, iterations, converged)."""
+    initial one, step_norms, weights at the returned estimate, iterations, converged, trials: (cost, trial cost, step, accepted) of
+    every solve, rejected: (cost, trial cost) of the rejected ones).  params linear="pcg" solves with pcg_solve (linear_rtol,
+    max_linear_iterations) in place of splu, as the device does: a solve that does not meet its tolerance ends the run with the
+    last accepted poses; linear_iterations is summed over the solves."""
     import scipy.sparse as sp
     import scipy.sparse.linalg as spl
     P = dict(PG_DEFAULTS)
     P.update(params or {})
+    if P["linear"] not in ("splu", "pcg"):
+        raise ValueError("linear is 'splu' or 'pcg'")
     x = np.array(poses, np.float64).reshape(-1, 7)
     n, m = len(x), len(edges["i"])
     _, _, _, cost = whitened_residuals(x, prior, edges)
     costs, steps = [cost], []
     converged, lam, it = 0, 0.0, 0
+    pcg, lin_its, lin_status, trials = P["linear"] == "pcg", 0, 0, []
     ar6 = np.arange(6)
     rows_e = (6 * np.arange(m)[:, None, None] + ar6[None, :, None] + 6) + np.zeros((1, 1, 6), np.int64)
     cols_i = 6 * edges["i"].astype(np.int64)[:, None, None] + ar6[None, None, :] + np.zeros((1, 6, 1), np.int64)
@@ -435,14 +584,23 @@ def optimize_pose_graph(poses, prior, edges, params=None):
                             np.concatenate([cols_p.reshape(-1), cols_i.reshape(-1), cols_j.reshape(-1)]))), shape=(6 * m + 6, 6 * n))
         H = (J.T @ J).tocsc()
         g = J.T @ b
+        if pcg:
+            Hb, gb = _blocks(n, prior, edges, w, ep, e, Jp, Ji, Jj)
         while True:
             it += 1
-            A = H if lam == 0 else (H + lam * sp.diags(H.diagonal())).tocsc()
-            d = spl.splu(A).solve(-g).reshape(n, 6)
+            if pcg:
+                d, k, lin_status = pcg_solve(damped_blocks(Hb, lam), gb, P["linear_rtol"], P["max_linear_iterations"])
+                lin_its += k
+                if lin_status != 0:
+                    break
+            else:
+                A = H if lam == 0 else (H + lam * sp.diags(H.diagonal())).tocsc()
+                d = spl.splu(A).solve(-g).reshape(n, 6)
             step = float(np.abs(d).max()) if n else 0.0
             xn = se3_retract(x, d)
             _, _, _, cn = whitened_residuals(xn, prior, edges)
-            ok = np.isfinite(cn) and cn <= cost
+            ok = bool(np.isfinite(cn) and cn <= cost)
+            trials.append((cost, cn, step, ok))
             if ok:
                 x, lam = xn, 0.0
                 costs.append(cn)
@@ -453,10 +611,12 @@ def optimize_pose_graph(poses, prior, edges, params=None):
                 converged = 1
             if ok or converged or it >= P["max_iterations"] or lam > P["lambda_max"]:
                 break
-        if converged or lam > P["lambda_max"]:
+        if converged or lam > P["lambda_max"] or lin_status != 0:
             break
     _, _, w, cost = whitened_residuals(x, prior, edges)
-    return x, dict(costs=costs, step_norms=steps, weights=w, iterations=it, converged=converged, final_cost=cost)
+    return x, dict(costs=costs, step_norms=steps, weights=w, iterations=it, converged=converged, final_cost=cost, trials=trials,
+                   rejected=[(c, cn) for c, cn, _, ok in trials if not ok],
+                   linear_iterations=lin_its, linear_status=lin_status)
 
 
 def build_pipeline_graph(gated_poses6, loop_records, kf_ids=None):
@@ -531,3 +691,77 @@ def out_and_back_graph(n_nodes, n_loops, **kw):
     true6 = np.stack([x, 0.3 * (k >= half) + 0.0 * k, 0.001 * k, 0.0 * k, 0.005 * np.sin(0.1 * k), yaw], 1)
     lj = half + 2 + (np.arange(n_loops) * (n_nodes - half - 3)) // max(n_loops, 1)
     return synthetic_graph(true6, 2 * half - lj, lj, **kw)
+
+
+def reverse_edges(edges, which):
+    """the same graph with the chosen edges (index array or boolean mask) entered from their other end: (i, j, Z) -> (j, i, Z^-1).
+    The reversed residual is -Ad(Z) r: the same zero, but not the same whitened norm, so the optimum is the same only where the
+    reversed edges' residuals vanish at it (a consistent graph)."""
+    out = {key: edges[key].copy() for key in ("i", "j", "z", "var", "k")}
+    sel = np.zeros(len(edges["i"]), bool)
+    sel[np.asarray(which)] = True
+    out["i"][sel], out["j"][sel] = edges["j"][sel], edges["i"][sel]
+    out["z"][sel] = se3_inverse(edges["z"][sel])
+    return out
+
+
+def reorder_edges(edges, order):
+    """the same edges added in another order"""
+    order = np.asarray(order, np.int64)
+    return {key: edges[key][order].copy() for key in ("i", "j", "z", "var", "k")}
+
+
+def interleave_order(n_odo, n_loops):
+    """an add order that spreads the loop edges (n_odo ...) evenly between the odometry edges (0 ... n_odo - 1), the first loop first"""
+    at = (np.arange(n_loops) * n_odo) // max(n_loops, 1)
+    key = np.concatenate([np.arange(n_odo) + 0.5, at.astype(np.float64)])
+    return np.argsort(key, kind="stable")
+
+
+def prior_at(init, node):
+    """a prior (the node's variances) that holds `node` at its initial pose"""
+    return dict(node=int(node), pose7=np.array(init[int(node)], np.float64), var=np.array(PRIOR_VARIANCES))
+
+
+GRAPH_VARIANTS = ("plain", "prior_last", "prior_middle", "prior_displaced", "loops_reversed", "odometry_alternate_reversed", "interleaved",
+                  "parallel_loop", "parallel_loop_reversed", "double_loop", "tight_loops", "tight_loops_reversed")
+
+
+def graph_variant(init, prior, edges, variant):
+    """Another form of a synthetic_graph (odometry edges (k, k + 1) first, then the loops) for the tests of the device's index
+    handling: the prior on the last or a middle node, or on node 0 but 0.2 rad and 0.4 m away from its initial pose; all loop edges
+    or every second odometry edge entered from the other end; the loops spread between the odometry edges in the add order; one more
+    Cauchy loop edge on the nodes of odometry edge n // 3 (its measurement, entered as (k, k + 1) or as (k + 1, k)); the first loop
+    edge twice; the loops with the odometry's variances and no robust kernel (they carry as much of a step as the chain does: their
+    Jacobians show in its leading digits, and H is far from its block-tridiagonal part), also entered from their other end.  Returns
+    init, prior, edges."""
+    n, m = len(init), len(edges["i"])
+    n_odo = n - 1
+    if variant == "plain":
+        return init, prior, edges
+    if variant == "prior_last":
+        return init, prior_at(init, n - 1), edges
+    if variant == "prior_middle":
+        return init, prior_at(init, n // 2), edges
+    if variant == "prior_displaced":
+        P = dict(prior, pose7=se3_retract(np.asarray(prior["pose7"], np.float64), np.array([0.15, -0.1, 0.09, 0.3, -0.2, 0.15])))
+        return init, P, edges
+    if variant == "loops_reversed":
+        return init, prior, reverse_edges(edges, np.arange(n_odo, m))
+    if variant == "odometry_alternate_reversed":
+        return init, prior, reverse_edges(edges, np.arange(1, n_odo, 2))
+    if variant == "interleaved":
+        return init, prior, reorder_edges(edges, interleave_order(n_odo, m - n_odo))
+    if variant in ("parallel_loop", "parallel_loop_reversed"):
+        k = n // 3
+        extra = make_edges([k], [k + 1], edges["z"][k], LOOP_VARIANCES, LOOP_CAUCHY_K)
+        if variant == "parallel_loop_reversed":
+            extra = reverse_edges(extra, [0])
+        return init, prior, concat_edges(edges, extra)
+    if variant in ("tight_loops", "tight_loops_reversed"):
+        out = {key: edges[key].copy() for key in ("i", "j", "z", "var", "k")}
+        out["var"][n_odo:], out["k"][n_odo:] = ODOM_VARIANCES, 0.0
+        return init, prior, reverse_edges(out, np.arange(n_odo, m)) if variant == "tight_loops_reversed" else out
+    if variant == "double_loop":
+        return init, prior, concat_edges(edges, reorder_edges(edges, [n_odo]))
+    raise ValueError("unknown variant %r" % (variant,))

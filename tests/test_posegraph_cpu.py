@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import posegraph_cases as PC
 from scaloam import pgo as G
 
 
@@ -161,3 +162,178 @@ def test_capi_argument_checks_and_no_device(S):
     assert L.scal_posegraph_get_edge_weights(None, z6.ctypes.data_as(f64p), 0) == S.E_ARG
     assert L.scal_pipeline_optimize_keyframes(None, 0, 0, None, None, 0, None) == S.E_ARG
     L.scal_posegraph_destroy(None)
+
+
+# ---------------------------------------------------------------------------------------------- the restated linear solver
+# (pgo.normal_blocks / pcr_factor / pcr_solve / pcg_solve: what csrc/posegraph.hip's solve() does, in numpy) and the properties of the
+# small graphs that tests/test_posegraph_small_gpu.py relies on.
+CASES = PC.cases()
+ALL_CASES = {**CASES["one_step"], **CASES["variants"], **CASES["chains"], **CASES["damping"]}
+
+
+def _pose_diff(a, b):
+    d = G.se3_log(G.se3_between(a, b))
+    return max(np.abs(a[:, 4:] - b[:, 4:]).max(), np.abs(d[:, :3]).max())
+
+
+def _angles(init, edges):
+    r = G.between_residual(init[edges["i"]], init[edges["j"]], edges["z"])
+    return np.linalg.norm(r[:, :3], axis=1)
+
+
+def test_normal_blocks_are_the_normal_equations():
+    """H and g in blocks against J^T J and J^T b assembled densely from whitened_residuals, with and without damping; blocks_matvec"""
+    init, prior, edges = PC.small_graph(9, 2, 0.3, "parallel_loop_reversed")
+    n, m = len(init), len(edges["i"])
+    ep, e, w, _, Jp, Ji, Jj = G.whitened_residuals(init, prior, edges, True)
+    J, b = np.zeros((6 * m + 6, 6 * n)), np.concatenate([ep, (e * np.sqrt(w)[:, None]).reshape(-1)])
+    J[:6, 6 * prior["node"]:6 * prior["node"] + 6] = Jp
+    for k in range(m):
+        J[6 * k + 6:6 * k + 12, 6 * edges["i"][k]:6 * edges["i"][k] + 6] = Ji[k] * np.sqrt(w[k])
+        J[6 * k + 6:6 * k + 12, 6 * edges["j"][k]:6 * edges["j"][k] + 6] = Jj[k] * np.sqrt(w[k])
+    Hd = J.T @ J
+    for lam in (0.0, 1e-4):
+        H, g = G.normal_blocks(init, prior, edges, lam)
+        want = Hd + lam * np.diag(np.diag(Hd))
+        assert np.abs(G.blocks_dense(H) - want).max() <= 1e-12 * np.abs(want).max()
+        assert np.abs(g.reshape(-1) - J.T @ b).max() <= 1e-12 * np.abs(J.T @ b).max()
+        p = np.random.default_rng(0).normal(size=(n, 6))
+        assert np.abs(G.blocks_matvec(H, p).reshape(-1) - want @ p.reshape(-1)).max() <= 1e-12 * np.abs(want @ p.reshape(-1)).max()
+    # M keeps the parallel loop edge's block and drops the other loops'
+    M = G.blocks_dense(H, tridiagonal=True).reshape(n, 6, n, 6)
+    A = G.blocks_dense(H).reshape(n, 6, n, 6)
+    for a in range(n):
+        for c in range(n):
+            assert np.array_equal(M[a, :, c, :], A[a, :, c, :] if abs(a - c) <= 1 else np.zeros((6, 6)))
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 6, 7, 8, 9, 14, 15, 32, 33, 100])
+def test_pcr_against_a_dense_solve(n):
+    """pcr_solve(pcr_factor(H), r) against numpy's dense solve of the block-tridiagonal part, on a looped graph (M != H) where n
+    allows loops: relative error <= 1e-6 of |solution|_inf (observed <= 3.2e-12 at cond(H) up to 4e12)"""
+    init, prior, edges = PC.prior_only_graph() if n == 1 else PC.small_graph(n, {1: 0, 2: 0}.get(n, max(1, n // 8)), 0.3, "prior_middle" if n % 2 else "plain")
+    H, _ = G.normal_blocks(init, prior, edges)
+    F = G.pcr_factor(H)
+    assert len(F["levels"]) == int(np.ceil(np.log2(n))) if n > 1 else len(F["levels"]) == 0
+    r = np.random.default_rng(n).normal(size=(n, 6))
+    want = np.linalg.solve(G.blocks_dense(H, tridiagonal=True), r.reshape(-1)).reshape(n, 6)
+    err = np.abs(G.pcr_solve(F, r) - want).max() / np.abs(want).max()
+    print("n", n, "relative error", err)
+    assert err <= 1e-6
+
+
+@pytest.mark.parametrize("name", list(CASES["chains"]))
+def test_chain_only_graphs_need_at_most_two_pcg_iterations(name):
+    init, prior, edges = PC.small_graph(*CASES["chains"][name])
+    H, g = G.normal_blocks(init, prior, edges)
+    d, its, status = G.pcg_solve(H, g)
+    assert status == 0 and 1 <= its <= 2
+    assert _angles(init, edges).min() >= 0.1
+
+
+@pytest.mark.parametrize("name", list(ALL_CASES))
+def test_pcg_against_a_dense_solve(name):
+    """the first system of every small graph: pcg_solve within 1e-8 (the optimizer's step_tol) of numpy's dense solve; observed
+    <= 4.7e-10"""
+    init, prior, edges = PC.small_graph(*ALL_CASES[name])
+    H, g = G.normal_blocks(init, prior, edges)
+    d, its, status = G.pcg_solve(H, g)
+    want = np.linalg.solve(G.blocks_dense(H), -g.reshape(-1)).reshape(-1, 6)
+    print(name, "iterations", its, "max |d_pcg - d_dense|", np.abs(d - want).max(), "max |d|", np.abs(want).max())
+    assert status == 0 and np.abs(d - want).max() <= 1e-8
+
+
+def test_pcg_reports_the_bound_and_a_breakdown():
+    init, prior, edges = PC.small_graph(33, 4, 0.3)
+    H, g = G.normal_blocks(init, prior, edges)
+    d, its, status = G.pcg_solve(H, g, max_iterations=2)
+    assert (its, status) == (2, 1)
+    d, its, status = G.pcg_solve(H, np.zeros_like(g))
+    assert (its, status) == (0, 0) and not d.any()
+    H["O"][-1] *= 1e4     # a loop's off-diagonal block that its nodes' diagonal blocks do not cover: H is indefinite, M is not
+    assert G.pcg_solve(H, g)[2] == 2
+
+
+@pytest.mark.parametrize("name", list(CASES["one_step"]))
+def test_one_step_inputs(name):
+    """what the device's one-step tests assume of their graphs: the first Gauss-Newton step is accepted with room (trial cost <= 0.99 x
+    the cost), the pcg restatement makes the same step as splu within 1e-8 (observed <= 2.7e-10), perturb 0.3 has every residual angle
+    on the closed-form side of 0.1 rad and perturb 0.05 has angles below it"""
+    n, loops, perturb, _, _ = CASES["one_step"][name]
+    init, prior, edges = PC.small_graph(*CASES["one_step"][name])
+    x, s = G.optimize_pose_graph(init, prior, edges, dict(max_iterations=1))
+    xp, sp = G.optimize_pose_graph(init, prior, edges, dict(max_iterations=1, linear="pcg"))
+    assert not s["rejected"] and not sp["rejected"] and s["final_cost"] <= 0.99 * s["costs"][0]
+    assert _pose_diff(x, xp) <= 1e-8 and sp["linear_status"] == 0 and sp["linear_iterations"] >= 1
+    a = _angles(init, edges)
+    if n == 1:      # no between edge: the prior's own residual is on the closed-form side
+        assert np.linalg.norm(G.prior_residual(init[0], prior["pose7"])[:3]) >= 0.1
+    elif perturb == 0.3:
+        assert a.min() >= 0.1
+    else:
+        assert a.min() < 0.1
+
+
+def test_mixed_case_has_angles_on_both_sides_of_the_switch():
+    init, prior, edges = PC.small_graph(33, 4, 0.05)
+    a = _angles(init, edges)
+    assert (a < 0.1).sum() >= 5 and (a >= 0.1).sum() >= 5
+
+
+def test_damping_case_rejects_its_first_step():
+    """33 nodes, 4 loops, perturb 0.5, seed 1: the first step raises the cost from 4.90e7 to 8.92e7 (1.82 x, no knife edge), the run
+    converges all the same, to the optimum of the perturb 0.3 graph (same seed: same measurements); pcg makes the same decisions"""
+    init, prior, edges = PC.small_graph(*CASES["damping"][PC.DAMPING_CASE])
+    x1, s1 = G.optimize_pose_graph(init, prior, edges, dict(max_iterations=1))
+    assert len(s1["rejected"]) == 1 and s1["rejected"][0][1] >= 1.01 * s1["rejected"][0][0]
+    assert np.array_equal(x1, init) and s1["converged"] == 0 and s1["final_cost"] == s1["costs"][0] and s1["iterations"] == 1
+    x, s = G.optimize_pose_graph(init, prior, edges)
+    xp, sp = G.optimize_pose_graph(init, prior, edges, dict(linear="pcg"))
+    assert s["converged"] == 1 and sp["converged"] == 1 and s["iterations"] == sp["iterations"] == 9
+    assert s["rejected"][0][1] >= 1.01 * s["rejected"][0][0] and sp["rejected"][0][1] >= 1.01 * sp["rejected"][0][0]
+    assert _pose_diff(x, xp) <= 1e-7
+    y, t = G.optimize_pose_graph(*PC.small_graph(33, 4, 0.3))
+    assert _pose_diff(x, y) <= 1e-7 and abs(s["final_cost"] - t["final_cost"]) <= 1e-9 * t["final_cost"]
+
+
+@pytest.mark.parametrize("variant,noise", [("loops_reversed", 0.0), ("odometry_alternate_reversed", 0.0), ("parallel_loop_reversed", 0.0),
+                                           ("interleaved", 0.0), ("interleaved", 1.0)])
+def test_reversed_and_reordered_forms_have_the_same_optimum(variant, noise):
+    """(i, j, Z) -> (j, i, Z^-1) and another add order leave the restatement's optimum where it was, within 1e-9.  A reversed edge's
+    residual is -Ad(Z) r - the same zero, another whitened norm - so the reversed forms are compared on the consistent graph (noise 0:
+    every residual vanishes at the optimum); with noise the optimum itself moves, by 6.6e-6 (loops) and 1.2e-4 (odometry) here.
+    parallel_loop_reversed is compared with parallel_loop."""
+    plain = "parallel_loop" if variant.startswith("parallel") else "plain"
+    x, s = G.optimize_pose_graph(*PC.small_graph(33, 4, 0.3, plain, noise))
+    y, t = G.optimize_pose_graph(*PC.small_graph(33, 4, 0.3, variant, noise))
+    print(variant, noise, "pose difference", _pose_diff(x, y), "iterations", s["iterations"], t["iterations"])
+    assert s["converged"] == 1 and t["converged"] == 1
+    assert _pose_diff(x, y) <= 1e-9
+    if "reversed" in variant:   # the first residuals: -Ad(Z) r
+        init, prior, e0 = PC.small_graph(33, 4, 0.3, plain, noise)
+        _, _, e1 = PC.small_graph(33, 4, 0.3, variant, noise)
+        r0 = G.between_residual(init[e0["i"]], init[e0["j"]], e0["z"])
+        r1 = G.between_residual(init[e1["i"]], init[e1["j"]], e1["z"])
+        rev = e0["i"] != e1["i"]
+        assert rev.any() and np.array_equal(e0["i"][rev], e1["j"][rev])
+        want = -np.einsum("eij,ej->ei", G.se3_adjoint(e0["z"][rev]), r0[rev])
+        assert np.abs(r1[rev] - want).max() <= 1e-9 * np.abs(want).max() and np.array_equal(r0[~rev], r1[~rev])
+
+
+@pytest.mark.parametrize("name", [k for k, v in ALL_CASES.items() if v[1] > 0])
+def test_looped_runs_decide_with_room_at_the_counting_step_tol(name):
+    """The device's count of CG iterations is compared with the restatement's over whole runs, which holds only while both make the
+    same accept / reject decisions and end on the same step.  At the default step_tol the last steps change the cost by parts in
+    1e13: rounding decides (a cost of 0.04 summed from whitened residuals of order 0.1, each known to about 1e-12, is known to a few
+    parts in 1e10).  At COUNTING_STEP_TOL = 1e-5 every decision that a count depends on (steps >= the tolerance; the ending step's
+    own decision changes no count) has a relative margin >= 1e-9 - observed >= 3.8e-8 - and no step is within 10 % of the tolerance."""
+    init, prior, edges = PC.small_graph(*ALL_CASES[name])
+    tol = PC.COUNTING_STEP_TOL
+    x, s = G.optimize_pose_graph(init, prior, edges, dict(step_tol=tol, linear="pcg"))
+    y, t = G.optimize_pose_graph(init, prior, edges, dict(step_tol=tol))
+    assert s["converged"] == 1 and s["linear_status"] == 0 and t["iterations"] == s["iterations"]
+    margins = [abs(cn - c) / c for c, cn, step, ok in s["trials"] if step >= tol]
+    print(name, "iterations", s["iterations"], "linear", s["linear_iterations"], "smallest margin", min(margins))
+    assert min(margins) >= 1e-9
+    assert all(not (0.9 * tol <= step <= 1.1 * tol) for _, _, step, _ in s["trials"])
+    assert s["trials"][-1][2] < tol and all(step >= tol for _, _, step, _ in s["trials"][:-1])
